@@ -20,7 +20,14 @@ the GPU's shard.  Multi-GPU: one process per GPU, no collective on the data path
 distinct keys, 1M VRF verifies + leader checks, 1M Sum6KES verifies), c1 the
 10k-block / 100-pool chain of configs[0] (GPU and CPU side by side).
 
-CPU baseline (rank 0, N = 1): the CPU twin libpraos_cpu.so (C++ restatement of the
+A plain run sets up, warms up, times --steps passes and prints the result line
+(metric, value, unit, ms_per_step, ...); --dump-outputs DIR also writes what the last
+timed pass computed.  Everything below is measured only with --full: the serial
+per-kernel pass and the roofline, the key-cache and dedup figures, the rate with the
+dedup off, the strong-scaling proxy, the end-to-end paths, the self-check and the CPU
+baseline.
+
+CPU baseline (--full, rank 0, N = 1): the CPU twin libpraos_cpu.so (C++ restatement of the
 reference semantics with the same C ABI; the Haskell reference cannot run here)
 timed over a bounded sample of the same headers on the host cores this job may use,
 plus its single-core rate and an OpenSSL Ed25519 verify rate as an independent
@@ -399,6 +406,45 @@ def make_input(ctx, args, cfg, rank, world=1):
                          rank=rank, world=world, scaling=args.scaling)
 
 
+def headline(args, cfg, n, world, dt, npools):
+    """The result line of a plain run (a --full run adds its sections to it): `dt` seconds for
+    args.steps timed steps over `n` items on each of `world` GPUs."""
+    total = n * world if args.scaling == "weak" else (args.items or cfg["items"])
+    return {
+        "metric": cfg["metric"],
+        "value": round(total * args.steps / dt, 1), "unit": "headers/s" if cfg["kernels"] == 7 else "items/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt * 1e3 / args.steps, 3), "higher_is_better": True, "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "u32 (GF(2^255-19) radix-2^32 limbs; Fixed E34 bignum)",
+        "data": "synthetic: GPU-signed chain" + (" from the shipped first-leader-wins schedule"
+                                                  if args.config in ("c1", "c5") else ""),
+        "config": {"workload": cfg["workload"], "items_per_gpu": n, "items_total": total, "pools": npools or None,
+                   "active_slot_coeff": "1/20",
+                   "signed_body": "canonical HeaderBody CBOR" if args.config in ("c1", "c5") else "397 random bytes",
+                   "parallelism": f"shard-by-slot-range x{world}"},
+    }
+
+
+DUMP_BYTES = 60_000_000          # budget of one --dump-outputs directory (float32 values)
+
+
+def dump_outputs(path, out):
+    """Writes the output arrays of one validation pass (bits, pool_idx, beta / leader or the two
+    TPraos betas, nonce) as <path>/<name>.npy in float32 (every value is an integer below 2^24,
+    so exact).  The per-header scalars are written whole; of the per-header byte rows a fixed,
+    seeded sample of headers (sorted indices, the same for every run of one size) is kept so
+    that the directory stays below DUMP_BYTES."""
+    os.makedirs(path, exist_ok=True)
+    n = len(out["bits"])
+    wide = [k for k, v in out.items() if v.ndim == 2]
+    row_bytes = 4 * sum(out[k].shape[1] for k in wide)
+    m = int(max(1, min(n, (DUMP_BYTES - 4 * n * (len(out) - len(wide))) // row_bytes)))
+    rows = np.sort(np.random.default_rng(0).choice(n, m, replace=False)) if m < n else np.arange(n)
+    for k, v in out.items():
+        np.save(os.path.join(path, f"{k}.npy"), (v[rows] if v.ndim == 2 else v).astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -422,6 +468,13 @@ def main():
                     help="chunks of the stored-bytes e2e pipeline (PRAOS_OPT_PIPELINE; 0 = auto)")
     ap.add_argument("--dedup", type=int, default=1,
                     help="verify each distinct OCert tuple once per batch (PRAOS_OPT_DEDUP; 0 = off)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: serial per-kernel pass and "
+                         "roofline, dedup-off rate, strong-scaling proxy, end-to-end paths, self-check, CPU "
+                         "baseline (--no-cpu / --no-e2e / --no-proxy drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (what praos_batch_download returns) as "
+                         "DIR/<name>.npy in float32")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
     if args.scaling == "strong" and args.config not in ("c1", "c5"):
@@ -486,6 +539,17 @@ def main():
         t = torch.tensor([dt], device="cpu" if rehearsal else "cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx.download_tpraos(b, n) if args.config == "tp" else ctx.download(b, n))
+    if not args.full:
+        # the plain run ends here: the headline figures alone
+        ctx.free(b)
+        if rank == 0:
+            print(json.dumps(headline(args, cfg, n, world, dt, len(pool_list))), flush=True)
+        ctx.close()
+        if dist:
+            dist.destroy_process_group()
+        return
     log(f"[rank {rank}] serial pass")
     # per-kernel durations for the roofline: serial launches (HIP events on the
     # launch stream), untimed, after the timed region
@@ -673,9 +737,8 @@ def main():
     if rank != 0:
         return
     steps = args.steps
-    ms_step = dt * 1e3 / steps
-    total = n * world if args.scaling == "weak" else (args.items or cfg["items"])
-    value = total * steps / dt
+    line = headline(args, cfg, n, world, dt, len(pool_list))
+    value = line["config"]["items_total"] * steps / dt
     kms /= steps
     per_kernel = {"ocert": kser[0], "kes": kser[1], "vrf": kser[2], "leader": kser[3]}   # stream spans
     ran = [k for k in ("ocert", "kes", "vrf") if cfg["kernels"] & MASK[k]]
@@ -738,18 +801,7 @@ def main():
     ev_achieved = dom_achieved
     if rp_ms:
         dom_achieved = dom_work / (rp_ms * 1e-3)
-    line = {
-        "metric": cfg["metric"],
-        "value": round(value, 1), "unit": "headers/s" if cfg["kernels"] == 7 else "items/s",
-        "n_gpus": world, "steps": steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-        "dtype": "u32 (GF(2^255-19) radix-2^32 limbs; Fixed E34 bignum)",
-        "data": "synthetic: GPU-signed chain" + (" from the shipped first-leader-wins schedule"
-                                                  if args.config in ("c1", "c5") else ""),
-        "config": {"workload": cfg["workload"], "items_per_gpu": n, "items_total": total, "pools": len(pool_list) or None,
-                   "active_slot_coeff": "1/20",
-                   "signed_body": "canonical HeaderBody CBOR" if args.config in ("c1", "c5") else "397 random bytes",
-                   "parallelism": f"shard-by-slot-range x{world}"},
+    line.update({
         "roofline": {"bound": "valu-int32", "kernel": dom_kernel,
                      "achieved": round(dom_achieved / 1e12, 3), "peak": round(PEAK_INT32 / 1e12, 2),
                      "unit": "T int32-ops/s", "frac": round(dom_achieved / PEAK_INT32, 4),
@@ -782,7 +834,7 @@ def main():
                        "corrupted_rejected": corrupt_caught, "corrupted_in_checked_fields": int(rel.sum()),
                        "corrupted_in_checked_fields_rejected": corrupt_caught_rel,
                        "leader_pass": int(((out["bits"] & 0x1000) == 0).sum()) if cfg["kernels"] & 4 else None},
-    }
+    })
     if e2e:
         line["e2e"] = e2e
     if proxy:

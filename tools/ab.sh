@@ -13,7 +13,7 @@ for r in 0 1; do
   for setting in "$@"; do
     envs=()
     [ "$setting" != "-" ] && read -r -a envs <<< "$setting"
-    timeout -k 10 300 env "${envs[@]}" python3 bench.py --items "$ITEMS" --steps ${STEPS:-20} --warmup 3 --no-cpu $([ -n "${E2E:-}" ] || echo --no-e2e) \
+    timeout -k 10 300 env "${envs[@]}" python3 bench.py --items "$ITEMS" --steps ${STEPS:-20} --warmup 3 --full --no-cpu $([ -n "${E2E:-}" ] || echo --no-e2e) \
       --no-proxy ${EXTRA_ARGS:-} > "$OUT/${i}_${r}.json" 2> "$OUT/${i}_${r}.err"
     rc=$?
     if [ $rc -ne 0 ]; then echo "[$setting] rc=$rc"; tail -5 "$OUT/${i}_${r}.err"; exit $rc; fi
