@@ -362,6 +362,83 @@ praos_batch* praos_block_batch_upload(praos_ctx* ctx, const praos_header_bytes* 
 int praos_block_batch_run(praos_ctx* ctx, praos_batch* b, uint64_t slots_per_kes_period);
 int praos_block_batch_download(praos_ctx* ctx, praos_batch* b, uint8_t* result, uint8_t* body_hash);
 
+/* ---- ImmutableDB chunk validation (added without a version bump; purely additive) ----
+ * CRC-32 (zlib, System.FS.CRC) of each span; crc[i] for span i; len 0 -> 0.
+ * A span outside the arena: PRAOS_E_ARG before anything is launched.
+ * Replaces computeCRC (System.FS.CRC) over the stored blocks, the checksum column of
+ * Secondary.Entry.  Kernel tile size: PRAOS_CRC_TILE bytes, counted from a span's start. */
+#define PRAOS_CRC_TILE 16384
+int praos_crc32(praos_ctx* ctx, const praos_header_bytes* spans, uint32_t* crc);
+/* Device-resident form: CRC-32 of the block spans of a praos_block_batch_upload batch (bench /
+ * streaming validation); a span outside the arena: PRAOS_E_ARG, nothing launched. */
+int praos_block_batch_crc32(praos_ctx* ctx, praos_batch* b, uint32_t* crc);
+
+/* praos_validate_chunk replaces parseChunkFile (Storage/ImmutableDB/Impl/Parser.hs:92-197,
+ * block boundaries as Util/CBOR.hs:217-290 finds them) for Shelley-based chunks: the chunk
+ * file goes in once; out come the valid prefix as rebuilt Secondary entries, the first
+ * error and the truncation offset.  Block i starts where block i-1 ended (block 0 at 0) and
+ * is the one CBOR item that starts there.  Per block, in file order, the first offending
+ * block ending the parse (the blocks before it are yielded):
+ *   UNSUPPORTED    the item is well-formed CBOR and is [0, ...] or [1, ...] (Byron): the
+ *                  caller falls back to the reference parser;
+ *   ERR_READ       the item does not decode: not a well-formed item, not a block envelope
+ *                  (praos_verify_block_integrity's rules) or the header does not decode.
+ *                  This is as far as this library decodes blocks; the reference's
+ *                  transaction decoders are stricter (a block whose segments are well-formed
+ *                  CBOR but not valid transactions is a ReadFailure there, accepted here);
+ *   checkEntries   i < n_expected and crc(block) == expected_crc[i]: trusted; otherwise
+ *                  verifyBlockIntegrity runs, non-zero bits -> ERR_CORRUPT
+ *                  (ChunkErrCorrupt, with blockPoint);
+ *   checkIfHashesLineUp  i > 0 and prevHash /= BlockHash (headerHash of block i-1), a
+ *                  GenesisHash prev at i > 0 included -> ERR_HASH_MISMATCH.
+ * truncate_at is the offending block's start, bytes_len when there is none.
+ * block_off is a HINT only (the index's blockOffsets): the device checks that every
+ * candidate [block_off[i], block_off[i+1]) is exactly one item (the last one running to the
+ * end of the file); from the first candidate that is not -- or from 0 without hints, with
+ * off[0] != 0, or from the first non-ascending / out-of-range offset -- the host walks the
+ * items itself (rescanned_from, bytes_len when no walk was needed).  Hints never change the
+ * outcome; expected_crc is positional by true block index. */
+#define PRAOS_CHUNK_OK                0
+#define PRAOS_CHUNK_ERR_READ          1 /* ChunkErrRead */
+#define PRAOS_CHUNK_ERR_CORRUPT       2 /* ChunkErrCorrupt */
+#define PRAOS_CHUNK_ERR_HASH_MISMATCH 3 /* ChunkErrHashMismatch */
+#define PRAOS_CHUNK_UNSUPPORTED       4 /* a Byron block: not handled here */
+#define PRAOS_CHUNK_ENTRY_SIZE        56
+typedef struct {
+  const uint8_t* bytes;           /* NNNNN.chunk as read */
+  size_t bytes_len;
+  const uint32_t* expected_crc;   /* parseChunkFile's [CRC]: checksums of the secondary index, in order */
+  size_t n_expected;              /* 0 = index missing or invalid */
+  const uint64_t* block_off;      /* NULL, or n_expected blockOffsets of the same entries */
+} praos_chunk;
+typedef struct {
+  uint32_t outcome;               /* PRAOS_CHUNK_* */
+  uint32_t integrity_bits;        /* ERR_CORRUPT: PRAOS_BLK_* of the offending block */
+  uint64_t blocks;                /* blocks yielded (with PRAOS_E_ARG for a small out->cap: needed) */
+  uint64_t checked;               /* blocks that took verifyBlockIntegrity */
+  uint64_t truncate_at;
+  uint64_t rescanned_from;
+  uint64_t err_slot;              /* ERR_CORRUPT / ERR_HASH_MISMATCH: the offending block's point */
+  uint8_t err_hash[32];
+  uint8_t expected_prev[32];      /* ERR_HASH_MISMATCH: headerHash of the block before */
+  uint8_t actual_prev[32];        /* ERR_HASH_MISMATCH: the block's prevHash (zeros: GenesisHash) */
+  uint8_t actual_prev_is_genesis;
+  uint8_t pad_[7];
+} praos_chunk_result;
+typedef struct {
+  size_t cap;                     /* capacity of the buffers below, in blocks */
+  uint8_t* entries;               /* cap*56: Secondary.Entry as on disk (Secondary.hs:93-128): blockOffset u64,
+                                     headerOffset u16, headerSize u16, checksum u32 (computed), headerHash,
+                                     blockOrEBB = slot u64, big-endian */
+  uint64_t* block_no;             /* for the Tip */
+  uint8_t* prev_hash;             /* cap*32 (zeros when GenesisHash) */
+  uint8_t* prev_is_genesis;       /* cap; block 0's fit against the previous chunk stays the caller's
+                                     (Validation.hs:389-399) */
+  int8_t* integrity;              /* cap: -1 trusted by its CRC, 0 checked and passed */
+} praos_chunk_out;
+int praos_validate_chunk(praos_ctx* ctx, const praos_chunk* chunk, uint64_t slots_per_kes_period,
+                         praos_chunk_result* res, praos_chunk_out* out);
+
 /* ---- TPraos (Shelley..Alonzo), the d = 0 path of cardano-protocol-tpraos ----
  * Replaces SL.updateChainDepState's crypto (TPraos.hs:378-387): OVERLAY
  * praosVrfChecks (pool, VRF key, eta cert with mkSeed seedEta, leader cert with

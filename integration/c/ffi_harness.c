@@ -6,6 +6,13 @@
  *
  *   ffi_harness <immutable dir> <epoch file> <threads>
  *   ffi_harness --chunk <immutable dir> <chunk no> <slots per KES period> <members>
+ *   ffi_harness --validate-chunk <immutable dir> <chunk no> <slots per KES period>
+ *
+ * --validate-chunk: parseChunkFile as one call, as Batch.hs validateChunkBatch runs it: the chunk
+ *   file as read, the secondary index's checksums and block offsets when the index is there and
+ *   well-formed (none otherwise), praos_validate_chunk, and the comparison validateChunk makes
+ *   (Validation.hs:412-420): are the rebuilt entries the index file's bytes.  Prints the result
+ *   fields, the rebuilt entries (hex) and per-block block_no / integrity as JSON.
  *
  * --chunk: ImmutableDB chunk validation as Batch.hs verifyChunkIntegrity runs it (the batched
  *   checkIntegrity of parseChunkFile, ImmutableDB/Impl/Parser.hs:118-141, Validation.hs:379-384):
@@ -934,12 +941,77 @@ static int chunk_main(const char* dir, int chunk, uint64_t spkp, int members) {
   return 0;
 }
 
+/* ---- parseChunkFile as one call (Batch.hs validateChunkBatch) ---- */
+static int validate_chunk_main(const char* dir, int chunk, uint64_t spkp) {
+  static const char* OUTCOME[] = {"OK", "ERR_READ", "ERR_CORRUPT", "ERR_HASH_MISMATCH", "UNSUPPORTED"};
+  char p[4096];
+  size_t dl = 0, sl = 0;
+  snprintf(p, sizeof p, "%s/%05d.chunk", dir, chunk);
+  uint8_t* data = slurp(p, &dl);
+  if (!data) DIE("chunk %d: missing chunk file", chunk);
+  snprintf(p, sizeof p, "%s/%05d.secondary", dir, chunk);
+  uint8_t* sec = slurp(p, &sl);
+  size_t n = (sec && sl % PRAOS_CHUNK_ENTRY_SIZE == 0) ? sl / PRAOS_CHUNK_ENTRY_SIZE : 0;   /* invalid index: none */
+  uint32_t* crc = calloc(n + 1, 4);
+  uint64_t* boff = calloc(n + 1, 8);
+  for (size_t i = 0; i < n; i++) {
+    boff[i] = be(sec + PRAOS_CHUNK_ENTRY_SIZE * i, 8);
+    crc[i] = (uint32_t)be(sec + PRAOS_CHUNK_ENTRY_SIZE * i + 12, 4);
+  }
+  praos_ctx* ctx = praos_open(0);
+  if (!ctx) DIE("praos_open(0)");
+  praos_chunk ch = {data, dl, n ? crc : NULL, n, n ? boff : NULL};
+  praos_chunk_result res;
+  praos_chunk_out out;
+  size_t cap = n ? n : 64;
+  for (;;) {   /* the index says how many blocks to expect; a longer file asks again */
+    out.cap = cap;
+    out.entries = calloc(cap, PRAOS_CHUNK_ENTRY_SIZE);
+    out.block_no = calloc(cap, 8);
+    out.prev_hash = calloc(cap, 32);
+    out.prev_is_genesis = calloc(cap, 1);
+    out.integrity = calloc(cap, 1);
+    const int rc = praos_validate_chunk(ctx, &ch, spkp, &res, &out);
+    if (rc == PRAOS_OK) break;
+    if (rc != PRAOS_E_ARG || res.blocks <= cap) DIE("praos_validate_chunk -> %d: %s", rc, praos_last_error(ctx));
+    free(out.entries); free(out.block_no); free(out.prev_hash); free(out.prev_is_genesis); free(out.integrity);
+    cap = res.blocks;
+  }
+  const size_t y = res.blocks;
+  const int same = sec && sl == y * PRAOS_CHUNK_ENTRY_SIZE && memcmp(sec, out.entries, sl) == 0;
+  printf("{\"phase\": \"validate_chunk\", \"outcome\": \"%s\", \"integrity_bits\": %u, \"blocks\": %zu, "
+         "\"checked\": %llu, \"truncate_at\": %llu, \"rescanned_from\": %llu, \"err_slot\": %llu, "
+         "\"actual_prev_is_genesis\": %u, \"entries_match\": %s, \"err_hash\": \"",
+         OUTCOME[res.outcome], res.integrity_bits, y, (unsigned long long)res.checked,
+         (unsigned long long)res.truncate_at, (unsigned long long)res.rescanned_from,
+         (unsigned long long)res.err_slot, res.actual_prev_is_genesis, same ? "true" : "false");
+  hex_out(res.err_hash, 32);
+  printf("\", \"expected_prev\": \"");
+  hex_out(res.expected_prev, 32);
+  printf("\", \"actual_prev\": \"");
+  hex_out(res.actual_prev, 32);
+  printf("\", \"entries\": \"");
+  hex_out(out.entries, y * PRAOS_CHUNK_ENTRY_SIZE);
+  printf("\", \"block_no\": [");
+  for (size_t i = 0; i < y; i++) printf("%s%llu", i ? ", " : "", (unsigned long long)out.block_no[i]);
+  printf("], \"integrity\": [");
+  for (size_t i = 0; i < y; i++) printf("%s%d", i ? ", " : "", (int)out.integrity[i]);
+  printf("]}\n");
+  fflush(stdout);
+  praos_close(ctx);
+  free(out.entries); free(out.block_no); free(out.prev_hash); free(out.prev_is_genesis); free(out.integrity);
+  free(crc); free(boff); free(data); free(sec);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (praos_abi_version() != PRAOS_ABI_VERSION) DIE("ABI version %d, header %d", praos_abi_version(), PRAOS_ABI_VERSION);
   if (argc == 6 && strcmp(argv[1], "--chunk") == 0)
     return chunk_main(argv[2], atoi(argv[3]), strtoull(argv[4], NULL, 10), atoi(argv[5]));
-  if (argc != 4) DIE("usage: %s <immutable dir> <epoch file> <threads> | --chunk <dir> <chunk> <spkp> <members>",
-                     argv[0]);
+  if (argc == 5 && strcmp(argv[1], "--validate-chunk") == 0)
+    return validate_chunk_main(argv[2], atoi(argv[3]), strtoull(argv[4], NULL, 10));
+  if (argc != 4) DIE("usage: %s <immutable dir> <epoch file> <threads> | --chunk <dir> <chunk> <spkp> <members>"
+                     " | --validate-chunk <dir> <chunk> <spkp>", argv[0]);
   read_epoch_file(argv[2]);
   chain_t ch;
   read_chain(argv[1], &ch);

@@ -58,6 +58,9 @@ module Ouroboros.Consensus.Protocol.Praos.Batch
     -- * ImmutableDB chunk validation (verifyBlockIntegrity batched)
   , ChunkValidation (..)
   , verifyChunkIntegrity
+  , ChunkOutcome (..)
+  , ChunkParse (..)
+  , validateChunkBatch
   , praosVerifyBlockIntegrity
     -- * Error reconstruction (typed constructors: module Batch.Errors)
   , verdictToError
@@ -173,6 +176,15 @@ foreign import ccall safe "praos_group_verify_block_integrity" c_group_verify_bl
 foreign import ccall safe "praos_verify_header_bytes_submit" c_verify_header_bytes_submit
   :: Ptr PraosCtx -> Ptr () -> Ptr () -> Ptr () -> IO CInt
 foreign import ccall safe "praos_verify_drain" c_verify_drain :: Ptr PraosCtx -> IO CInt
+
+-- added without a version bump (purely additive): parseChunkFile as one call.  The structs it
+-- pokes and peeks (checked against the C compiler by tests/test_chunk_abi.py; "layout", not
+-- "struct": the lines above are the ones tests/test_abi.py owns):
+-- layout praos_chunk (40 bytes): bytes@0 bytes_len@8 expected_crc@16 n_expected@24 block_off@32
+-- layout praos_chunk_result (152 bytes): outcome@0 integrity_bits@4 blocks@8 checked@16 truncate_at@24 rescanned_from@32 err_slot@40 err_hash@48 expected_prev@80 actual_prev@112 actual_prev_is_genesis@144
+-- layout praos_chunk_out (48 bytes): cap@0 entries@8 block_no@16 prev_hash@24 prev_is_genesis@32 integrity@40
+foreign import ccall safe "praos_validate_chunk" c_validate_chunk
+  :: Ptr PraosCtx -> Ptr () -> Word64 -> Ptr () -> Ptr () -> IO CInt
 
 abiVersion :: CInt
 abiVersion = 15
@@ -953,6 +965,107 @@ verifyChunkIntegrity ctx spkp crc32 chunk entries = do
     { cvResults = results
     , cvFirstCorrupt = firstBad
     , cvTruncateAt = maybe (fromIntegral (BS.length chunk)) (\i -> fst (entries !! i)) firstBad }
+
+-- | What parseChunkFile ended with (ChunkFileError, Parser.hs:60-90), or that the chunk holds
+-- a block this library does not parse (Byron): the caller then runs the reference parser.
+data ChunkOutcome
+  = ChunkOK
+  | ChunkErrRead                                  -- ^ ChunkErrRead (a ReadIncrementalErr)
+  | ChunkErrCorrupt !Word32 !Word64 !BS.ByteString -- ^ PRAOS_BLK_* bits, blockPoint (slot, hash)
+  | ChunkErrHashMismatch !BS.ByteString !(Maybe BS.ByteString)
+    -- ^ headerHash of the block before, the block's prevHash (Nothing = GenesisHash)
+  | ChunkUnsupported
+  deriving (Eq, Show)
+
+-- | parseChunkFile's yield: the rebuilt Secondary entries of the valid prefix in their on-disk
+-- form (56 bytes each, Secondary.hs:93-128), block numbers and prev hashes (for the Tip and the
+-- first block's fit against the previous chunk), the error that ended the parse and the offset
+-- to truncate the chunk file at.
+data ChunkParse = ChunkParse
+  { cpOutcome       :: !ChunkOutcome
+  , cpEntries       :: !BS.ByteString
+  , cpBlockNos      :: !(VS.Vector Word64)
+  , cpFirstPrev     :: !(Maybe (Maybe BS.ByteString))  -- ^ prevHash of block 0 (Just Nothing = GenesisHash)
+  , cpChecked       :: !Word64
+  , cpTruncateAt    :: !Word64
+  , cpRescannedFrom :: !Word64
+  }
+
+-- | parseChunkFile (ImmutableDB/Impl/Parser.hs:92-197) as one device call: the chunk file as
+-- read, the secondary index's checksums (parseChunkFile's [CRC], empty when the index is missing
+-- or invalid) and its block offsets as a hint.  CRC-32 of every block, the block boundaries, the
+-- header hashes, the prev-hash line-up and verifyBlockIntegrity of the blocks whose checksum does
+-- not match all run on the GPU; validateChunk (Validation.hs:374-420) compares 'cpEntries' with
+-- the index file's bytes and rewrites it when they differ (immutabledb-validation.patch).
+-- Replayed from C by ffi_harness --validate-chunk.
+validateChunkBatch :: PraosBatchCtx -> Word64 -> BS.ByteString -> [(Word64, Word32)] -> IO ChunkParse
+validateChunkBatch (PraosBatchGroup _ _ _) _ _ _ =
+  throwIO (PraosBatchError (-2) "validateChunkBatch: one context, not a group")
+validateChunkBatch ctx@(PraosBatchCtx p) spkp chunk entries = go (max 64 (length entries))
+  where
+    nExp = length entries
+    crcs = VS.fromList (map snd entries)
+    offs = VS.fromList (map fst entries)
+    go cap = do
+      ents <- VSM.new (56 * cap) :: IO (VSM.IOVector Word8)
+      bnos <- VSM.new cap :: IO (VSM.IOVector Word64)
+      prevs <- VSM.new (32 * cap) :: IO (VSM.IOVector Word8)
+      gens <- VSM.new cap :: IO (VSM.IOVector Word8)
+      integ <- VSM.new cap :: IO (VSM.IOVector Word8)
+      r <- BSU.unsafeUseAsCStringLen chunk $ \(cp, clen) ->
+        VS.unsafeWith crcs $ \crcp -> VS.unsafeWith offs $ \offp ->
+        VSM.unsafeWith ents $ \ep -> VSM.unsafeWith bnos $ \bp -> VSM.unsafeWith prevs $ \pp ->
+        VSM.unsafeWith gens $ \gp -> VSM.unsafeWith integ $ \ip ->
+        allocaBytes 40 $ \ch -> allocaBytes 152 $ \res -> allocaBytes 48 $ \out -> do
+          pokeByteOff ch 0 cp >> pokeByteOff ch 8 (fromIntegral clen :: CSize)
+          pokeByteOff ch 16 (if nExp == 0 then nullPtr else crcp)
+          pokeByteOff ch 24 (fromIntegral nExp :: CSize)
+          pokeByteOff ch 32 (if nExp == 0 then nullPtr else offp)
+          pokeByteOff out 0 (fromIntegral cap :: CSize)
+          pokeByteOff out 8 ep >> pokeByteOff out 16 bp >> pokeByteOff out 24 pp
+          pokeByteOff out 32 gp >> pokeByteOff out 40 ip
+          rc <- c_validate_chunk p (castPtr ch) spkp (castPtr res) (castPtr out)
+          blocks <- peekByteOff res 8 :: IO Word64
+          if rc == (-2) && blocks > fromIntegral cap
+            then pure (Left (fromIntegral blocks))      -- out->cap too small: ask again
+            else do
+              check ctx (pure rc)
+              outcome <- peekByteOff res 0 :: IO Word32
+              bits <- peekByteOff res 4 :: IO Word32
+              checked <- peekByteOff res 16
+              trunc <- peekByteOff res 24
+              rescan <- peekByteOff res 32
+              slot <- peekByteOff res 40 :: IO Word64
+              errHash <- BS.packCStringLen (castPtr res `plusPtr` 48, 32)
+              expPrev <- BS.packCStringLen (castPtr res `plusPtr` 80, 32)
+              actPrev <- BS.packCStringLen (castPtr res `plusPtr` 112, 32)
+              actGen <- peekByteOff res 144 :: IO Word8
+              pure (Right (outcome, bits, fromIntegral blocks :: Int, checked, trunc, rescan, slot, errHash,
+                           expPrev, actPrev, actGen))
+      case r of
+        Left need -> go need
+        Right (outcome, bits, y, checked, trunc, rescan, slot, errHash, expPrev, actPrev, actGen) -> do
+          ev <- VS.unsafeFreeze ents
+          bv <- VS.unsafeFreeze bnos
+          pv <- VS.unsafeFreeze prevs
+          gv <- VS.unsafeFreeze gens
+          let firstPrev | y == 0 = Nothing
+                        | gv VS.! 0 /= 0 = Just Nothing
+                        | otherwise = Just (Just (BS.pack (VS.toList (VS.take 32 pv))))
+              oc = case outcome of
+                0 -> ChunkOK
+                1 -> ChunkErrRead
+                2 -> ChunkErrCorrupt bits slot errHash
+                3 -> ChunkErrHashMismatch expPrev (if actGen /= 0 then Nothing else Just actPrev)
+                _ -> ChunkUnsupported
+          pure ChunkParse
+            { cpOutcome = oc
+            , cpEntries = BS.pack (VS.toList (VS.take (56 * y) ev))
+            , cpBlockNos = VS.take y bv
+            , cpFirstPrev = firstPrev
+            , cpChecked = checked
+            , cpTruncateAt = trunc
+            , cpRescannedFrom = rescan }
 
 -- ---------------------------------------------------------------- errors
 

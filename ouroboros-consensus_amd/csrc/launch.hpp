@@ -195,6 +195,9 @@ void launch_decode_praos(dim3 grid, dim3 block, hipStream_t stream, size_t n, co
 void launch_block_split(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint8_t* arena,
                         uint64_t arena_len, uint64_t* off_io, uint32_t* len_io, uint64_t* seg_off, uint32_t* seg_len,
                         uint8_t* nseg, uint8_t* status);
+// k_crc32.hip: CRC-32 of n spans; tile_first = exclusive prefix sum of ceil(len / PRAOS_CRC_TILE), n + 1 entries
+void launch_crc32(hipStream_t stream, uint32_t n, uint32_t ntiles, const uint8_t* arena, const uint64_t* off,
+                  const uint32_t* len, const uint32_t* tile_first, uint32_t* tile_raw, uint32_t* crc);
 void launch_seg_hash(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint8_t* arena,
                      const uint64_t* seg_off, const uint32_t* seg_len, const uint8_t* nseg, uint8_t* seg_hash);
 void launch_block_join(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint8_t* nseg,

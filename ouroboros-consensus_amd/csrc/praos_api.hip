@@ -5,6 +5,7 @@
 #include "launch.hpp"
 #include "host_util.hpp"
 #include "replay_internal.hpp"
+#include "chunk_scan.hpp"
 
 static constexpr size_t NT = 256;                  // threads per block of the crypto kernels
 static constexpr size_t NIELS_BYTES = 3 * 32;      // sizeof(ge_niels)
@@ -573,6 +574,9 @@ struct praos_batch {
   uint64_t *blk_off = nullptr, *seg_off = nullptr;
   uint32_t *blk_len = nullptr, *seg_len = nullptr;
   uint8_t *nseg = nullptr, *split_status = nullptr, *seg_hash = nullptr, *blk_result = nullptr, *blk_hash = nullptr;
+  // CRC-32 of the block spans (k_crc32.hip): tile list, per-tile registers, results; kept for re-runs
+  uint32_t *crc_first = nullptr, *crc_raw = nullptr, *crc_out = nullptr;
+  uint32_t crc_tiles = 0;
   std::vector<void*> owned;
   std::vector<size_t> owned_sz;
   praos_ctx* owner = nullptr;
@@ -1830,9 +1834,8 @@ static int batch_run_impl(praos_ctx* c, praos_batch* b) {
 }
 
 // ---- block-integrity batch (k_block.hip + k_decode + k_kes header mode)
-praos_batch* praos_block_batch_upload(praos_ctx* c, const praos_header_bytes* blocks) {
-  praos_batch* b = praos_batch_upload_bytes(c, blocks);
-  if (!b) return nullptr;
+// the buffers a block batch has beyond a from-bytes batch
+static bool block_batch_buffers(praos_batch* b) {
   const size_t n = b->n;
   b->is_block = true;
   bool ok = dalloc(b, &b->blk_off, 8 * n) == hipSuccess;
@@ -1848,6 +1851,14 @@ praos_batch* praos_block_batch_upload(praos_ctx* c, const praos_header_bytes* bl
   b->signed_stride = TP_SIGNED_STRIDE;
   b->body_bytes_len = (size_t)TP_SIGNED_STRIDE * n;
   ok &= dalloc(b, &b->body, b->body_bytes_len + 16) == hipSuccess;
+  return ok;
+}
+
+praos_batch* praos_block_batch_upload(praos_ctx* c, const praos_header_bytes* blocks) {
+  praos_batch* b = praos_batch_upload_bytes(c, blocks);
+  if (!b) return nullptr;
+  const size_t n = b->n;
+  bool ok = block_batch_buffers(b);
   if (!ok) { c->err = "device allocation failed"; praos_batch_free(c, b); return nullptr; }
   // the uploaded spans are whole blocks; k_block_split rewrites hoff/hlen to the header spans
   if (n) {
@@ -1913,6 +1924,334 @@ int praos_verify_block_integrity(praos_ctx* c, const praos_header_bytes* blocks,
   int r = praos_block_batch_run(c, b, slots_per_kes_period);
   if (r == PRAOS_OK) r = praos_block_batch_download(c, b, result, body_hash);
   praos_batch_free(c, b);
+  return r;
+}
+
+// ---- ImmutableDB chunk validation: CRC-32 (k_crc32.hip) and parseChunkFile as one call
+// CRC-32 of n spans of d_arena on stream st; the buffers belong to batch b.  len_h: the
+// spans' lengths on the host (the tile list is their prefix sum).
+static int crc_spans(praos_ctx* c, praos_batch* b, hipStream_t st, size_t n, const uint32_t* len_h,
+                     const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, uint32_t** d_crc) {
+  if (!b->crc_out) {   // a batch's spans do not change: the tile list is built once
+    std::vector<uint32_t> first(n + 1);
+    uint64_t tiles = 0;
+    for (size_t i = 0; i < n; i++) {
+      first[i] = (uint32_t)tiles;
+      tiles += ((uint64_t)len_h[i] + PRAOS_CRC_TILE - 1) / PRAOS_CRC_TILE;
+      if (tiles > 0x7fffffffu) { c->err = "too many CRC tiles"; return PRAOS_E_ARG; }
+    }
+    first[n] = (uint32_t)tiles;
+    bool ok = dalloc(b, &b->crc_first, 4 * (n + 1)) == hipSuccess;
+    ok &= dalloc(b, &b->crc_raw, 4 * (size_t)tiles) == hipSuccess;
+    uint32_t* out = nullptr;
+    ok &= dalloc(b, &out, 4 * n) == hipSuccess;
+    if (!ok) { c->err = "device allocation failed"; return PRAOS_E_OOM; }
+    HIPCHK(c, hipMemcpy(b->crc_first, first.data(), 4 * (n + 1), hipMemcpyHostToDevice));
+    b->crc_tiles = (uint32_t)tiles;
+    b->crc_out = out;
+  }
+  (void)hipGetLastError();
+  launch_crc32(st, (uint32_t)n, b->crc_tiles, d_arena, d_off, d_len, b->crc_first, b->crc_raw, b->crc_out);
+  HIPCHK(c, hipGetLastError());
+  *d_crc = b->crc_out;
+  return PRAOS_OK;
+}
+
+// arena upload of a from-bytes batch (zero padding for ld64u, then the bytes), on the ctx stream
+static int arena_upload(praos_ctx* c, praos_batch* b, const uint8_t* bytes, size_t bytes_len) {
+  const size_t pad = ((bytes_len + 7) & ~(size_t)7) + 16 - bytes_len;
+  HIPCHK(c, hipMemsetAsync(b->arena + bytes_len, 0, pad, c->stream));
+  if (bytes_len) HIPCHK(c, h2d(c, b->arena, bytes, bytes_len));
+  return PRAOS_OK;
+}
+
+int praos_crc32(praos_ctx* c, const praos_header_bytes* s, uint32_t* crc) {
+  if (!c || !s || (s->n && (!s->off || !s->len || !crc)) || (!s->bytes && s->bytes_len) || s->n > 0x7fffffffu)
+    return PRAOS_E_ARG;
+  for (size_t i = 0; i < s->n; i++)
+    if (s->off[i] > s->bytes_len || s->len[i] > s->bytes_len - s->off[i]) {
+      c->err = "praos_crc32: span " + std::to_string(i) + " outside the arena";
+      return PRAOS_E_ARG;
+    }
+  if (c->device < 0) { c->err = "host-only context: no HIP device"; return PRAOS_E_STATE; }
+  if (s->n == 0) return PRAOS_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = s->n;
+  praos_batch* b = new praos_batch();
+  b->owner = c;
+  b->n = n;
+  b->arena_len = s->bytes_len;
+  auto run = [&]() -> int {
+    bool ok = dalloc(b, &b->arena, ((s->bytes_len + 7) & ~(size_t)7) + 16) == hipSuccess;
+    ok &= dalloc(b, &b->hoff, 8 * n) == hipSuccess;
+    ok &= dalloc(b, &b->hlen, 4 * n) == hipSuccess;
+    if (!ok) { c->err = "device allocation failed"; return PRAOS_E_OOM; }
+    int r = arena_upload(c, b, s->bytes, s->bytes_len);
+    if (r != PRAOS_OK) return r;
+    HIPCHK(c, hipMemcpyAsync(b->hoff, s->off, 8 * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b->hlen, s->len, 4 * n, hipMemcpyHostToDevice, c->stream));
+    uint32_t* d_crc = nullptr;
+    r = crc_spans(c, b, c->stream, n, s->len, b->arena, b->hoff, b->hlen, &d_crc);
+    if (r != PRAOS_OK) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(crc, d_crc, 4 * n, hipMemcpyDeviceToHost));
+    return PRAOS_OK;
+  };
+  const int r = run();
+  (void)hipStreamSynchronize(c->stream);
+  praos_batch_free(c, b);
+  return r;
+}
+
+int praos_block_batch_crc32(praos_ctx* c, praos_batch* b, uint32_t* crc) {
+  if (!c || !b || !b->is_block || (b->n && !crc) || b->n > 0x7fffffffu) return PRAOS_E_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = b->n;
+  if (n == 0) return PRAOS_OK;
+  std::vector<uint32_t> len;
+  if (!b->crc_out) {
+    len.resize(n);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(len.data(), b->blk_len, 4 * n, hipMemcpyDeviceToHost));
+    std::vector<uint64_t> off(n);
+    HIPCHK(c, hipMemcpy(off.data(), b->blk_off, 8 * n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++)   // the kernel does not range-check: nothing is launched on a bad span
+      if (off[i] > b->arena_len || len[i] > b->arena_len - off[i]) {
+        c->err = "praos_block_batch_crc32: span " + std::to_string(i) + " outside the arena";
+        return PRAOS_E_ARG;
+      }
+  }
+  uint32_t* d_crc = nullptr;
+  const int r = crc_spans(c, b, c->stream, n, len.data(), b->arena, b->blk_off, b->blk_len, &d_crc);
+  if (r != PRAOS_OK) return r;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(crc, d_crc, 4 * n, hipMemcpyDeviceToHost));
+  return PRAOS_OK;
+}
+
+namespace {
+// per-block columns of pass A, on the host
+struct ChunkCols {
+  std::vector<uint64_t> off, hoff, slot, block_no;
+  std::vector<uint32_t> len, hlen, crc;
+  std::vector<uint16_t> dec;
+  std::vector<uint8_t> split, gen, prev, hh;
+  void resize(size_t n) {
+    off.resize(n); hoff.resize(n); slot.resize(n); block_no.resize(n); len.resize(n); hlen.resize(n);
+    crc.resize(n); dec.resize(n); split.resize(n); gen.resize(n); prev.resize(32 * n); hh.resize(32 * n);
+  }
+};
+void put_be(uint8_t* p, uint64_t v, int nbytes) {
+  for (int k = 0; k < nbytes; k++) p[k] = (uint8_t)(v >> (8 * (nbytes - 1 - k)));
+}
+}  // namespace
+
+// a block batch of n blocks over the arena of `arena_of` (no upload), or over a fresh arena
+static praos_batch* chunk_batch(praos_ctx* c, size_t n, size_t bytes_len, const praos_batch* arena_of) {
+  praos_batch* b = bytes_batch_alloc(c, n, arena_of ? 0 : bytes_len, false, c);
+  if (!b) return nullptr;
+  if (!block_batch_buffers(b)) { c->err = "device allocation failed"; praos_batch_free(c, b); return nullptr; }
+  if (arena_of) { b->arena = arena_of->arena; b->arena_len = arena_of->arena_len; }
+  return b;
+}
+
+// pass A over blocks [base, base + b->n) of col (off / len filled in): CRC on a side stream
+// beside split + decode on the ctx stream, then the columns come back
+static int chunk_pass_a(praos_ctx* c, praos_batch* b, size_t base, ChunkCols& col) {
+  const size_t n = b->n;
+  if (n == 0) return PRAOS_OK;
+  const dim3 g(nblocks(n, NT)), blk(NT);
+  HIPCHK(c, hipMemcpyAsync(b->blk_off, col.off.data() + base, 8 * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b->blk_len, col.len.data() + base, 4 * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b->hoff, b->blk_off, 8 * n, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b->hlen, b->blk_len, 4 * n, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+  HIPCHK(c, hipStreamWaitEvent(c->side[0], c->ev[0], 0));
+  uint32_t* d_crc = nullptr;
+  int r = crc_spans(c, b, c->side[0], n, col.len.data() + base, b->arena, b->blk_off, b->blk_len, &d_crc);
+  if (r != PRAOS_OK) return r;
+  HIPCHK(c, hipEventRecord(c->side_ev[0], c->side[0]));
+  launch_block_split(g, blk, c->stream, n, b->arena, b->arena_len, b->hoff, b->hlen, b->seg_off, b->seg_len, b->nseg,
+                     b->split_status);
+  HIPCHK(c, hipGetLastError());
+  r = batch_decode(c, b);
+  if (r != PRAOS_OK) { c->err = "decode launch failed"; return r; }
+  HIPCHK(c, hipStreamWaitEvent(c->stream, c->side_ev[0], 0));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(col.crc.data() + base, d_crc, 4 * n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(col.split.data() + base, b->split_status, n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(col.dec.data() + base, b->dec_status, 2 * n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(col.hoff.data() + base, b->hoff, 8 * n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(col.hlen.data() + base, b->hlen, 4 * n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(col.slot.data() + base, b->slot, 8 * n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(col.block_no.data() + base, b->block_no, 8 * n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(col.gen.data() + base, b->prev_genesis, n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(col.prev.data() + 32 * base, b->prev_hash, 32 * n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(col.hh.data() + 32 * base, b->header_hash, 32 * n, hipMemcpyDeviceToHost));
+  return PRAOS_OK;
+}
+
+int praos_validate_chunk(praos_ctx* c, const praos_chunk* ch, uint64_t spkp, praos_chunk_result* res,
+                         praos_chunk_out* out) {
+  if (!c || !ch || !res || !out || spkp == 0 || (!ch->bytes && ch->bytes_len) ||
+      (ch->n_expected && !ch->expected_crc) || ch->bytes_len > 0xffffffffu)
+    return PRAOS_E_ARG;
+  if (c->device < 0) { c->err = "host-only context: no HIP device"; return PRAOS_E_STATE; }
+  const uint64_t L = ch->bytes_len;
+  const size_t m = ch->n_expected;
+  std::memset(res, 0, sizeof *res);
+  res->truncate_at = L;
+  res->rescanned_from = L;
+  if (L == 0) { res->rescanned_from = 0; return PRAOS_OK; }
+  HIPCHK(c, hipSetDevice(c->device));
+  // the leading offsets that can be candidates at all: off[0] == 0, ascending, inside the file
+  size_t k = 0;
+  if (ch->block_off)
+    while (k < m && ch->block_off[k] < L && (k == 0 ? ch->block_off[0] == 0 : ch->block_off[k] > ch->block_off[k - 1]))
+      k++;
+  const bool all = m > 0 && k == m;
+  const size_t ncand = all ? m : (k ? k - 1 : 0);
+  ChunkCols col;
+  col.resize(ncand);
+  for (size_t j = 0; j < ncand; j++) {
+    col.off[j] = ch->block_off[j];
+    col.len[j] = (uint32_t)((j + 1 < m ? ch->block_off[j + 1] : L) - ch->block_off[j]);
+  }
+  praos_batch *b1 = nullptr, *b2 = nullptr, *b3 = nullptr;
+  std::vector<uint8_t> verdict;
+  std::vector<size_t> sub;
+  size_t nblk = 0;           // blocks with columns
+  bool bad_tail = false;     // the item after them is not well-formed
+  auto run = [&]() -> int {
+    uint64_t rs = all ? L : (k ? ch->block_off[k - 1] : 0);
+    bool rescan = !all;
+    size_t keep = ncand;
+    if (ncand) {
+      b1 = chunk_batch(c, ncand, L, nullptr);
+      if (!b1) return PRAOS_E_OOM;
+      int r = arena_upload(c, b1, ch->bytes, L);
+      if (r == PRAOS_OK) r = chunk_pass_a(c, b1, 0, col);
+      if (r != PRAOS_OK) return r;
+      for (size_t j = 0; j < ncand; j++)
+        if (col.split[j]) { keep = j; rs = col.off[j]; rescan = true; break; }
+    }
+    nblk = keep;
+    if (rescan) {
+      // the host finds the true boundaries from rs on; the device passes run on them
+      res->rescanned_from = rs;
+      std::vector<uint64_t> o;
+      uint64_t pos = rs;
+      while (pos < L) {
+        const int64_t e = chunk_scan::chunk_item_end(ch->bytes, pos, L);
+        if (e < 0) { bad_tail = true; break; }
+        o.push_back(pos);
+        pos = (uint64_t)e;
+      }
+      const uint64_t stop = pos;
+      nblk = keep + o.size();
+      col.resize(nblk + (bad_tail ? 1 : 0));
+      for (size_t j = 0; j < o.size(); j++) {
+        col.off[keep + j] = o[j];
+        col.len[keep + j] = (uint32_t)((j + 1 < o.size() ? o[j + 1] : stop) - o[j]);
+      }
+      if (bad_tail) col.off[nblk] = stop;
+      if (!o.empty()) {
+        b2 = chunk_batch(c, o.size(), L, b1);
+        if (!b2) return PRAOS_E_OOM;
+        int r = b1 ? PRAOS_OK : arena_upload(c, b2, ch->bytes, L);
+        if (r == PRAOS_OK) r = chunk_pass_a(c, b2, keep, col);
+        if (r != PRAOS_OK) return r;
+      }
+    }
+    // the first block that does not decode ends the parse; so does the first prev-hash mismatch,
+    // where a corrupt block still comes first
+    size_t E = nblk;
+    for (size_t i = 0; i < nblk; i++)
+      if (col.split[i] || (col.dec[i] & PRAOS_DEC_FAILED)) { E = i; break; }
+    auto mismatch = [&](size_t i) {
+      return i > 0 && (col.gen[i] || std::memcmp(&col.prev[32 * i], &col.hh[32 * (i - 1)], 32) != 0);
+    };
+    auto trusted = [&](size_t i) { return i < m && col.crc[i] == ch->expected_crc[i]; };
+    size_t M = E;
+    for (size_t i = 0; i < E; i++)
+      if (mismatch(i)) { M = i; break; }
+    for (size_t i = 0; i < E && i <= M; i++)
+      if (!trusted(i)) sub.push_back(i);
+    // pass B: verifyBlockIntegrity of the untrusted blocks, over the same device arena
+    verdict.assign(sub.size(), 0);
+    if (!sub.empty()) {
+      praos_batch* arena_b = b1 ? b1 : b2;
+      b3 = chunk_batch(c, sub.size(), L, arena_b);
+      if (!b3) return PRAOS_E_OOM;
+      std::vector<uint64_t> so(sub.size());
+      std::vector<uint32_t> sl(sub.size());
+      for (size_t j = 0; j < sub.size(); j++) { so[j] = col.off[sub[j]]; sl[j] = col.len[sub[j]]; }
+      HIPCHK(c, hipMemcpy(b3->blk_off, so.data(), 8 * so.size(), hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(b3->blk_len, sl.data(), 4 * sl.size(), hipMemcpyHostToDevice));
+      int r = praos_block_batch_run(c, b3, spkp);
+      if (r == PRAOS_OK) r = praos_block_batch_download(c, b3, verdict.data(), nullptr);
+      if (r != PRAOS_OK) return r;
+    }
+    // fold in file order: read, then corrupt, then mismatch
+    size_t y = 0, q = 0;
+    for (size_t i = 0; i < nblk + (bad_tail ? 1 : 0); i++) {
+      if (i == E || i == nblk) {
+        const bool byron = i < nblk && chunk_scan::chunk_item_end(ch->bytes, col.off[i], L) == (int64_t)(col.off[i] + col.len[i]) &&
+                           chunk_scan::is_byron_item(ch->bytes, col.off[i], L);
+        res->outcome = byron ? PRAOS_CHUNK_UNSUPPORTED : PRAOS_CHUNK_ERR_READ;
+        res->truncate_at = col.off[i];
+        break;
+      }
+      if (!trusted(i)) {
+        res->checked++;
+        const uint8_t v = verdict[q++];
+        if (v) {
+          res->outcome = PRAOS_CHUNK_ERR_CORRUPT;
+          res->integrity_bits = v;
+          res->truncate_at = col.off[i];
+          res->err_slot = col.slot[i];
+          std::memcpy(res->err_hash, &col.hh[32 * i], 32);
+          break;
+        }
+      }
+      if (mismatch(i)) {
+        res->outcome = PRAOS_CHUNK_ERR_HASH_MISMATCH;
+        res->truncate_at = col.off[i];
+        res->err_slot = col.slot[i];
+        std::memcpy(res->err_hash, &col.hh[32 * i], 32);
+        std::memcpy(res->expected_prev, &col.hh[32 * (i - 1)], 32);
+        std::memcpy(res->actual_prev, &col.prev[32 * i], 32);
+        res->actual_prev_is_genesis = col.gen[i];
+        break;
+      }
+      y++;
+    }
+    res->blocks = y;
+    if (y > out->cap) { c->err = "praos_validate_chunk: out->cap too small"; return PRAOS_E_ARG; }
+    if (y && (!out->entries || !out->block_no || !out->prev_hash || !out->prev_is_genesis || !out->integrity))
+      return PRAOS_E_ARG;
+    for (size_t i = 0; i < y; i++) {
+      uint8_t* e = out->entries + PRAOS_CHUNK_ENTRY_SIZE * i;
+      put_be(e, col.off[i], 8);
+      put_be(e + 8, col.hoff[i] - col.off[i], 2);
+      put_be(e + 10, col.hlen[i], 2);
+      put_be(e + 12, col.crc[i], 4);
+      std::memcpy(e + 16, &col.hh[32 * i], 32);
+      put_be(e + 48, col.slot[i], 8);
+      out->block_no[i] = col.block_no[i];
+      std::memcpy(out->prev_hash + 32 * i, &col.prev[32 * i], 32);
+      out->prev_is_genesis[i] = col.gen[i];
+      out->integrity[i] = trusted(i) ? -1 : 0;
+    }
+    return PRAOS_OK;
+  };
+  const int r = run();
+  (void)hipStreamSynchronize(c->side[0]);
+  (void)hipStreamSynchronize(c->stream);
+  // the batches that borrow the arena go first
+  praos_batch_free(c, b3);
+  praos_batch_free(c, b2 && b1 ? b2 : nullptr);
+  praos_batch_free(c, b1 ? b1 : b2);
   return r;
 }
 

@@ -169,6 +169,32 @@ class Decoded(ctypes.Structure):
     _fields_ = [(name, _CT[dt]) for name, dt, _ in DECODED_FIELDS]
 
 
+# ImmutableDB chunk validation (praos_crc32 / praos_validate_chunk)
+CRC_TILE = (16384,)     # PRAOS_CRC_TILE: the tile size(s) of k_crc32.hip, counted from a span's start
+CHUNK_OK, CHUNK_ERR_READ, CHUNK_ERR_CORRUPT, CHUNK_ERR_HASH_MISMATCH, CHUNK_UNSUPPORTED = 0, 1, 2, 3, 4
+CHUNK_OUTCOMES = ("OK", "ERR_READ", "ERR_CORRUPT", "ERR_HASH_MISMATCH", "UNSUPPORTED")
+CHUNK_ENTRY_SIZE = 56
+E_ARG = -2
+
+
+class Chunk(ctypes.Structure):
+    _fields_ = [("bytes", u8p), ("bytes_len", ctypes.c_size_t), ("expected_crc", u32p),
+                ("n_expected", ctypes.c_size_t), ("block_off", u64p)]
+
+
+class ChunkResult(ctypes.Structure):
+    _fields_ = [("outcome", ctypes.c_uint32), ("integrity_bits", ctypes.c_uint32), ("blocks", ctypes.c_uint64),
+                ("checked", ctypes.c_uint64), ("truncate_at", ctypes.c_uint64), ("rescanned_from", ctypes.c_uint64),
+                ("err_slot", ctypes.c_uint64), ("err_hash", ctypes.c_uint8 * 32),
+                ("expected_prev", ctypes.c_uint8 * 32), ("actual_prev", ctypes.c_uint8 * 32),
+                ("actual_prev_is_genesis", ctypes.c_uint8), ("pad_", ctypes.c_uint8 * 7)]
+
+
+class ChunkOut(ctypes.Structure):
+    _fields_ = [("cap", ctypes.c_size_t), ("entries", u8p), ("block_no", u64p), ("prev_hash", u8p),
+                ("prev_is_genesis", u8p), ("integrity", ctypes.POINTER(ctypes.c_int8))]
+
+
 # decode status (PRAOS_DEC_*)
 DEC_RANGE, DEC_SYNTAX, DEC_SIZE, DEC_UNSUPPORTED, DEC_TRAILING, DEC_NONCANONICAL, DEC_OVERFLOW = \
     0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
@@ -319,6 +345,10 @@ SIGNATURES = {
                                                      ctypes.POINTER(ctypes.c_size_t)]),
     "praos_verify_block_integrity": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HeaderBytes), ctypes.c_uint64,
                                                     u8p, u8p]),
+    "praos_crc32": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HeaderBytes), u32p]),
+    "praos_block_batch_crc32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u32p]),
+    "praos_validate_chunk": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Chunk), ctypes.c_uint64,
+                                            ctypes.POINTER(ChunkResult), ctypes.POINTER(ChunkOut)]),
     "praos_block_batch_upload": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.POINTER(HeaderBytes)]),
     "praos_block_batch_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "praos_block_batch_download": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u8p, u8p]),
@@ -680,6 +710,73 @@ class Context:
         self.check(self.L.praos_verify_block_integrity(self.h, ctypes.byref(hb), slots_per_kes_period, ptr(res),
                                                        ptr(bh)))
         return res, bh
+
+    # ---- ImmutableDB chunk validation (k_crc32.hip, praos_validate_chunk) ----
+    def crc32(self, arena, off, length):
+        """CRC-32 (zlib) of arena[off[i]:off[i]+len[i]] on the GPU; returns u32[n]."""
+        arena, off, length = self._chunk(arena, off, length)
+        hb = self.header_bytes_struct(arena, off, length)
+        crc = np.zeros(len(off), np.uint32)
+        self.check(self.L.praos_crc32(self.h, ctypes.byref(hb), ptr(crc, u32p)))
+        return crc
+
+    def crc32_blocks(self, b, n):
+        """CRC-32 of the block spans of an upload_blocks batch (device-resident form)."""
+        crc = np.zeros(n, np.uint32)
+        self.check(self.L.praos_block_batch_crc32(self.h, b, ptr(crc, u32p)))
+        return crc
+
+    def validate_chunk(self, chunk, expected_crc=None, block_off=None, slots_per_kes_period=129600, cap=None):
+        """parseChunkFile over one chunk file's bytes (praos_validate_chunk).  expected_crc: the
+        secondary index's checksums in order (None: index missing); block_off: its blockOffsets, a
+        hint.  Returns a dict: outcome (CHUNK_*), integrity_bits, blocks, checked, truncate_at,
+        rescanned_from, err_slot, err_hash, expected_prev, actual_prev, actual_prev_is_genesis, and
+        per yielded block entries (bytes, 56 each), block_no, prev_hash, prev_is_genesis, integrity.
+        cap: capacity of the output buffers (default: grown until the blocks fit); a smaller one
+        raises PraosError with .needed set."""
+        data = np.ascontiguousarray(np.frombuffer(chunk, np.uint8) if isinstance(chunk, (bytes, bytearray))
+                                    else chunk, dtype=np.uint8)
+        ch = Chunk()
+        ch.bytes, ch.bytes_len = ptr(data), len(data)
+        ecrc = None if expected_crc is None else np.ascontiguousarray(expected_crc, dtype=np.uint32)
+        boff = None if block_off is None else np.ascontiguousarray(block_off, dtype=np.uint64)
+        ch.n_expected = 0 if ecrc is None else len(ecrc)
+        ch.expected_crc = ptr(ecrc, u32p) if ch.n_expected else None
+        if boff is not None and len(boff) != ch.n_expected:
+            raise ValueError("block_off must have one offset per expected_crc entry")
+        ch.block_off = ptr(boff, u64p) if (boff is not None and ch.n_expected) else None
+        grow = cap is None
+        cap = max(ch.n_expected, 64) if grow else cap
+        while True:
+            ent = np.zeros(cap * CHUNK_ENTRY_SIZE, np.uint8)
+            bno = np.zeros(cap, np.uint64)
+            prev = np.zeros((cap, 32), np.uint8)
+            gen = np.zeros(cap, np.uint8)
+            integ = np.zeros(cap, np.int8)
+            out = ChunkOut()
+            out.cap, out.entries, out.block_no, out.prev_hash = cap, ptr(ent), ptr(bno, u64p), ptr(prev)
+            out.prev_is_genesis, out.integrity = ptr(gen), ptr(integ, ctypes.POINTER(ctypes.c_int8))
+            res = ChunkResult()
+            rc = self.L.praos_validate_chunk(self.h, ctypes.byref(ch), slots_per_kes_period, ctypes.byref(res),
+                                             ctypes.byref(out))
+            if rc == E_ARG and res.blocks > cap:
+                if grow:
+                    cap = int(res.blocks)
+                    continue
+                msg = self.L.praos_last_error(self.h)
+                err = PraosError(f"praos rc={rc}: {msg.decode() if msg else ''}")
+                err.needed = int(res.blocks)
+                raise err
+            self.check(rc)
+            break
+        y = int(res.blocks)
+        return {"outcome": int(res.outcome), "integrity_bits": int(res.integrity_bits), "blocks": y,
+                "checked": int(res.checked), "truncate_at": int(res.truncate_at),
+                "rescanned_from": int(res.rescanned_from), "err_slot": int(res.err_slot),
+                "err_hash": bytes(res.err_hash), "expected_prev": bytes(res.expected_prev),
+                "actual_prev": bytes(res.actual_prev), "actual_prev_is_genesis": int(res.actual_prev_is_genesis),
+                "entries": ent[:y * CHUNK_ENTRY_SIZE].tobytes(), "block_no": bno[:y].copy(),
+                "prev_hash": prev[:y].copy(), "prev_is_genesis": gen[:y].copy(), "integrity": integ[:y].copy()}
 
     def upload_blocks(self, arena, off, length):
         arena, off, length = self._chunk(arena, off, length)

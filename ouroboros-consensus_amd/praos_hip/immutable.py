@@ -170,3 +170,56 @@ def make_multi_epoch_chain(ctx, cfg, epochs, epoch_length, stability_window, tpr
             "slots": np.concatenate(slots_all), "header_hash": np.concatenate(hh_all), "pools": pool_list,
             "params": p, "nonces": nonces, "state": st,
             "epoch_info": ei, "views": views, "schedules": used}
+
+
+def read_index(path, chunk):
+    """(.secondary bytes or None, checksums, block offsets) of one chunk; an index file whose
+    size is no multiple of the entry size counts as missing, as the reference treats an
+    invalid index."""
+    p = os.path.join(path, f"{chunk:05d}.secondary")
+    if not os.path.exists(p):
+        return None, None, None
+    raw = open(p, "rb").read()
+    if len(raw) % ENTRY:
+        return None, None, None
+    e = np.frombuffer(raw, np.uint8).reshape(-1, ENTRY)
+    crc = e[:, 12:16].copy().view(">u4").reshape(-1).astype(np.uint32)
+    off = e[:, 0:8].copy().view(">u8").reshape(-1).astype(np.uint64)
+    return raw, crc, off
+
+
+def chunk_report(chunk, res, sec, prev_tip):
+    """One row of validate_immutable from a parse result (Context.validate_chunk's dict):
+    the cross-chunk fit (Validation.hs:389-399: the first block's prevHash against the tip
+    before this chunk, None = Origin), the outcome, and whether the rebuilt entries are the
+    secondary file's bytes (Validation.hs:412-420).  Returns (row, tip after the chunk)."""
+    fits = True
+    if res["blocks"]:
+        if prev_tip is None:
+            fits = bool(res["prev_is_genesis"][0])
+        else:
+            fits = not res["prev_is_genesis"][0] and bytes(res["prev_hash"][0]) == prev_tip
+    row = {"chunk": chunk, "outcome": res["outcome"], "blocks": res["blocks"], "checked": res["checked"],
+           "truncate_at": res["truncate_at"], "integrity_bits": res["integrity_bits"], "fits": fits,
+           "entries_match": sec is not None and res["entries"] == sec, "entries": res["entries"]}
+    tip = res["entries"][-40:-8] if res["blocks"] else prev_tip
+    return row, tip
+
+
+def validate_immutable(ctx, path, slots_per_kes_period, parse=None):
+    """validateAllChunks over NNNNN.chunk / NNNNN.secondary (Validation.hs:150-260): one
+    praos_validate_chunk call per chunk file, in order, with the index's checksums and block
+    offsets when the index is there.  Returns one chunk_report row per chunk; stops after the
+    first chunk that has an error or does not fit its predecessor, where the reference
+    truncates.  parse: the parser (default ctx.validate_chunk), for checkers."""
+    parse = parse or (lambda data, crc, off: ctx.validate_chunk(data, crc, off, slots_per_kes_period))
+    chunks = sorted(int(f[:5]) for f in os.listdir(path) if f.endswith(".chunk"))
+    rows, tip = [], None
+    for c in chunks:
+        data = np.fromfile(os.path.join(path, f"{c:05d}.chunk"), np.uint8)
+        sec, crc, off = read_index(path, c)
+        row, tip = chunk_report(c, parse(data, crc, off), sec, tip)
+        rows.append(row)
+        if row["outcome"] != 0 or not row["fits"]:
+            break
+    return rows
