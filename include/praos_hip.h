@@ -439,6 +439,68 @@ typedef struct {
 int praos_validate_chunk(praos_ctx* ctx, const praos_chunk* chunk, uint64_t slots_per_kes_period,
                          praos_chunk_result* res, praos_chunk_out* out);
 
+/* ---- Byron blocks and EBBs in a chunk (added without a version bump; purely additive) ----
+ * praos_validate_chunk_cfg is praos_validate_chunk with the Byron era switched on:
+ * praos_validate_chunk(ctx, ch, spkp, res, out) is this call with byron_epoch_slots = 0 and
+ * is_ebb = NULL, and with byron_epoch_slots = 0 the results are byte-identical to it (a Byron
+ * item ends the parse with UNSUPPORTED).  With byron_epoch_slots > 0 a stored item
+ * 82 00 83 <hdr> <body> <extra> (EBB) or 82 01 83 <hdr> <body> <extra> (main block,
+ * Byron/Ledger/Serialisation.hs:165-177) is a block like any other; a chunk may hold both
+ * kinds (the first Shelley block's prevHash is a Byron header hash):
+ *   point / entry  headerOffset 3, headerSize = the header item's length, headerHash =
+ *                  Blake2b-256(82 0k || header); slot = epoch * byron_epoch_slots
+ *                  (+ slotInEpoch for a main block), blockNo = difficulty; the entry's
+ *                  blockOrEBB is the slot of a main block and the EPOCH NUMBER of an EBB
+ *                  (Secondary.hs:84-88); is_ebb[i] = 1 marks the EBBs (0 for every other block);
+ *   prevHash       GenesisHash for an EBB of epoch 0 (its 32 bytes are the genesis hash, not a
+ *                  block; parity unpinned), BlockHash otherwise (Block.hs:215-221);
+ *   ERR_READ       the item is [0|1, ...] but not of the shapes in csrc/k_byron.hip: a wrong list
+ *                  length, a hash that is not bytes32, a key or signature that is not bytes64, a
+ *                  signature tag other than 2, an integer too wide (pm u32, slotInEpoch u16,
+ *                  the rest u64), an item that is not well-formed, a body that is not 4 items or
+ *                  whose txPayload is not a list of 2-item lists.  This is as far as the library
+ *                  decodes Byron blocks: the reference's transaction, ssc, delegation and update
+ *                  decoders are stricter (a body of well-formed CBOR that is not a valid payload
+ *                  is a ReadFailure there, accepted here);
+ *   checkEntries   an untrusted block takes verifyBlockIntegrity (Byron/Ledger/Integrity.hs:
+ *                  21-53): an EBB passes; a main block needs pm == byron_protocol_magic
+ *                  (PRAOS_BLK_PM), the PBFT signature -- Ed25519 under the first 32 bytes of the
+ *                  delegate key over "01" || issuerXPub || 09 || CBOR(pm) || 85 || the stored
+ *                  prev, proof, slot-id, difficulty and extra items (PRAOS_BLK_PBFT_SIG; the
+ *                  delegation certificate's own signature is not part of this check) -- and
+ *                  blockMatchesHeader (PRAOS_BLK_BODY_HASH): dlgHash, updHash, nTx, witHash and
+ *                  txRoot against the stored body (the ssc proof is not compared);
+ *   UNSUPPORTED    with Byron on, only this: an untrusted main block with nTx != 1 whose ONLY
+ *                  failing check is txRoot.  The Merkle root for n = 0 and n >= 2 follows the
+ *                  published Byron rule (leaf H(00 || tx), node H(01 || l || r), split at the
+ *                  largest power of two below n, empty tree H("")) and no reference file pins
+ *                  it, so the caller lets the reference decide; truncate_at is that block and
+ *                  the blocks before it are yielded.
+ * err_slot is the offending block's slot (an EBB's too). */
+#define PRAOS_BLK_PBFT_SIG 0x08u /* Byron verifyHeaderIntegrity: the PBFT signature does not verify */
+#define PRAOS_BLK_PM       0x10u /* Byron verifyHeaderIntegrity: protocol magic /= the configured one */
+/* which of blockMatchesHeader's five comparisons failed (praos_verify_byron_integrity) */
+#define PRAOS_BYRON_W_DLG  0x01u
+#define PRAOS_BYRON_W_UPD  0x02u
+#define PRAOS_BYRON_W_NTX  0x04u
+#define PRAOS_BYRON_W_WIT  0x08u
+#define PRAOS_BYRON_W_ROOT 0x10u
+typedef struct {
+  uint64_t slots_per_kes_period;
+  uint64_t byron_epoch_slots;     /* 0 = Byron items are UNSUPPORTED */
+  uint32_t byron_protocol_magic;
+  uint32_t pad_;
+} praos_chunk_cfg;
+int praos_validate_chunk_cfg(praos_ctx* ctx, const praos_chunk* chunk, const praos_chunk_cfg* cfg,
+                             praos_chunk_result* res, praos_chunk_out* out,
+                             uint8_t* is_ebb /* out->cap bytes, may be NULL */);
+/* The direct form (tests, GetVerifiedBlock): verifyBlockIntegrity of stored Byron blocks
+ * arena[off[i], off[i] + len[i]).  result[i] = 0 or PRAOS_BLK_DECODE (not a Byron block of the
+ * shapes above) / PRAOS_BLK_PM / PRAOS_BLK_PBFT_SIG / PRAOS_BLK_BODY_HASH; which[i] (may be
+ * NULL) = PRAOS_BYRON_W_* of the failing body comparisons.  epoch_slots > 0. */
+int praos_verify_byron_integrity(praos_ctx* ctx, const praos_header_bytes* blocks, uint64_t epoch_slots,
+                                 uint32_t protocol_magic, uint8_t* result, uint8_t* which);
+
 /* ---- TPraos (Shelley..Alonzo), the d = 0 path of cardano-protocol-tpraos ----
  * Replaces SL.updateChainDepState's crypto (TPraos.hs:378-387): OVERLAY
  * praosVrfChecks (pool, VRF key, eta cert with mkSeed seedEta, leader cert with

@@ -7,6 +7,7 @@
  *   ffi_harness <immutable dir> <epoch file> <threads>
  *   ffi_harness --chunk <immutable dir> <chunk no> <slots per KES period> <members>
  *   ffi_harness --validate-chunk <immutable dir> <chunk no> <slots per KES period>
+ *   ffi_harness --validate-chunk-byron <immutable dir> <chunk no> <slots per KES period> <byron epoch slots> <pm>
  *
  * --validate-chunk: parseChunkFile as one call, as Batch.hs validateChunkBatch runs it: the chunk
  *   file as read, the secondary index's checksums and block offsets when the index is there and
@@ -942,7 +943,9 @@ static int chunk_main(const char* dir, int chunk, uint64_t spkp, int members) {
 }
 
 /* ---- parseChunkFile as one call (Batch.hs validateChunkBatch) ---- */
-static int validate_chunk_main(const char* dir, int chunk, uint64_t spkp) {
+/* es > 0: --validate-chunk-byron, the same call through praos_validate_chunk_cfg with the Byron era on
+ * (es = slots per Byron epoch, pm = protocol magic); the line also carries is_ebb */
+static int validate_chunk_main(const char* dir, int chunk, uint64_t spkp, uint64_t es, uint32_t pm) {
   static const char* OUTCOME[] = {"OK", "ERR_READ", "ERR_CORRUPT", "ERR_HASH_MISMATCH", "UNSUPPORTED"};
   char p[4096];
   size_t dl = 0, sl = 0;
@@ -964,6 +967,7 @@ static int validate_chunk_main(const char* dir, int chunk, uint64_t spkp) {
   praos_chunk_result res;
   praos_chunk_out out;
   size_t cap = n ? n : 64;
+  uint8_t* is_ebb = NULL;
   for (;;) {   /* the index says how many blocks to expect; a longer file asks again */
     out.cap = cap;
     out.entries = calloc(cap, PRAOS_CHUNK_ENTRY_SIZE);
@@ -971,18 +975,23 @@ static int validate_chunk_main(const char* dir, int chunk, uint64_t spkp) {
     out.prev_hash = calloc(cap, 32);
     out.prev_is_genesis = calloc(cap, 1);
     out.integrity = calloc(cap, 1);
-    const int rc = praos_validate_chunk(ctx, &ch, spkp, &res, &out);
+    is_ebb = calloc(cap, 1);
+    const praos_chunk_cfg cfg = {spkp, es, pm, 0};
+    const int rc = es ? praos_validate_chunk_cfg(ctx, &ch, &cfg, &res, &out, is_ebb)
+                      : praos_validate_chunk(ctx, &ch, spkp, &res, &out);
     if (rc == PRAOS_OK) break;
     if (rc != PRAOS_E_ARG || res.blocks <= cap) DIE("praos_validate_chunk -> %d: %s", rc, praos_last_error(ctx));
     free(out.entries); free(out.block_no); free(out.prev_hash); free(out.prev_is_genesis); free(out.integrity);
+    free(is_ebb);
     cap = res.blocks;
   }
   const size_t y = res.blocks;
   const int same = sec && sl == y * PRAOS_CHUNK_ENTRY_SIZE && memcmp(sec, out.entries, sl) == 0;
-  printf("{\"phase\": \"validate_chunk\", \"outcome\": \"%s\", \"integrity_bits\": %u, \"blocks\": %zu, "
+  printf("{\"phase\": \"%s\", \"outcome\": \"%s\", \"integrity_bits\": %u, \"blocks\": %zu, "
          "\"checked\": %llu, \"truncate_at\": %llu, \"rescanned_from\": %llu, \"err_slot\": %llu, "
          "\"actual_prev_is_genesis\": %u, \"entries_match\": %s, \"err_hash\": \"",
-         OUTCOME[res.outcome], res.integrity_bits, y, (unsigned long long)res.checked,
+         es ? "validate_chunk_byron" : "validate_chunk", OUTCOME[res.outcome], res.integrity_bits, y,
+         (unsigned long long)res.checked,
          (unsigned long long)res.truncate_at, (unsigned long long)res.rescanned_from,
          (unsigned long long)res.err_slot, res.actual_prev_is_genesis, same ? "true" : "false");
   hex_out(res.err_hash, 32);
@@ -996,9 +1005,14 @@ static int validate_chunk_main(const char* dir, int chunk, uint64_t spkp) {
   for (size_t i = 0; i < y; i++) printf("%s%llu", i ? ", " : "", (unsigned long long)out.block_no[i]);
   printf("], \"integrity\": [");
   for (size_t i = 0; i < y; i++) printf("%s%d", i ? ", " : "", (int)out.integrity[i]);
+  if (es) {
+    printf("], \"is_ebb\": [");
+    for (size_t i = 0; i < y; i++) printf("%s%d", i ? ", " : "", (int)is_ebb[i]);
+  }
   printf("]}\n");
   fflush(stdout);
   praos_close(ctx);
+  free(is_ebb);
   free(out.entries); free(out.block_no); free(out.prev_hash); free(out.prev_is_genesis); free(out.integrity);
   free(crc); free(boff); free(data); free(sec);
   return 0;
@@ -1009,9 +1023,16 @@ int main(int argc, char** argv) {
   if (argc == 6 && strcmp(argv[1], "--chunk") == 0)
     return chunk_main(argv[2], atoi(argv[3]), strtoull(argv[4], NULL, 10), atoi(argv[5]));
   if (argc == 5 && strcmp(argv[1], "--validate-chunk") == 0)
-    return validate_chunk_main(argv[2], atoi(argv[3]), strtoull(argv[4], NULL, 10));
+    return validate_chunk_main(argv[2], atoi(argv[3]), strtoull(argv[4], NULL, 10), 0, 0);
+  if (argc == 7 && strcmp(argv[1], "--validate-chunk-byron") == 0) {
+    const uint64_t es = strtoull(argv[5], NULL, 10);
+    if (es == 0) DIE("--validate-chunk-byron: epoch slots must be positive");
+    return validate_chunk_main(argv[2], atoi(argv[3]), strtoull(argv[4], NULL, 10), es,
+                               (uint32_t)strtoul(argv[6], NULL, 10));
+  }
   if (argc != 4) DIE("usage: %s <immutable dir> <epoch file> <threads> | --chunk <dir> <chunk> <spkp> <members>"
-                     " | --validate-chunk <dir> <chunk> <spkp>", argv[0]);
+                     " | --validate-chunk <dir> <chunk> <spkp>"
+                     " | --validate-chunk-byron <dir> <chunk> <spkp> <byron epoch slots> <protocol magic>", argv[0]);
   read_epoch_file(argv[2]);
   chain_t ch;
   read_chain(argv[1], &ch);

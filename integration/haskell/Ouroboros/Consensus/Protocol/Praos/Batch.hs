@@ -70,6 +70,7 @@ import           Control.Exception (Exception, bracket, bracket_, throwIO)
 import           Control.Monad (forM_, when)
 import qualified Data.ByteString as BS
 import qualified Data.ByteString.Unsafe as BSU
+import           Data.Maybe (fromMaybe)
 import qualified Data.Vector.Storable as VS
 import qualified Data.Vector.Storable.Mutable as VSM
 import           Data.Ratio (denominator, numerator)
@@ -185,6 +186,12 @@ foreign import ccall safe "praos_verify_drain" c_verify_drain :: Ptr PraosCtx ->
 -- layout praos_chunk_out (48 bytes): cap@0 entries@8 block_no@16 prev_hash@24 prev_is_genesis@32 integrity@40
 foreign import ccall safe "praos_validate_chunk" c_validate_chunk
   :: Ptr PraosCtx -> Ptr () -> Word64 -> Ptr () -> Ptr () -> IO CInt
+-- added without a version bump (purely additive): the same call with the Byron era switched on.
+-- Its configuration struct (checked against the C compiler by tests/test_byron_abi.py;
+-- "layout-byron": tests/test_chunk_abi.py owns the "layout" lines above and knows only its own structs):
+-- layout-byron praos_chunk_cfg (24 bytes): slots_per_kes_period@0 byron_epoch_slots@8 byron_protocol_magic@16 pad_@20
+foreign import ccall safe "praos_validate_chunk_cfg" c_validate_chunk_cfg
+  :: Ptr PraosCtx -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> Ptr Word8 -> IO CInt
 
 abiVersion :: CInt
 abiVersion = 15
@@ -967,7 +974,9 @@ verifyChunkIntegrity ctx spkp crc32 chunk entries = do
     , cvTruncateAt = maybe (fromIntegral (BS.length chunk)) (\i -> fst (entries !! i)) firstBad }
 
 -- | What parseChunkFile ended with (ChunkFileError, Parser.hs:60-90), or that the chunk holds
--- a block this library does not parse (Byron): the caller then runs the reference parser.
+-- a block this library leaves to the reference parser: a Byron block when no Byron parameters
+-- were given, or -- with them -- a Byron main block with nTx /= 1 whose only failing check is
+-- the Merkle root of its transactions, a rule no reference file pins.
 data ChunkOutcome
   = ChunkOK
   | ChunkErrRead                                  -- ^ ChunkErrRead (a ReadIncrementalErr)
@@ -989,6 +998,8 @@ data ChunkParse = ChunkParse
   , cpChecked       :: !Word64
   , cpTruncateAt    :: !Word64
   , cpRescannedFrom :: !Word64
+  , cpIsEBB         :: !(VS.Vector Word8)  -- ^ 1 for an EBB: its entry's blockOrEBB is the epoch number
+  , cpByronEpochSlots :: !Word64           -- ^ the Byron epoch length the parse ran with (0: Byron off)
   }
 
 -- | parseChunkFile (ImmutableDB/Impl/Parser.hs:92-197) as one device call: the chunk file as
@@ -998,11 +1009,19 @@ data ChunkParse = ChunkParse
 -- not match all run on the GPU; validateChunk (Validation.hs:374-420) compares 'cpEntries' with
 -- the index file's bytes and rewrites it when they differ (immutabledb-validation.patch).
 -- Replayed from C by ffi_harness --validate-chunk.
-validateChunkBatch :: PraosBatchCtx -> Word64 -> BS.ByteString -> [(Word64, Word32)] -> IO ChunkParse
-validateChunkBatch (PraosBatchGroup _ _ _) _ _ _ =
+--
+-- The Byron parameters, @Just (epochSlots, protocolMagic)@ (epochSlots > 0), switch the Byron
+-- era on (praos_validate_chunk_cfg; ffi_harness --validate-chunk-byron): EBBs and Byron main
+-- blocks are decoded, PBFT-verified and matched against their body proof like any other block,
+-- so a database validates from genesis.  @Nothing@ is the call as it was: a Byron item ends the
+-- parse with 'ChunkUnsupported'.
+validateChunkBatch :: PraosBatchCtx -> Word64 -> Maybe (Word64, Word32) -> BS.ByteString -> [(Word64, Word32)]
+                   -> IO ChunkParse
+validateChunkBatch (PraosBatchGroup _ _ _) _ _ _ _ =
   throwIO (PraosBatchError (-2) "validateChunkBatch: one context, not a group")
-validateChunkBatch ctx@(PraosBatchCtx p) spkp chunk entries = go (max 64 (length entries))
+validateChunkBatch ctx@(PraosBatchCtx p) spkp byron chunk entries = go (max 64 (length entries))
   where
+    (byronSlots, byronMagic) = fromMaybe (0, 0) byron
     nExp = length entries
     crcs = VS.fromList (map snd entries)
     offs = VS.fromList (map fst entries)
@@ -1012,11 +1031,14 @@ validateChunkBatch ctx@(PraosBatchCtx p) spkp chunk entries = go (max 64 (length
       prevs <- VSM.new (32 * cap) :: IO (VSM.IOVector Word8)
       gens <- VSM.new cap :: IO (VSM.IOVector Word8)
       integ <- VSM.new cap :: IO (VSM.IOVector Word8)
+      ebbs <- VSM.replicate cap 0 :: IO (VSM.IOVector Word8)
       r <- BSU.unsafeUseAsCStringLen chunk $ \(cp, clen) ->
         VS.unsafeWith crcs $ \crcp -> VS.unsafeWith offs $ \offp ->
         VSM.unsafeWith ents $ \ep -> VSM.unsafeWith bnos $ \bp -> VSM.unsafeWith prevs $ \pp ->
-        VSM.unsafeWith gens $ \gp -> VSM.unsafeWith integ $ \ip ->
-        allocaBytes 40 $ \ch -> allocaBytes 152 $ \res -> allocaBytes 48 $ \out -> do
+        VSM.unsafeWith gens $ \gp -> VSM.unsafeWith integ $ \ip -> VSM.unsafeWith ebbs $ \bbp ->
+        allocaBytes 40 $ \ch -> allocaBytes 152 $ \res -> allocaBytes 48 $ \out -> allocaBytes 24 $ \cfg -> do
+          pokeByteOff cfg 0 spkp >> pokeByteOff cfg 8 byronSlots
+          pokeByteOff cfg 16 byronMagic >> pokeByteOff cfg 20 (0 :: Word32)
           pokeByteOff ch 0 cp >> pokeByteOff ch 8 (fromIntegral clen :: CSize)
           pokeByteOff ch 16 (if nExp == 0 then nullPtr else crcp)
           pokeByteOff ch 24 (fromIntegral nExp :: CSize)
@@ -1024,7 +1046,9 @@ validateChunkBatch ctx@(PraosBatchCtx p) spkp chunk entries = go (max 64 (length
           pokeByteOff out 0 (fromIntegral cap :: CSize)
           pokeByteOff out 8 ep >> pokeByteOff out 16 bp >> pokeByteOff out 24 pp
           pokeByteOff out 32 gp >> pokeByteOff out 40 ip
-          rc <- c_validate_chunk p (castPtr ch) spkp (castPtr res) (castPtr out)
+          rc <- if byronSlots == 0
+                  then c_validate_chunk p (castPtr ch) spkp (castPtr res) (castPtr out)
+                  else c_validate_chunk_cfg p (castPtr ch) (castPtr cfg) (castPtr res) (castPtr out) bbp
           blocks <- peekByteOff res 8 :: IO Word64
           if rc == (-2) && blocks > fromIntegral cap
             then pure (Left (fromIntegral blocks))      -- out->cap too small: ask again
@@ -1049,6 +1073,7 @@ validateChunkBatch ctx@(PraosBatchCtx p) spkp chunk entries = go (max 64 (length
           bv <- VS.unsafeFreeze bnos
           pv <- VS.unsafeFreeze prevs
           gv <- VS.unsafeFreeze gens
+          bbv <- VS.unsafeFreeze ebbs
           let firstPrev | y == 0 = Nothing
                         | gv VS.! 0 /= 0 = Just Nothing
                         | otherwise = Just (Just (BS.pack (VS.toList (VS.take 32 pv))))
@@ -1065,7 +1090,9 @@ validateChunkBatch ctx@(PraosBatchCtx p) spkp chunk entries = go (max 64 (length
             , cpFirstPrev = firstPrev
             , cpChecked = checked
             , cpTruncateAt = trunc
-            , cpRescannedFrom = rescan }
+            , cpRescannedFrom = rescan
+            , cpIsEBB = VS.take y bbv
+            , cpByronEpochSlots = byronSlots }
 
 -- ---------------------------------------------------------------- errors
 

@@ -87,7 +87,9 @@ inline int64_t chunk_item_end(const uint8_t* a, uint64_t pos, uint64_t end) {
 }
 
 // a Byron block or EBB of the HardForkBlock encoding: [0, ...] / [1, ...]
-// (a definite-length array whose first element is the unsigned integer 0 or 1)
+// (a definite-length array whose first element is the unsigned integer 0 or 1).  Names the
+// verdict of an item that ended the parse: UNSUPPORTED while Byron is off, ERR_READ once
+// praos_validate_chunk_cfg decodes Byron items itself (k_byron.hip).
 inline bool is_byron_item(const uint8_t* a, uint64_t pos, uint64_t end) {
   Cur c{a, pos, end};
   uint32_t mt, ai;

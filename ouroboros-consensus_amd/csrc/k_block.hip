@@ -27,86 +27,9 @@
 // ~3.6 TB/s of block bytes.  The KES verify per block dominates for small blocks.
 #include "kcommon.hpp"
 #include "arena.hpp"
+#include "cbor_dev.hpp"
 
 namespace {
-
-constexpr uint32_t MAX_INDEF = 16;          // nested indefinite items (oracle MAX_INDEF)
-constexpr uint64_t BIG = 1ull << 62;        // "at an indefinite level" marker for `need`
-
-struct Cur {
-  const uint8_t* __restrict__ a;
-  uint64_t p, end;
-  bool ok;
-};
-
-// item head: major type, additional info, argument (indef = true for ai 31)
-__device__ __forceinline__ bool head(Cur& c, uint32_t& mt, uint32_t& ai, uint64_t& arg, bool& indef) {
-  if (c.p >= c.end) return false;
-  const uint32_t ib = c.a[c.p++];
-  mt = ib >> 5;
-  ai = ib & 31u;
-  indef = false;
-  if (ai < 24) { arg = ai; return true; }
-  if (ai <= 27) {
-    const uint32_t nb = 1u << (ai - 24);
-    if (nb > c.end - c.p) return false;
-    uint64_t v = 0;
-    for (uint32_t k = 0; k < nb; k++) v = (v << 8) | c.a[c.p + k];
-    c.p += nb;
-    arg = v;
-    return true;
-  }
-  if (ai == 31 && (mt == 2 || mt == 3 || mt == 4 || mt == 5 || mt == 7)) { indef = true; arg = 0; return true; }
-  return false;   // 28..30 reserved; indefinite uint / nint / tag
-}
-
-// advance c.p past ONE well-formed CBOR item (oracle block_integrity.cbor_skip)
-__device__ bool cbor_skip(Cur& c) {
-  uint64_t need = 1;
-  uint64_t st_need[MAX_INDEF];
-  uint8_t st_kind[MAX_INDEF];
-  uint32_t sp = 0;
-  while (need || sp) {
-    if (c.p >= c.end) return false;
-    if (c.a[c.p] == 0xFF) {
-      if (!sp || need != BIG) return false;
-      need = st_need[--sp];
-      c.p++;
-      continue;
-    }
-    uint32_t mt, ai;
-    uint64_t arg;
-    bool indef;
-    if (!head(c, mt, ai, arg, indef)) return false;
-    if (sp && need == BIG && st_kind[sp - 1] != 0 && (mt != st_kind[sp - 1] || indef)) return false;
-    if (need != BIG) need -= 1;
-    if (mt == 2 || mt == 3) {
-      if (indef) {
-        if (sp == MAX_INDEF) return false;
-        st_need[sp] = need; st_kind[sp] = (uint8_t)mt; sp++;
-        need = BIG;
-      } else {
-        if (arg > c.end - c.p) return false;
-        c.p += arg;
-      }
-    } else if (mt == 4 || mt == 5) {
-      if (indef) {
-        if (sp == MAX_INDEF) return false;
-        st_need[sp] = need; st_kind[sp] = 0; sp++;
-        need = BIG;
-      } else {
-        const uint64_t k = mt == 5 ? 2 * arg : arg;
-        if (arg > c.end - c.p || k > c.end - c.p) return false;   // each item takes >= 1 byte
-        need += k;
-      }
-    } else if (mt == 6) {
-      need += 1;
-    } else if (mt == 7) {
-      if (ai == 24 && arg < 32) return false;
-    }
-  }
-  return true;
-}
 
 __global__ void __launch_bounds__(NT) k_block_split(size_t n, const uint8_t* __restrict__ arena, uint64_t arena_len,
                                                     uint64_t* __restrict__ off_io, uint32_t* __restrict__ len_io,

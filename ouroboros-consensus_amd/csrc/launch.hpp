@@ -203,5 +203,19 @@ void launch_seg_hash(dim3 grid, dim3 block, hipStream_t stream, size_t n, const 
 void launch_block_join(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint8_t* nseg,
                        const uint8_t* split_status, const uint16_t* dec_status, const uint16_t* kes_bits,
                        const uint8_t* seg_hash, const uint8_t* body_hash, uint8_t* result, uint8_t* calc_hash);
+// k_byron.hip: Byron envelope + header columns (kind: 0 not Byron, 1 EBB, 2 main block, 3 does not decode;
+// epoch_out: the header's epoch; spans: PRAOS_BYRON_SPANS u32 columns per block, may be null) and
+// verifyBlockIntegrity of Byron blocks (which: PRAOS_BYRON_W_* | PRAOS_BYRON_W_ONE_TX)
+#define PRAOS_BYRON_SPANS 28
+#define PRAOS_BYRON_W_ONE_TX 0x80u   // which[], host-internal: the block holds exactly one transaction
+void launch_byron_split(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint8_t* arena, uint64_t arena_len,
+                        const uint64_t* blk_off, const uint32_t* blk_len, uint64_t epoch_slots, uint64_t* hoff,
+                        uint32_t* hlen, uint64_t* slot, uint64_t* block_no, uint8_t* prev_hash, uint8_t* prev_genesis,
+                        uint8_t* header_hash, uint8_t* split_status, uint16_t* dec_status, uint8_t* kind,
+                        uint64_t* epoch_out, uint32_t* spans);
+void launch_byron_integrity(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint8_t* arena,
+                            const uint64_t* blk_off, const uint32_t* blk_len, const uint8_t* kind,
+                            const uint32_t* spans, uint32_t cfg_pm, const ge_niels* gbtab, ge_cached* tabs,
+                            uint8_t* result, uint8_t* which);
 // replay: nonce contribution of each header's certified VRF output (k_misc.hip)
 void launch_vrf_nonce(hipStream_t stream, size_t n, const uint8_t* vrf_out, int tpraos, uint8_t* nonce_out);

@@ -195,6 +195,15 @@ class ChunkOut(ctypes.Structure):
                 ("prev_is_genesis", u8p), ("integrity", ctypes.POINTER(ctypes.c_int8))]
 
 
+class ChunkCfg(ctypes.Structure):
+    _fields_ = [("slots_per_kes_period", ctypes.c_uint64), ("byron_epoch_slots", ctypes.c_uint64),
+                ("byron_protocol_magic", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
+
+
+# Byron blocks: further PRAOS_BLK_* bits and the failing body comparisons (PRAOS_BYRON_W_*)
+BLK_PBFT_SIG, BLK_PM = 0x08, 0x10
+BYRON_W_DLG, BYRON_W_UPD, BYRON_W_NTX, BYRON_W_WIT, BYRON_W_ROOT = 0x01, 0x02, 0x04, 0x08, 0x10
+
 # decode status (PRAOS_DEC_*)
 DEC_RANGE, DEC_SYNTAX, DEC_SIZE, DEC_UNSUPPORTED, DEC_TRAILING, DEC_NONCANONICAL, DEC_OVERFLOW = \
     0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
@@ -349,6 +358,10 @@ SIGNATURES = {
     "praos_block_batch_crc32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u32p]),
     "praos_validate_chunk": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Chunk), ctypes.c_uint64,
                                             ctypes.POINTER(ChunkResult), ctypes.POINTER(ChunkOut)]),
+    "praos_validate_chunk_cfg": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Chunk), ctypes.POINTER(ChunkCfg),
+                                                ctypes.POINTER(ChunkResult), ctypes.POINTER(ChunkOut), u8p]),
+    "praos_verify_byron_integrity": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HeaderBytes), ctypes.c_uint64,
+                                                    ctypes.c_uint32, u8p, u8p]),
     "praos_block_batch_upload": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.POINTER(HeaderBytes)]),
     "praos_block_batch_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "praos_block_batch_download": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u8p, u8p]),
@@ -726,14 +739,36 @@ class Context:
         self.check(self.L.praos_block_batch_crc32(self.h, b, ptr(crc, u32p)))
         return crc
 
-    def validate_chunk(self, chunk, expected_crc=None, block_off=None, slots_per_kes_period=129600, cap=None):
+    def verify_byron_integrity(self, arena, off, length, epoch_slots, protocol_magic):
+        """verifyBlockIntegrity of stored Byron blocks and EBBs arena[off[i]:off[i]+len[i]]
+        (praos_verify_byron_integrity); returns (result u8[n] of PRAOS_BLK_* bits, which u8[n] of
+        BYRON_W_* bits: the failing comparisons of blockMatchesHeader)."""
+        arena, off, length = self._chunk(arena, off, length)
+        n = len(off)
+        hb = self.header_bytes_struct(arena, off, length)
+        res = np.zeros(n, np.uint8)
+        which = np.zeros(n, np.uint8)
+        self.check(self.L.praos_verify_byron_integrity(self.h, ctypes.byref(hb), epoch_slots, protocol_magic,
+                                                       ptr(res), ptr(which)))
+        return res, which
+
+    def validate_chunk(self, chunk, expected_crc=None, block_off=None, slots_per_kes_period=129600, cap=None,
+                       byron=None):
         """parseChunkFile over one chunk file's bytes (praos_validate_chunk).  expected_crc: the
         secondary index's checksums in order (None: index missing); block_off: its blockOffsets, a
         hint.  Returns a dict: outcome (CHUNK_*), integrity_bits, blocks, checked, truncate_at,
         rescanned_from, err_slot, err_hash, expected_prev, actual_prev, actual_prev_is_genesis, and
         per yielded block entries (bytes, 56 each), block_no, prev_hash, prev_is_genesis, integrity.
         cap: capacity of the output buffers (default: grown until the blocks fit); a smaller one
-        raises PraosError with .needed set."""
+        raises PraosError with .needed set.
+        byron: None (a Byron item ends the parse with UNSUPPORTED), or (epoch_slots,
+        protocol_magic): praos_validate_chunk_cfg decodes and checks Byron blocks and EBBs too, an
+        EBB's entry carries its epoch number, and the dict also has is_ebb per yielded block."""
+        cfg = None
+        if byron is not None:
+            cfg = ChunkCfg(slots_per_kes_period, int(byron[0]), int(byron[1]), 0)
+            if cfg.byron_epoch_slots == 0:
+                raise ValueError("byron epoch_slots must be positive")
         data = np.ascontiguousarray(np.frombuffer(chunk, np.uint8) if isinstance(chunk, (bytes, bytearray))
                                     else chunk, dtype=np.uint8)
         ch = Chunk()
@@ -757,8 +792,13 @@ class Context:
             out.cap, out.entries, out.block_no, out.prev_hash = cap, ptr(ent), ptr(bno, u64p), ptr(prev)
             out.prev_is_genesis, out.integrity = ptr(gen), ptr(integ, ctypes.POINTER(ctypes.c_int8))
             res = ChunkResult()
-            rc = self.L.praos_validate_chunk(self.h, ctypes.byref(ch), slots_per_kes_period, ctypes.byref(res),
-                                             ctypes.byref(out))
+            ebb = np.zeros(cap, np.uint8)
+            if cfg is None:
+                rc = self.L.praos_validate_chunk(self.h, ctypes.byref(ch), slots_per_kes_period, ctypes.byref(res),
+                                                 ctypes.byref(out))
+            else:
+                rc = self.L.praos_validate_chunk_cfg(self.h, ctypes.byref(ch), ctypes.byref(cfg), ctypes.byref(res),
+                                                     ctypes.byref(out), ptr(ebb))
             if rc == E_ARG and res.blocks > cap:
                 if grow:
                     cap = int(res.blocks)
@@ -770,7 +810,8 @@ class Context:
             self.check(rc)
             break
         y = int(res.blocks)
-        return {"outcome": int(res.outcome), "integrity_bits": int(res.integrity_bits), "blocks": y,
+        extra = {} if cfg is None else {"is_ebb": ebb[:y].copy()}
+        return {**extra, "outcome": int(res.outcome), "integrity_bits": int(res.integrity_bits), "blocks": y,
                 "checked": int(res.checked), "truncate_at": int(res.truncate_at),
                 "rescanned_from": int(res.rescanned_from), "err_slot": int(res.err_slot),
                 "err_hash": bytes(res.err_hash), "expected_prev": bytes(res.expected_prev),

@@ -206,13 +206,15 @@ def chunk_report(chunk, res, sec, prev_tip):
     return row, tip
 
 
-def validate_immutable(ctx, path, slots_per_kes_period, parse=None):
+def validate_immutable(ctx, path, slots_per_kes_period, parse=None, byron=None):
     """validateAllChunks over NNNNN.chunk / NNNNN.secondary (Validation.hs:150-260): one
     praos_validate_chunk call per chunk file, in order, with the index's checksums and block
     offsets when the index is there.  Returns one chunk_report row per chunk; stops after the
     first chunk that has an error or does not fit its predecessor, where the reference
-    truncates.  parse: the parser (default ctx.validate_chunk), for checkers."""
-    parse = parse or (lambda data, crc, off: ctx.validate_chunk(data, crc, off, slots_per_kes_period))
+    truncates.  parse: the parser (default ctx.validate_chunk), for checkers.  byron: None, or
+    (epoch_slots, protocol_magic) for a database that starts at genesis (without it the first
+    Byron chunk is UNSUPPORTED)."""
+    parse = parse or (lambda data, crc, off: ctx.validate_chunk(data, crc, off, slots_per_kes_period, byron=byron))
     chunks = sorted(int(f[:5]) for f in os.listdir(path) if f.endswith(".chunk"))
     rows, tip = [], None
     for c in chunks:
