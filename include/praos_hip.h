@@ -501,6 +501,98 @@ int praos_validate_chunk_cfg(praos_ctx* ctx, const praos_chunk* chunk, const pra
 int praos_verify_byron_integrity(praos_ctx* ctx, const praos_header_bytes* blocks, uint64_t epoch_slots,
                                  uint32_t protocol_magic, uint8_t* result, uint8_t* which);
 
+/* ---- Byron header validation: PBFT (additive as the two sections above: ABI version unchanged) ----
+ * validateHeader for Byron = validateEnvelope (HeaderValidation.hs:297-344 with the Byron
+ * instance, Byron/Ledger/HeaderValidation.hs:39-75) + PBFT updateChainDepState
+ * (Protocol/PBFT.hs:320-353, the window of Protocol/PBFT/State.hs:206-228), over the view
+ * Byron/Ledger/PBFT.hs:43-69 builds.  Split as the Praos path is: the per-header work on the
+ * GPU (praos_verify_pbft_headers), the sequential fold on the host
+ * (praos_pbft_update_chain_dep_state).  One delegation map per call: the caller splits a batch
+ * at a re-delegation.  Not checked (the Byron ledger's, not PBFT's): the delegation certificate's
+ * own signature.  Ed25519 edge rules are ed25519_verify_core's, as praos_verify_byron_integrity's
+ * (cardano-crypto's are not pinned by the reference tree). */
+#define PRAOS_PBFT_BIT_DECODE       0x01u /* not a Byron header of the shapes in csrc/k_byron.hip (for its is_ebb) */
+#define PRAOS_PBFT_BIT_SIG          0x02u /* PBftInvalidSignature (PBFT.hs:330-336) */
+#define PRAOS_PBFT_BIT_NOT_DELEGATE 0x04u /* PBftNotGenesisDelegate (PBFT.hs:344-348): hashVerKey not in the map */
+/* verdicts of the fold, after the ones in use */
+#define PRAOS_V_PBFT_INVALID_SIG   20 /* PBftInvalidSignature */
+#define PRAOS_V_PBFT_INVALID_SLOT  21 /* PBftInvalidSlot: slot < lastSignedSlot (PBFT.hs:341-342) */
+#define PRAOS_V_PBFT_NOT_DELEGATE  22 /* PBftNotGenesisDelegate */
+#define PRAOS_V_PBFT_EXCEEDED      23 /* PBftExceededSignThreshold gk n (PBFT.hs:351-352); aux = n */
+#define PRAOS_V_ENV_EBB_IN_SLOT    24 /* UnexpectedEBBInSlot (Byron/Ledger/HeaderValidation.hs:58-60) */
+typedef struct {
+  uint64_t window_size;           /* k: PBftWindowSize */
+  uint64_t threshold;             /* floor (pbftSignatureThreshold * k), computed by the caller: no float crosses the ABI */
+  uint64_t epoch_slots;           /* > 0 */
+  uint32_t protocol_magic;        /* the configured one: part of the signed message (mkByronContextDSIGN) */
+  uint32_t pad_;
+} praos_pbft_params;
+typedef struct {
+  uint8_t* bits;                  /* n: PRAOS_PBFT_BIT_* */
+  int32_t* gk_idx;                /* n: index of the delegate's pair in delegs, -1 when absent (EBBs: -1) */
+  uint64_t* slot;                 /* n: epoch * epoch_slots + slotInEpoch; an EBB's epoch * epoch_slots */
+  uint64_t* block_no;             /* n: difficulty */
+  uint8_t* prev_hash;             /* n*32 (zeros when GenesisHash) */
+  uint8_t* prev_is_genesis;       /* n: an EBB of epoch 0 */
+  uint8_t* header_hash;           /* n*32: Blake2b-256(82 0k || header) */
+  uint8_t* delegate_hash;         /* n*28, may be NULL: hashVerKey of the delegate (zeros for an EBB) */
+} praos_pbft_out;
+/* hashVerKey of Byron (cardano-crypto-wrapper): Blake2b-224(SHA3-256(58 40 || xpub64)); keys64 n*64,
+ * out28 n*28.  On the device of a device context, on the host of a host-only one. */
+int praos_byron_key_hash(praos_ctx* ctx, const uint8_t* keys64, size_t n, uint8_t* out28);
+/* The per-header half.  in: the stored headers (headerOffset / headerSize of the secondary
+ * index); is_ebb: n bytes; delegs: n_delegs pairs of 56 bytes (genesis key hash 28, delegate key
+ * hash 28), the Bimap of the ledger view: a duplicate in either column is PRAOS_E_ARG, a span
+ * outside the arena too.  A main header that decodes gets its delegate looked up and its
+ * signature verified; an EBB and a header that does not decode skip both.  PRAOS_OPT_KEYCACHE 0
+ * turns the delegate-key cache off; results are the same either way.  Needs a device. */
+int praos_verify_pbft_headers(praos_ctx* ctx, const praos_header_bytes* in, const uint8_t* is_ebb,
+                              const praos_pbft_params* params, const uint8_t* delegs, uint32_t n_delegs,
+                              praos_pbft_out* out);
+/* Which kernels the context's last praos_verify_pbft_headers ran: out[0] = 1 when the delegate-key
+ * cache ran (0: every verify uncached), out[1] = keys cached, out[2] = verifies on cached keys
+ * (k_pbft_sig_ck), out[3] = uncached verifies (k_pbft_sig).  Results do not depend on any of this. */
+int praos_pbft_stats(praos_ctx* ctx, uint32_t out[4]);
+typedef struct {
+  uint8_t origin;                 /* 1: no tip (Origin); the other fields are ignored */
+  uint8_t is_ebb;
+  uint8_t pad_[6];
+  uint64_t slot;
+  uint64_t block_no;
+  uint8_t hash[32];
+} praos_pbft_tip;
+typedef struct {                  /* PBftState: the signers in the window, oldest first */
+  uint64_t cap;                   /* capacity of the arrays; the fold needs cap >= window_size > 0 */
+  uint64_t n;
+  uint64_t* slot;                 /* cap */
+  uint8_t* genesis_hash;          /* cap*28 */
+} praos_pbft_state;
+/* The sequential half, on the host (works on a host-only context), over the outputs above.  Per
+ * header: PRAOS_PBFT_BIT_DECODE -> PRAOS_V_INPUT; then the envelope in the reference's order --
+ * block number (0 at Origin; the tip's for an EBB after a non-EBB; the tip's + 1 otherwise:
+ * PRAOS_V_ENV_BLOCK_NO, aux = expected), slot (>= 0 at Origin; >= the tip's for a non-EBB after an
+ * EBB; >= the tip's + 1 otherwise: PRAOS_V_ENV_SLOT_NO, aux = the minimum), prev hash
+ * (PRAOS_V_ENV_PREV_HASH), an EBB whose slot mod epoch_slots /= 0 (PRAOS_V_ENV_EBB_IN_SLOT) --
+ * then, for a main header, PBFT in its order: signature, slot < lastSignedSlot, delegate, and the
+ * window step: append (slot, genesis key), drop the oldest signer iff the window held exactly
+ * window_size signers before the append, PRAOS_V_PBFT_EXCEEDED iff the key's count after that
+ * exceeds threshold (aux = the count).  An EBB leaves the state alone.  Batch semantics are
+ * praos_update_chain_dep_state's: *chain_stop = the first failing header (n when none), tip and
+ * st on return are those at chain_stop, later headers get would-be verdicts against a working
+ * copy that skips the invalid ones.  aux (n) may be NULL.  window_size = 0 is PRAOS_E_ARG (no
+ * window the reference's append could keep a signer in). */
+int praos_pbft_update_chain_dep_state(praos_ctx* ctx, size_t n, const praos_pbft_out* h, const uint8_t* is_ebb,
+                                      const praos_pbft_params* params, const uint8_t* delegs, uint32_t n_delegs,
+                                      praos_pbft_tip* tip, praos_pbft_state* st, uint8_t* verdict, uint64_t* aux,
+                                      size_t* chain_stop);
+/* encodePBftState / decodePBftState (Protocol/PBFT/State.hs:277-305): [1, {genesis key hash:
+ * [_ slots, newest first]}], keys in ascending byte order, an empty window a0.  encode: *len
+ * gets the size; PRAOS_E_ARG if cap is too small (call with cap 0 to size).  decode: the signers
+ * sorted by slot, stable over (key order, stored order) as sortOn is; st->n gets the count,
+ * PRAOS_E_ARG if it exceeds st->cap or the bytes are not that encoding. */
+int praos_pbft_state_encode(const praos_pbft_state* st, uint8_t* out, size_t cap, size_t* len);
+int praos_pbft_state_decode(const uint8_t* in, size_t len, praos_pbft_state* st);
+
 /* ---- TPraos (Shelley..Alonzo), the d = 0 path of cardano-protocol-tpraos ----
  * Replaces SL.updateChainDepState's crypto (TPraos.hs:378-387): OVERLAY
  * praosVrfChecks (pool, VRF key, eta cert with mkSeed seedEta, leader cert with

@@ -8,6 +8,7 @@
  *   ffi_harness --chunk <immutable dir> <chunk no> <slots per KES period> <members>
  *   ffi_harness --validate-chunk <immutable dir> <chunk no> <slots per KES period>
  *   ffi_harness --validate-chunk-byron <immutable dir> <chunk no> <slots per KES period> <byron epoch slots> <pm>
+ *   ffi_harness --pbft-headers <immutable dir> <window> <threshold> <byron epoch slots> <pm> <delegs file>
  *
  * --validate-chunk: parseChunkFile as one call, as Batch.hs validateChunkBatch runs it: the chunk
  *   file as read, the secondary index's checksums and block offsets when the index is there and
@@ -1018,6 +1019,100 @@ static int validate_chunk_main(const char* dir, int chunk, uint64_t spkp, uint64
   return 0;
 }
 
+/* ---- Byron header validation (Batch.hs validatePBftHeaderBatch) ---- */
+/* --pbft-headers: the chunk files of <dir> in order; per chunk the header spans of the secondary
+ * index (blockOffset + headerOffset, headerSize) and the EBB flag of each block's two prefix bytes
+ * go through praos_verify_pbft_headers, then praos_pbft_update_chain_dep_state with the tip and the
+ * PBftState carried from the chunk before; stops at the first invalid header.  <delegs file>: one
+ * "<genesis key hash, 56 hex> <delegate key hash, 56 hex>" line per pair.  Prints the headers
+ * validated, the stopping header's verdict, aux and bits, the tip and praos_pbft_state_encode of
+ * the state it ends in. */
+static int pbft_headers_main(const char* dir, uint64_t window, uint64_t threshold, uint64_t es, uint32_t pm,
+                             const char* delegs_file) {
+  uint8_t* delegs = NULL;
+  uint32_t nd = 0;
+  FILE* f = fopen(delegs_file, "r");
+  if (!f) DIE("cannot open %s", delegs_file);
+  char g[128], d[128];
+  while (fscanf(f, "%120s %120s", g, d) == 2) {
+    delegs = realloc(delegs, 56 * (size_t)(nd + 1));
+    hex_in(g, delegs + 56 * (size_t)nd, 28);
+    hex_in(d, delegs + 56 * (size_t)nd + 28, 28);
+    nd++;
+  }
+  fclose(f);
+  praos_ctx* ctx = praos_open(0);
+  if (!ctx) DIE("praos_open(0)");
+  const praos_pbft_params P = {window, threshold, es, pm, 0};
+  praos_pbft_tip tip;
+  memset(&tip, 0, sizeof tip);
+  tip.origin = 1;
+  const size_t cap = window ? (size_t)window : 1;
+  praos_pbft_state st = {cap, 0, calloc(cap, 8), calloc(cap, 28)};
+  size_t total = 0, valid = 0;
+  int stop_chunk = -1;
+  unsigned stop_verdict = 0, stop_bits = 0;
+  unsigned long long stop_aux = 0, stop_index = 0;
+  for (int chunk = 0; stop_chunk < 0; chunk++) {
+    char p[4096];
+    size_t dl = 0, sl = 0;
+    snprintf(p, sizeof p, "%s/%05d.chunk", dir, chunk);
+    uint8_t* data = slurp(p, &dl);
+    if (!data) break;
+    snprintf(p, sizeof p, "%s/%05d.secondary", dir, chunk);
+    uint8_t* sec = slurp(p, &sl);
+    if (!sec || sl % PRAOS_CHUNK_ENTRY_SIZE) DIE("chunk %d: missing or malformed secondary index", chunk);
+    const size_t n = sl / PRAOS_CHUNK_ENTRY_SIZE;
+    uint64_t* off = calloc(n + 1, 8);
+    uint32_t* len = calloc(n + 1, 4);
+    uint8_t* is_ebb = calloc(n + 1, 1);
+    for (size_t i = 0; i < n; i++) {
+      const uint8_t* e = sec + PRAOS_CHUNK_ENTRY_SIZE * i;
+      const uint64_t bo = be(e, 8);
+      if (bo + 2 > dl) DIE("chunk %d entry %zu outside the chunk file", chunk, i);
+      off[i] = bo + be(e + 8, 2);
+      len[i] = (uint32_t)be(e + 10, 2);
+      is_ebb[i] = data[bo + 1] == 0;
+    }
+    praos_header_bytes hb = {n, data, dl, off, len};
+    praos_pbft_out o = {calloc(n + 1, 1), calloc(n + 1, 4), calloc(n + 1, 8), calloc(n + 1, 8), calloc(n + 1, 32),
+                        calloc(n + 1, 1), calloc(n + 1, 32), NULL};
+    uint8_t* verdict = calloc(n + 1, 1);
+    uint64_t* aux = calloc(n + 1, 8);
+    size_t stop = 0;
+    CK(ctx, praos_verify_pbft_headers(ctx, &hb, is_ebb, &P, delegs, nd, &o));
+    CK(ctx, praos_pbft_update_chain_dep_state(ctx, n, &o, is_ebb, &P, delegs, nd, &tip, &st, verdict, aux, &stop));
+    total += n;
+    valid += stop;
+    if (stop != n) {
+      stop_chunk = chunk;
+      stop_index = stop;
+      stop_verdict = verdict[stop];
+      stop_aux = aux[stop];
+      stop_bits = o.bits[stop];
+    }
+    free(o.bits); free(o.gk_idx); free(o.slot); free(o.block_no); free(o.prev_hash); free(o.prev_is_genesis);
+    free(o.header_hash); free(verdict); free(aux); free(off); free(len); free(is_ebb); free(data); free(sec);
+  }
+  size_t elen = 0;
+  (void)praos_pbft_state_encode(&st, NULL, 0, &elen);
+  uint8_t* enc = malloc(elen + 1);
+  if (praos_pbft_state_encode(&st, enc, elen, &elen) != PRAOS_OK) DIE("praos_pbft_state_encode");
+  printf("{\"phase\": \"pbft_headers\", \"headers\": %zu, \"valid\": %zu, \"stop_chunk\": %d, \"stop_index\": %llu, "
+         "\"stop_verdict\": %u, \"stop_aux\": %llu, \"stop_bits\": %u, \"tip_origin\": %u, \"tip_is_ebb\": %u, "
+         "\"tip_slot\": %llu, \"tip_block_no\": %llu, \"tip_hash\": \"",
+         total, valid, stop_chunk, stop_index, stop_verdict, stop_aux, stop_bits, tip.origin, tip.is_ebb,
+         (unsigned long long)tip.slot, (unsigned long long)tip.block_no);
+  hex_out(tip.hash, 32);
+  printf("\", \"signers\": %llu, \"state\": \"", (unsigned long long)st.n);
+  hex_out(enc, elen);
+  printf("\"}\n");
+  fflush(stdout);
+  praos_close(ctx);
+  free(enc); free(st.slot); free(st.genesis_hash); free(delegs);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (praos_abi_version() != PRAOS_ABI_VERSION) DIE("ABI version %d, header %d", praos_abi_version(), PRAOS_ABI_VERSION);
   if (argc == 6 && strcmp(argv[1], "--chunk") == 0)
@@ -1030,9 +1125,17 @@ int main(int argc, char** argv) {
     return validate_chunk_main(argv[2], atoi(argv[3]), strtoull(argv[4], NULL, 10), es,
                                (uint32_t)strtoul(argv[6], NULL, 10));
   }
+  if (argc == 8 && strcmp(argv[1], "--pbft-headers") == 0) {
+    const uint64_t es = strtoull(argv[5], NULL, 10);
+    if (es == 0) DIE("--pbft-headers: epoch slots must be positive");
+    return pbft_headers_main(argv[2], strtoull(argv[3], NULL, 10), strtoull(argv[4], NULL, 10), es,
+                             (uint32_t)strtoul(argv[6], NULL, 10), argv[7]);
+  }
   if (argc != 4) DIE("usage: %s <immutable dir> <epoch file> <threads> | --chunk <dir> <chunk> <spkp> <members>"
                      " | --validate-chunk <dir> <chunk> <spkp>"
-                     " | --validate-chunk-byron <dir> <chunk> <spkp> <byron epoch slots> <protocol magic>", argv[0]);
+                     " | --validate-chunk-byron <dir> <chunk> <spkp> <byron epoch slots> <protocol magic>"
+                     " | --pbft-headers <dir> <window> <threshold> <byron epoch slots> <protocol magic> <delegs file>",
+                     argv[0]);
   read_epoch_file(argv[2]);
   chain_t ch;
   read_chain(argv[1], &ch);

@@ -62,6 +62,11 @@ module Ouroboros.Consensus.Protocol.Praos.Batch
   , ChunkParse (..)
   , validateChunkBatch
   , praosVerifyBlockIntegrity
+    -- * Byron header validation (PBFT)
+  , PBftParamsC (..)
+  , PBftTipC
+  , PBftBatchResult (..)
+  , validatePBftHeaderBatch
     -- * Error reconstruction (typed constructors: module Batch.Errors)
   , verdictToError
   ) where
@@ -192,6 +197,22 @@ foreign import ccall safe "praos_validate_chunk" c_validate_chunk
 -- layout-byron praos_chunk_cfg (24 bytes): slots_per_kes_period@0 byron_epoch_slots@8 byron_protocol_magic@16 pad_@20
 foreign import ccall safe "praos_validate_chunk_cfg" c_validate_chunk_cfg
   :: Ptr PraosCtx -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> Ptr Word8 -> IO CInt
+-- additive as well (ABI version unchanged): Byron header validation.  The structs
+-- validatePBftHeaderBatch pokes and peeks (checked against the C compiler by tests/test_pbft_abi.py;
+-- "layout-pbft": the other layout lines belong to the tests named above):
+-- layout-pbft praos_pbft_params (32 bytes): window_size@0 threshold@8 epoch_slots@16 protocol_magic@24 pad_@28
+-- layout-pbft praos_pbft_out (64 bytes): bits@0 gk_idx@8 slot@16 block_no@24 prev_hash@32 prev_is_genesis@40 header_hash@48 delegate_hash@56
+-- layout-pbft praos_pbft_tip (56 bytes): origin@0 is_ebb@1 pad_@2 slot@8 block_no@16 hash@24
+-- layout-pbft praos_pbft_state (32 bytes): cap@0 n@8 slot@16 genesis_hash@24
+foreign import ccall safe "praos_verify_pbft_headers" c_verify_pbft_headers
+  :: Ptr PraosCtx -> Ptr () -> Ptr Word8 -> Ptr () -> Ptr Word8 -> Word32 -> Ptr () -> IO CInt
+foreign import ccall safe "praos_pbft_update_chain_dep_state" c_pbft_update_chain_dep_state
+  :: Ptr PraosCtx -> CSize -> Ptr () -> Ptr Word8 -> Ptr () -> Ptr Word8 -> Word32 -> Ptr () -> Ptr ()
+  -> Ptr Word8 -> Ptr Word64 -> Ptr CSize -> IO CInt
+foreign import ccall safe "praos_pbft_state_encode" c_pbft_state_encode
+  :: Ptr () -> Ptr Word8 -> CSize -> Ptr CSize -> IO CInt
+foreign import ccall safe "praos_pbft_state_decode" c_pbft_state_decode
+  :: Ptr Word8 -> CSize -> Ptr () -> IO CInt
 
 abiVersion :: CInt
 abiVersion = 15
@@ -1094,6 +1115,129 @@ validateChunkBatch ctx@(PraosBatchCtx p) spkp byron chunk entries = go (max 64 (
             , cpIsEBB = VS.take y bbv
             , cpByronEpochSlots = byronSlots }
 
+-- ---------------------------------------------------------------- Byron header validation (PBFT)
+
+-- | PBftWindowParams and the Byron block configuration the header check reads.  'pbThreshold' is
+-- @floor (pbftSignatureThreshold * k)@ (pbftWindowParams, Protocol/PBFT.hs): the Double stays on
+-- this side, the ABI takes the integer.
+data PBftParamsC = PBftParamsC
+  { pbWindowSize    :: !Word64   -- ^ k
+  , pbThreshold     :: !Word64
+  , pbEpochSlots    :: !Word64
+  , pbProtocolMagic :: !Word32
+  }
+
+-- | The old tip: 'Nothing' = Origin, else (slot, block number, header hash, is EBB).
+type PBftTipC = Maybe (Word64, Word64, BS.ByteString, Bool)
+
+data PBftBatchResult = PBftBatchResult
+  { pbrVerdicts  :: ![Word8]                 -- ^ PRAOS_V_* per header (Batch.Errors rebuilds the typed errors)
+  , pbrAux       :: ![Word64]                -- ^ expected block number / minimum slot / the count n
+  , pbrBits      :: ![Word8]                 -- ^ PRAOS_PBFT_BIT_*
+  , pbrGkIdx     :: ![Int32]                 -- ^ index of the signing delegate's pair in the map, -1 when absent
+  , pbrDelegate  :: ![BS.ByteString]         -- ^ hashVerKey of each header's delegate (28 bytes)
+  , pbrChainStop :: !Int                     -- ^ the first invalid header (= the batch length when none)
+  , pbrState     :: !BS.ByteString           -- ^ encodePBftState of the state at 'pbrChainStop'
+  , pbrTip       :: !PBftTipC                -- ^ the tip at 'pbrChainStop'
+  }
+
+-- | validateHeader over a batch of stored Byron headers under one delegation map: the envelope
+-- (HeaderValidation.hs:297-344, Byron/Ledger/HeaderValidation.hs:39-75), then PBFT
+-- updateChainDepState (Protocol/PBFT.hs:320-353).  @headers@: (offset, length) of each header in
+-- @arena@ (blockOffset + headerOffset, headerSize of the secondary index); @isEBB@: from the nested
+-- context.  @delegs@: (genesis key hash, delegate key hash) pairs, the Bimap of the PBftLedgerView;
+-- the caller splits a batch at a re-delegation.  @st@: encodePBftState bytes of the state before the
+-- batch.  The per-header half runs on the GPU (praos_verify_pbft_headers), the fold on the host
+-- (praos_pbft_update_chain_dep_state); the delegation certificate's own signature is the Byron
+-- ledger's check, not this one's.  Replayed from C by ffi_harness --pbft-headers.
+validatePBftHeaderBatch :: PraosBatchCtx -> PBftParamsC -> [(BS.ByteString, BS.ByteString)] -> BS.ByteString
+                        -> [(Word64, Word32)] -> [Bool] -> PBftTipC -> BS.ByteString -> IO PBftBatchResult
+validatePBftHeaderBatch (PraosBatchGroup _ _ _) _ _ _ _ _ _ _ =
+  throwIO (PraosBatchError (-2) "validatePBftHeaderBatch: one context, not a group")
+validatePBftHeaderBatch ctx@(PraosBatchCtx p) PBftParamsC{pbWindowSize, pbThreshold, pbEpochSlots, pbProtocolMagic}
+                        delegs arena headers isEBB tip st = do
+  let n = length headers
+      nd = length delegs
+      cap = fromIntegral (max 1 pbWindowSize) :: Int
+      offs = VS.fromList (map fst headers)
+      lens = VS.fromList (map snd headers)
+      ebbs = VS.fromList (map (\b -> if b then 1 else 0 :: Word8) isEBB)
+      dl = VS.fromList (concatMap (\(g, d) -> BS.unpack (pad28 g) ++ BS.unpack (pad28 d)) delegs)
+      pad28 b = BS.take 28 (b <> BS.replicate 28 0)
+  bits <- VSM.replicate (max 1 n) 0 :: IO (VSM.IOVector Word8)
+  gks <- VSM.replicate (max 1 n) (-1) :: IO (VSM.IOVector Int32)
+  slots <- VSM.new (max 1 n) :: IO (VSM.IOVector Word64)
+  bnos <- VSM.new (max 1 n) :: IO (VSM.IOVector Word64)
+  prevs <- VSM.new (32 * max 1 n) :: IO (VSM.IOVector Word8)
+  gens <- VSM.new (max 1 n) :: IO (VSM.IOVector Word8)
+  hhs <- VSM.new (32 * max 1 n) :: IO (VSM.IOVector Word8)
+  dhs <- VSM.replicate (28 * max 1 n) 0 :: IO (VSM.IOVector Word8)
+  verd <- VSM.replicate (max 1 n) 0 :: IO (VSM.IOVector Word8)
+  aux <- VSM.replicate (max 1 n) 0 :: IO (VSM.IOVector Word64)
+  sslot <- VSM.replicate cap 0 :: IO (VSM.IOVector Word64)
+  shash <- VSM.replicate (28 * cap) 0 :: IO (VSM.IOVector Word8)
+  (stop, enc, tip') <- BSU.unsafeUseAsCStringLen arena $ \(ap, alen) ->
+    VS.unsafeWith offs $ \offp -> VS.unsafeWith lens $ \lenp -> VS.unsafeWith ebbs $ \ebbp ->
+    VS.unsafeWith dl $ \dlp ->
+    VSM.unsafeWith bits $ \bitp -> VSM.unsafeWith gks $ \gkp -> VSM.unsafeWith slots $ \slp ->
+    VSM.unsafeWith bnos $ \bnp -> VSM.unsafeWith prevs $ \pvp -> VSM.unsafeWith gens $ \gnp ->
+    VSM.unsafeWith hhs $ \hhp -> VSM.unsafeWith dhs $ \dhp -> VSM.unsafeWith verd $ \vp ->
+    VSM.unsafeWith aux $ \axp -> VSM.unsafeWith sslot $ \ssp -> VSM.unsafeWith shash $ \shp ->
+    allocaBytes 40 $ \hb -> allocaBytes 32 $ \prm -> allocaBytes 64 $ \out -> allocaBytes 56 $ \tp ->
+    allocaBytes 32 $ \stp -> alloca $ \stopp -> alloca $ \lenq -> do
+      -- praos_header_bytes: n, bytes, bytes_len, off, len
+      pokeByteOff hb 0 (fromIntegral n :: CSize) >> pokeByteOff hb 8 ap
+      pokeByteOff hb 16 (fromIntegral alen :: CSize) >> pokeByteOff hb 24 offp >> pokeByteOff hb 32 lenp
+      pokeByteOff prm 0 pbWindowSize >> pokeByteOff prm 8 pbThreshold >> pokeByteOff prm 16 pbEpochSlots
+      pokeByteOff prm 24 pbProtocolMagic >> pokeByteOff prm 28 (0 :: Word32)
+      pokeByteOff out 0 bitp >> pokeByteOff out 8 gkp >> pokeByteOff out 16 slp >> pokeByteOff out 24 bnp
+      pokeByteOff out 32 pvp >> pokeByteOff out 40 gnp >> pokeByteOff out 48 hhp >> pokeByteOff out 56 dhp
+      -- the state before the batch
+      pokeByteOff stp 0 (fromIntegral cap :: Word64) >> pokeByteOff stp 8 (0 :: Word64)
+      pokeByteOff stp 16 ssp >> pokeByteOff stp 24 shp
+      BSU.unsafeUseAsCStringLen st $ \(sp, sl) ->
+        check ctx (c_pbft_state_decode (castPtr sp) (fromIntegral sl) (castPtr stp))
+      fillBytes tp 0 56
+      case tip of
+        Nothing -> pokeByteOff tp 0 (1 :: Word8)
+        Just (s, b, h, e) -> do
+          pokeByteOff tp 1 (if e then 1 else 0 :: Word8)
+          pokeByteOff tp 8 s >> pokeByteOff tp 16 b
+          BSU.unsafeUseAsCStringLen (BS.take 32 (h <> BS.replicate 32 0)) $ \(hp, _) ->
+            copyBytes (castPtr tp `plusPtr` 24) hp 32
+      let dlq = if nd == 0 then nullPtr else dlp
+      check ctx (c_verify_pbft_headers p (castPtr hb) ebbp (castPtr prm) dlq (fromIntegral nd) (castPtr out))
+      check ctx (c_pbft_update_chain_dep_state p (fromIntegral n) (castPtr out) ebbp (castPtr prm) dlq
+                   (fromIntegral nd) (castPtr tp) (castPtr stp) vp axp stopp)
+      stop <- fromIntegral <$> peek stopp
+      _ <- c_pbft_state_encode (castPtr stp) nullPtr 0 lenq
+      need <- fromIntegral <$> peek lenq :: IO Int
+      enc <- allocaBytes (max 1 need) $ \ep -> do
+        check ctx (c_pbft_state_encode (castPtr stp) ep (fromIntegral need) lenq)
+        BS.packCStringLen (castPtr ep, need)
+      origin <- peekByteOff tp 0 :: IO Word8
+      tip' <- if origin /= 0 then pure Nothing else do
+        e <- peekByteOff tp 1 :: IO Word8
+        s <- peekByteOff tp 8
+        b <- peekByteOff tp 16
+        h <- BS.packCStringLen (castPtr tp `plusPtr` 24, 32)
+        pure (Just (s, b, h, e /= 0))
+      pure (stop :: Int, enc, tip')
+  vv <- VS.unsafeFreeze verd
+  av <- VS.unsafeFreeze aux
+  bv <- VS.unsafeFreeze bits
+  gv <- VS.unsafeFreeze gks
+  dv <- VS.unsafeFreeze dhs
+  pure PBftBatchResult
+    { pbrVerdicts = VS.toList (VS.take n vv)
+    , pbrAux = VS.toList (VS.take n av)
+    , pbrBits = VS.toList (VS.take n bv)
+    , pbrGkIdx = VS.toList (VS.take n gv)
+    , pbrDelegate = [BS.pack (VS.toList (VS.slice (28 * i) 28 dv)) | i <- [0 .. n - 1]]
+    , pbrChainStop = stop
+    , pbrState = enc
+    , pbrTip = tip' }
+
 -- ---------------------------------------------------------------- errors
 
 -- | The reference error a verdict stands for, by name (logs, traces).  The typed
@@ -1124,4 +1268,9 @@ verdictToError v bits = case v of
   17 -> Just "HeaderSizeTooLarge"
   18 -> Just "BlockSizeTooLarge"
   19 -> Just "ChainTransitionError (TPraos PRTCL failures)"
+  20 -> Just "PBftInvalidSignature"
+  21 -> Just "PBftInvalidSlot"
+  22 -> Just "PBftNotGenesisDelegate"
+  23 -> Just "PBftExceededSignThreshold"
+  24 -> Just "UnexpectedEBBInSlot"
   _  -> Just ("unknown verdict " ++ show v)

@@ -2,6 +2,7 @@
 {-# LANGUAGE NamedFieldPuns      #-}
 {-# LANGUAGE ScopedTypeVariables #-}
 {-# LANGUAGE TypeApplications    #-}
+{-# LANGUAGE TypeFamilies        #-}
 
 -- | The reference's own error values, rebuilt from a batch verdict
 -- ('Ouroboros.Consensus.Protocol.Praos.Batch').
@@ -24,6 +25,8 @@ module Ouroboros.Consensus.Protocol.Praos.Batch.Errors
   , TPraosOverlaySlot (..)
   , tpraosChainTransitionError
   , verdictToChainPredicateFailure
+  , verdictToPBftValidationErr
+  , verdictToByronEnvelopeError
   ) where
 
 import           Cardano.Crypto.VRF (CertifiedVRF (certifiedOutput), getOutputVRFNatural, hashVerKeyVRF)
@@ -58,6 +61,10 @@ import           Ouroboros.Consensus.Protocol.Praos (PraosCrypto, PraosParams (.
 import qualified Ouroboros.Consensus.Protocol.Praos.Views as Views
 import           Ouroboros.Consensus.Protocol.Praos.VRF (vrfLeaderValue)
 import           Ouroboros.Consensus.Shelley.Protocol.Praos (PraosEnvelopeError (..))
+import           Ouroboros.Consensus.Byron.Ledger.HeaderValidation (ByronOtherHeaderEnvelopeError (..))
+import           Ouroboros.Consensus.Protocol.PBFT (PBftLedgerView, PBftValidationErr (..))
+import           Ouroboros.Consensus.Protocol.PBFT.Crypto (PBftCrypto (PBftVerKeyHash))
+import qualified Data.Text as Text
 
 -- | A protocol verdict (PRAOS_V_KES_BEFORE_START .. PRAOS_V_LEADER_TOO_BIG = 1..11) as
 -- the 'PraosValidationErr' the reference throws for that header.
@@ -281,4 +288,34 @@ verdictToChainPredicateFailure (m, maxpv) (hs, maxHS) (bs, maxBS) v = case v of
   16 -> Just (ObsoleteNodeCHAIN m maxpv)
   17 -> Just (HeaderSizeTooLargeCHAIN hs maxHS)
   18 -> Just (BlockSizeTooLargeCHAIN bs maxBS)
+  _  -> Nothing
+
+-- ---------------------------------------------------------------- Byron (PBFT)
+
+-- | The PBftValidationErr a verdict of validatePBftHeaderBatch stands for (Protocol/PBFT.hs:320-353),
+-- with the reference's payloads: @delegate@ = hashVerKey of the header's delegate key
+-- ('pbrDelegate'), @gk@ = the genesis key that delegated to it (the pair 'pbrGkIdx' points at;
+-- only read for PBftExceededSignThreshold), @aux@ = the count n.  The text of
+-- PBftInvalidSignature is the DSIGN error string of the reference's verifySignedDSIGN.
+verdictToPBftValidationErr
+  :: Word8 -> Word64 -> PBftVerKeyHash c -> PBftVerKeyHash c -> PBftLedgerView c -> Maybe (PBftValidationErr c)
+verdictToPBftValidationErr v aux delegate gk lv = case v of
+  20 -> Just (PBftInvalidSignature (Text.pack "Verification failed"))
+  21 -> Just PBftInvalidSlot
+  22 -> Just (PBftNotGenesisDelegate delegate lv)
+  23 -> Just (PBftExceededSignThreshold gk aux)
+  _  -> Nothing
+
+-- | The Byron HeaderEnvelopeError of verdicts 13-15 and 24 (HeaderValidation.hs:297-344,
+-- Byron/Ledger/HeaderValidation.hs:58-60): @aux@ is the expected block number / the minimum slot
+-- the fold reports, and for UnexpectedEBBInSlot the header's own slot.
+verdictToByronEnvelopeError
+  :: (OtherHeaderEnvelopeError blk ~ ByronOtherHeaderEnvelopeError)
+  => Word8 -> Word64 -> BlockNo -> SlotNo -> WithOrigin (HeaderHash blk) -> ChainHash blk
+  -> Maybe (HeaderEnvelopeError blk)
+verdictToByronEnvelopeError v aux actualBlockNo actualSlot oldTip prevHash = case v of
+  13 -> Just (UnexpectedBlockNo (fromIntegral aux) actualBlockNo)
+  14 -> Just (UnexpectedSlotNo (SlotNo aux) actualSlot)
+  15 -> Just (UnexpectedPrevHash oldTip prevHash)
+  24 -> Just (OtherHeaderEnvelopeError (UnexpectedEBBInSlot actualSlot))
   _  -> Nothing

@@ -217,5 +217,21 @@ void launch_byron_integrity(dim3 grid, dim3 block, hipStream_t stream, size_t n,
                             const uint64_t* blk_off, const uint32_t* blk_len, const uint8_t* kind,
                             const uint32_t* spans, uint32_t cfg_pm, const ge_niels* gbtab, ge_cached* tabs,
                             uint8_t* result, uint8_t* which);
+// k_pbft.hip: Byron header validation.  decode: one lane per stored header (columns, the verify
+// inputs keys / sig / hram, the delegate's key hash dhash [n][28] and its index in dtab -- n_delegs
+// x 8 words sorted by the 7 hash words, word 7 the caller's index -- and the list of lanes that
+// take the signature verify); sig: uncached verifies over list[0 .. *count); sig_ck: the key
+// cache's hits; keyhash: hashVerKey of n 64-byte keys into [n][28].  n sizes the grids.
+void launch_pbft_decode(hipStream_t stream, size_t n, const uint8_t* arena, uint64_t arena_len, const uint64_t* hoff,
+                        const uint32_t* hlen, const uint8_t* is_ebb, uint64_t epoch_slots, uint32_t pm,
+                        const uint32_t* dtab, uint32_t n_delegs, uint64_t* slot, uint64_t* block_no,
+                        uint8_t* prev_hash, uint8_t* prev_genesis, uint8_t* header_hash, uint8_t* bits, int32_t* gk_idx,
+                        uint8_t* dhash, uint8_t* keys, uint8_t* sig, uint8_t* hram, uint32_t* vlist, uint32_t* vcount);
+void launch_pbft_sig(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count, const ge_niels* gbtab,
+                     const uint8_t* keys, const uint8_t* sig, const uint8_t* hram, uint8_t* bits, ge_cached* tabs);
+void launch_pbft_sig_ck(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count,
+                        const int32_t* item_entry, const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* comb,
+                        const uint8_t* keys, const uint8_t* sig, const uint8_t* hram, uint8_t* bits);
+void launch_pbft_keyhash(hipStream_t stream, size_t n, const uint8_t* keys64, uint8_t* out28);
 // replay: nonce contribution of each header's certified VRF output (k_misc.hip)
 void launch_vrf_nonce(hipStream_t stream, size_t n, const uint8_t* vrf_out, int tpraos, uint8_t* nonce_out);

@@ -21,6 +21,7 @@ static constexpr uint32_t TP_SIGNED_STRIDE = 640;   // max canonical TPraos BHBo
 #include <sched.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <condition_variable>
 #include <cstdlib>
@@ -120,6 +121,15 @@ static constexpr size_t KEY_PRIO_BATCH = 400000;
 // (profiles/r04/y: 96k 4.06 -> 3.64 ms, 108k 4.25 -> 4.10, 112k 4.39 -> 4.15; equal at 120k,
 // slower at 128k)
 static constexpr size_t ILP4_BATCH = 120000;
+// Byron header batches (praos_verify_pbft_headers) below this many headers verify uncached: the
+// delegate keys' precompute chain (250 doublings, then the table pass) is pure latency there.
+// Measured on an MI355X (tools/pbft_bench.py: 7 delegates in turn, a freshly opened context per
+// variant and pass, medians of 9 runs, cached / uncached ms end to end): 16,384 2.07 / 1.83,
+// 32,768 2.38 / 2.16, 65,536 3.16 / 2.73, 98,304 4.17 / 3.95, 131,072 4.98 / 4.67, 163,840 6.03 /
+// 6.04, 216,000 7.51 / 7.94: the medians cross at about 163,840.  With 7 keys the cache's insert
+// and partition passes serialise on 7 hash slots (0.66 + 0.62 ms at 216,000, kernel trace), which
+// is what moves the crossing this far out.
+static constexpr size_t PBFT_CK_MIN = 163840;
 // below this many headers the KES leaf keys are not cached (every KES check uncached, from the
 // ILP-4 build, beside stage V): a 54k-header shard's stage V and uncached KES waves fit in one
 // round of wave slots (2 per SIMD), and the leaf-key chain -- lists, precompute, tables, k_kes_ck,
@@ -286,6 +296,9 @@ struct praos_ctx {
   int concurrent = 1;                                  // PRAOS_OPT_CONCURRENT
   int kernels = 7;                                     // PRAOS_OPT_KERNELS
   int keycache = 2;                                    // PRAOS_OPT_KEYCACHE (min uses; 0 = off)
+  size_t pbft_ck_min = PBFT_CK_MIN;                    // PRAOS_PBFT_CK_MIN (see PBFT_CK_MIN)
+  uint32_t pbft_stats[4] = {0, 0, 0, 0};               // praos_pbft_stats of the last praos_verify_pbft_headers
+  uint32_t pbft_raw[5] = {0, 0, 0, 0, 0};              // its download: the cache's counters, the verify count
   size_t kes_nocache = KES_NOCACHE_BATCH;              // PRAOS_KES_NOCACHE (see KES_NOCACHE_BATCH)
   int kc_min[3] = {0, 0, 0};                           // per cache (cold, VRF, KES leaf) min uses overriding
                                                        // keycache when > 0 (PRAOS_KC_MIN="c,v,k")
@@ -691,6 +704,7 @@ static bool open_streams(praos_ctx* c) {
   if (const char* e = std::getenv("PRAOS_V_MAIN")) c->v_main = std::atoi(e);
   if (const char* e = std::getenv("PRAOS_STREAM_CHUNK_V")) c->stream_chunk_v = std::atoi(e);
   if (const char* e = std::getenv("PRAOS_KES_NOCACHE")) c->kes_nocache = (size_t)std::atoll(e);
+  if (const char* e = std::getenv("PRAOS_PBFT_CK_MIN")) c->pbft_ck_min = (size_t)std::atoll(e);
   if (const char* e = std::getenv("PRAOS_MISS_PRIO")) c->miss_prio = std::atoi(e);
   if (const char* e = std::getenv("PRAOS_KES_PAIR")) c->kes_pair = std::atol(e);
   if (const char* e = std::getenv("PRAOS_KC_MIN")) (void)std::sscanf(e, "%d,%d,%d", &c->kc_min[0], &c->kc_min[1], &c->kc_min[2]);
@@ -2113,6 +2127,207 @@ int praos_verify_byron_integrity(praos_ctx* c, const praos_header_bytes* blocks,
   (void)hipStreamSynchronize(c->stream);
   praos_batch_free(c, b);
   return r;
+}
+
+// ---- Byron header validation, the device half (k_pbft.hip; the fold is praos_pbft.hip)
+}  // extern "C"
+void praos_pbft_key_hash_host_(const uint8_t* keys64, size_t n, uint8_t* out28);   // praos_pbft.hip
+bool praos_pbft_delegs_ok_(const uint8_t* delegs, uint32_t n);
+extern "C" {
+
+int praos_byron_key_hash(praos_ctx* c, const uint8_t* keys64, size_t n, uint8_t* out28) {
+  if (!c || (n && (!keys64 || !out28))) return PRAOS_E_ARG;
+  if (n == 0) return PRAOS_OK;
+  if (c->device < 0) {
+    praos_pbft_key_hash_host_(keys64, n, out28);
+    return PRAOS_OK;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  praos_batch* b = new praos_batch();
+  b->owner = c;
+  b->n = n;
+  auto run = [&]() -> int {
+    uint8_t *dk = nullptr, *dh = nullptr;
+    if (dalloc(b, &dk, 64 * n) != hipSuccess || dalloc(b, &dh, 28 * n) != hipSuccess) {
+      c->err = "device allocation failed";
+      return PRAOS_E_OOM;
+    }
+    HIPCHK(c, h2d(c, dk, keys64, 64 * n));
+    launch_pbft_keyhash(c->stream, n, dk, dh);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out28, dh, 28 * n, hipMemcpyDeviceToHost));
+    return PRAOS_OK;
+  };
+  const int r = run();
+  (void)hipStreamSynchronize(c->stream);
+  praos_batch_free(c, b);
+  return r;
+}
+
+int praos_verify_pbft_headers(praos_ctx* c, const praos_header_bytes* in, const uint8_t* is_ebb,
+                              const praos_pbft_params* p, const uint8_t* delegs, uint32_t n_delegs,
+                              praos_pbft_out* out) {
+  if (!c || !in || !p || !out || p->epoch_slots == 0 || (n_delegs && !delegs) || in->n > 0x7fffffffu ||
+      (!in->bytes && in->bytes_len))
+    return PRAOS_E_ARG;
+  const size_t n = in->n;
+  if (n && (!in->off || !in->len || !is_ebb || !out->bits || !out->gk_idx || !out->slot || !out->block_no ||
+            !out->prev_hash || !out->prev_is_genesis || !out->header_hash))
+    return PRAOS_E_ARG;
+  for (size_t i = 0; i < n; i++)   // nothing is launched on a bad span
+    if (in->off[i] > in->bytes_len || in->len[i] > in->bytes_len - in->off[i]) {
+      c->err = "praos_verify_pbft_headers: span " + std::to_string(i) + " outside the arena";
+      return PRAOS_E_ARG;
+    }
+  if (!praos_pbft_delegs_ok_(delegs, n_delegs)) {
+    c->err = "pbft: duplicate hash in the delegation map";
+    return PRAOS_E_ARG;
+  }
+  if (c->device < 0) { c->err = "host-only context: no HIP device"; return PRAOS_E_STATE; }
+  if (n == 0) return PRAOS_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  // the delegation table on the device: sorted by the delegate hash's 7 little-endian words
+  // (word 0 first, k_pbft.hip hash_cmp), word 7 = the caller's index
+  std::vector<std::array<uint32_t, 8>> tab(n_delegs);
+  for (uint32_t k = 0; k < n_delegs; k++) {
+    std::memcpy(tab[k].data(), delegs + 56 * (size_t)k + 28, 28);
+    tab[k][7] = k;
+  }
+  std::sort(tab.begin(), tab.end(), [](const std::array<uint32_t, 8>& x, const std::array<uint32_t, 8>& y) {
+    return std::lexicographical_compare(x.begin(), x.begin() + 7, y.begin(), y.begin() + 7);
+  });
+  // the arena behind 8 zero bytes: the header hash reads the two bytes before a header (its
+  // 82 0k prefix replaces them), and a header may start at offset 0 of the caller's arena
+  constexpr size_t FRONT = 8;
+  std::vector<uint64_t> off(n);
+  for (size_t i = 0; i < n; i++) off[i] = in->off[i] + FRONT;
+  const size_t alen = FRONT + in->bytes_len;
+  praos_batch* b = new praos_batch();
+  b->owner = c;
+  b->n = n;
+  const bool cached = c->keycache > 0 && n >= c->pbft_ck_min;
+  auto run = [&]() -> int {
+    uint8_t *d_ebb = nullptr, *d_bits = nullptr, *d_dhash = nullptr, *d_keys = nullptr, *d_sig = nullptr,
+            *d_hram = nullptr;
+    uint32_t *d_tab = nullptr, *d_vlist = nullptr, *d_vcount = nullptr;
+    int32_t* d_gk = nullptr;
+    bool ok = dalloc(b, &b->arena, ((alen + 7) & ~(size_t)7) + 16) == hipSuccess;
+    ok &= dalloc(b, &b->hoff, 8 * n) == hipSuccess;
+    ok &= dalloc(b, &b->hlen, 4 * n) == hipSuccess;
+    ok &= dalloc(b, &d_ebb, n) == hipSuccess;
+    ok &= dalloc(b, &d_tab, 32 * (size_t)n_delegs) == hipSuccess;
+    ok &= dalloc(b, &b->slot, 8 * n) == hipSuccess;
+    ok &= dalloc(b, &b->block_no, 8 * n) == hipSuccess;
+    ok &= dalloc(b, &b->prev_hash, 32 * n) == hipSuccess;
+    ok &= dalloc(b, &b->prev_genesis, n) == hipSuccess;
+    ok &= dalloc(b, &b->header_hash, 32 * n) == hipSuccess;
+    ok &= dalloc(b, &d_bits, n) == hipSuccess;
+    ok &= dalloc(b, &d_gk, 4 * n) == hipSuccess;
+    ok &= dalloc(b, &d_dhash, 28 * n) == hipSuccess;
+    ok &= dalloc(b, &d_keys, 32 * n) == hipSuccess;
+    ok &= dalloc(b, &d_sig, 64 * n) == hipSuccess;
+    ok &= dalloc(b, &d_hram, 64 * n) == hipSuccess;
+    ok &= dalloc(b, &d_vlist, 4 * n) == hipSuccess;
+    ok &= dalloc(b, &d_vcount, 16) == hipSuccess;
+    ok &= dalloc(b, (uint8_t**)&b->tab_ocert, LT_ED_B * n) == hipSuccess;
+    praos_batch::KeyCache& k = b->kc[0];
+    if (cached) {
+      // the delegate keys of a batch are few (7 on mainnet): a small entry space, the keys
+      // past it verify uncached
+      k.cap = 256;
+      while (k.cap < 2 * n) k.cap <<= 1;
+      k.max_entries = (uint32_t)std::min<size_t>(n / 2 + 1, 1024);
+      ok &= dalloc(b, &k.slot_rep, 4 * (size_t)k.cap) == hipSuccess;
+      ok &= dalloc(b, &k.slot_cnt, 4 * (size_t)k.cap) == hipSuccess;
+      ok &= dalloc(b, &k.slot_entry, 4 * (size_t)k.cap) == hipSuccess;
+      ok &= dalloc(b, &k.item_slot, 4 * n) == hipSuccess;
+      ok &= dalloc(b, &k.item_entry, 4 * n) == hipSuccess;
+      ok &= dalloc(b, &k.hit, 4 * n) == hipSuccess;
+      ok &= dalloc(b, &k.miss, 4 * n) == hipSuccess;
+      ok &= dalloc(b, &k.counters, 16) == hipSuccess;
+      ok &= dalloc(b, &k.entry_rep, 4 * (size_t)k.max_entries) == hipSuccess;
+      ok &= dalloc(b, &k.entry_pos, 4 * (size_t)k.max_entries) == hipSuccess;
+      ok &= dalloc(b, &k.kinfo, 36 * (size_t)k.max_entries) == hipSuccess;
+      ok &= dalloc(b, (uint8_t**)&k.ktab, KT_BYTES * k.max_entries) == hipSuccess;
+    }
+    if (!ok) { c->err = "device allocation failed"; return PRAOS_E_OOM; }
+    if (cached) {
+      const int r = ensure_bcomb16(c);
+      if (r != PRAOS_OK) return r;
+    }
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemsetAsync(b->arena, 0, FRONT, st));
+    HIPCHK(c, hipMemsetAsync(b->arena + alen, 0, ((alen + 7) & ~(size_t)7) + 16 - alen, st));
+    if (in->bytes_len) HIPCHK(c, h2d(c, b->arena + FRONT, in->bytes, in->bytes_len));
+    HIPCHK(c, hipMemcpyAsync(b->hoff, off.data(), 8 * n, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(b->hlen, in->len, 4 * n, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_ebb, is_ebb, n, hipMemcpyHostToDevice, st));
+    if (n_delegs) HIPCHK(c, hipMemcpyAsync(d_tab, tab.data(), 32 * (size_t)n_delegs, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(d_vcount, 0, 16, st));
+    (void)hipGetLastError();
+    launch_pbft_decode(st, n, b->arena, alen, b->hoff, b->hlen, d_ebb, p->epoch_slots, p->protocol_magic, d_tab,
+                       n_delegs, b->slot, b->block_no, b->prev_hash, b->prev_genesis, b->header_hash, d_bits, d_gk,
+                       d_dhash, d_keys, d_sig, d_hram, d_vlist, d_vcount);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev[0], st));             // the decode's columns are final here
+    // (an ILP-4 build of this kernel, as the OCert misses have below ILP4_BATCH, measured level
+    // with it -- 21,600 headers 2.152 ms against the ILP-4 build's 2.175, 65,536 2.878 against
+    // 2.960 -- and was not kept)
+    auto sig_nc = [&](const uint32_t* list, const uint32_t* count) {   // uncached verifies over a list
+      launch_pbft_sig(st, n, list, count, c->btab, d_keys, d_sig, d_hram, d_bits, b->tab_ocert);
+    };
+    if (cached) {
+      const bool pk = c->pk_on;
+      c->pk_on = false;                                  // the batch's own entries, not the pool-key store
+      const int r = kc_lists(c, k, n, d_keys, st, d_vlist, d_vcount, 0);
+      if (r == PRAOS_OK) kc_precompute(c, k, d_keys, 0, st, n);
+      c->pk_on = pk;
+      if (r != PRAOS_OK) return r;
+      launch_pbft_sig_ck(st, n, k.hit, k.counters + 1, k.item_entry, k.kt, k.ki, c->bcomb16, d_keys, d_sig, d_hram,
+                         d_bits);
+      sig_nc(k.miss, k.counters + 2);
+    } else {
+      sig_nc(d_vlist, d_vcount);
+    }
+    HIPCHK(c, hipGetLastError());
+    // every column but the bits comes back on the download stream while the verifies run
+    hipStream_t ds = c->dstream;
+    HIPCHK(c, hipStreamWaitEvent(ds, c->ev[0], 0));
+    // (large columns through the pinned staging buffers; the small ones queued, one wait for all)
+    auto col = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+      if (bytes >= (4u << 20)) return d2h_on(c, dst, src, bytes, ds);
+      return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ds);
+    };
+    HIPCHK(c, col(out->prev_hash, b->prev_hash, 32 * n));
+    HIPCHK(c, col(out->header_hash, b->header_hash, 32 * n));
+    if (out->delegate_hash) HIPCHK(c, col(out->delegate_hash, d_dhash, 28 * n));
+    HIPCHK(c, col(out->slot, b->slot, 8 * n));
+    HIPCHK(c, col(out->block_no, b->block_no, 8 * n));
+    HIPCHK(c, col(out->gk_idx, d_gk, 4 * n));
+    HIPCHK(c, col(out->prev_is_genesis, b->prev_genesis, n));
+    std::memset(c->pbft_raw, 0, sizeof c->pbft_raw);
+    if (cached) HIPCHK(c, hipMemcpyAsync(c->pbft_raw, k.counters, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->pbft_raw + 4, d_vcount, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(ds));
+    HIPCHK(c, hipStreamSynchronize(st));
+    c->pbft_stats[0] = cached ? 1 : 0;
+    c->pbft_stats[1] = cached ? std::min(c->pbft_raw[0], k.max_entries) : 0;
+    c->pbft_stats[2] = cached ? c->pbft_raw[1] : 0;
+    c->pbft_stats[3] = cached ? c->pbft_raw[2] : c->pbft_raw[4];
+    HIPCHK(c, hipMemcpy(out->bits, d_bits, n, hipMemcpyDeviceToHost));
+    return PRAOS_OK;
+  };
+  const int r = run();
+  (void)hipStreamSynchronize(c->stream);
+  praos_batch_free(c, b);
+  return r;
+}
+
+int praos_pbft_stats(praos_ctx* c, uint32_t out[4]) {
+  if (!c || !out) return PRAOS_E_ARG;
+  std::memcpy(out, c->pbft_stats, sizeof c->pbft_stats);
+  return PRAOS_OK;
 }
 
 // es: byron_epoch_slots (0: Byron off, pass A exactly as before)

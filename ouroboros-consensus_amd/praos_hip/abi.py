@@ -204,6 +204,36 @@ class ChunkCfg(ctypes.Structure):
 BLK_PBFT_SIG, BLK_PM = 0x08, 0x10
 BYRON_W_DLG, BYRON_W_UPD, BYRON_W_NTX, BYRON_W_WIT, BYRON_W_ROOT = 0x01, 0x02, 0x04, 0x08, 0x10
 
+# Byron header validation: PBFT (praos_verify_pbft_headers / praos_pbft_update_chain_dep_state)
+PBFT_BIT_DECODE, PBFT_BIT_SIG, PBFT_BIT_NOT_DELEGATE = 0x01, 0x02, 0x04
+V_OK, V_INPUT, V_ENV_BLOCK_NO, V_ENV_SLOT_NO, V_ENV_PREV_HASH = 0, 12, 13, 14, 15
+V_PBFT_INVALID_SIG, V_PBFT_INVALID_SLOT, V_PBFT_NOT_DELEGATE, V_PBFT_EXCEEDED, V_ENV_EBB_IN_SLOT = 20, 21, 22, 23, 24
+
+
+class PbftParams(ctypes.Structure):
+    _fields_ = [("window_size", ctypes.c_uint64), ("threshold", ctypes.c_uint64), ("epoch_slots", ctypes.c_uint64),
+                ("protocol_magic", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
+
+
+class PbftOut(ctypes.Structure):
+    _fields_ = [("bits", u8p), ("gk_idx", i32p), ("slot", u64p), ("block_no", u64p), ("prev_hash", u8p),
+                ("prev_is_genesis", u8p), ("header_hash", u8p), ("delegate_hash", u8p)]
+
+
+class PbftTip(ctypes.Structure):
+    _fields_ = [("origin", ctypes.c_uint8), ("is_ebb", ctypes.c_uint8), ("pad_", ctypes.c_uint8 * 6),
+                ("slot", ctypes.c_uint64), ("block_no", ctypes.c_uint64), ("hash", ctypes.c_uint8 * 32)]
+
+
+class PbftStateC(ctypes.Structure):
+    _fields_ = [("cap", ctypes.c_uint64), ("n", ctypes.c_uint64), ("slot", u64p), ("genesis_hash", u8p)]
+
+
+PBFT_OUT_FIELDS = (("bits", np.uint8, ()), ("gk_idx", np.int32, ()), ("slot", np.uint64, ()),
+                   ("block_no", np.uint64, ()), ("prev_hash", np.uint8, (32,)), ("prev_is_genesis", np.uint8, ()),
+                   ("header_hash", np.uint8, (32,)), ("delegate_hash", np.uint8, (28,)))
+
+
 # decode status (PRAOS_DEC_*)
 DEC_RANGE, DEC_SYNTAX, DEC_SIZE, DEC_UNSUPPORTED, DEC_TRAILING, DEC_NONCANONICAL, DEC_OVERFLOW = \
     0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
@@ -362,6 +392,18 @@ SIGNATURES = {
                                                 ctypes.POINTER(ChunkResult), ctypes.POINTER(ChunkOut), u8p]),
     "praos_verify_byron_integrity": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HeaderBytes), ctypes.c_uint64,
                                                     ctypes.c_uint32, u8p, u8p]),
+    "praos_byron_key_hash": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_size_t, u8p]),
+    "praos_verify_pbft_headers": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HeaderBytes), u8p,
+                                                 ctypes.POINTER(PbftParams), u8p, ctypes.c_uint32,
+                                                 ctypes.POINTER(PbftOut)]),
+    "praos_pbft_stats": (ctypes.c_int, [ctypes.c_void_p, u32p]),
+    "praos_pbft_update_chain_dep_state": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(PbftOut),
+                                                         u8p, ctypes.POINTER(PbftParams), u8p, ctypes.c_uint32,
+                                                         ctypes.POINTER(PbftTip), ctypes.POINTER(PbftStateC), u8p,
+                                                         u64p, ctypes.POINTER(ctypes.c_size_t)]),
+    "praos_pbft_state_encode": (ctypes.c_int, [ctypes.POINTER(PbftStateC), u8p, ctypes.c_size_t,
+                                               ctypes.POINTER(ctypes.c_size_t)]),
+    "praos_pbft_state_decode": (ctypes.c_int, [u8p, ctypes.c_size_t, ctypes.POINTER(PbftStateC)]),
     "praos_block_batch_upload": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.POINTER(HeaderBytes)]),
     "praos_block_batch_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "praos_block_batch_download": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u8p, u8p]),
@@ -751,6 +793,132 @@ class Context:
         self.check(self.L.praos_verify_byron_integrity(self.h, ctypes.byref(hb), epoch_slots, protocol_magic,
                                                        ptr(res), ptr(which)))
         return res, which
+
+    # ---- Byron header validation: PBFT (k_pbft.hip, praos_pbft.hip) ----
+    def byron_key_hash(self, keys64):
+        """hashVerKey of Byron extended public keys: Blake2b-224(SHA3-256(58 40 || xpub64)); keys64
+        u8[n, 64] (or bytes) -> u8[n, 28].  Host-only contexts compute it on the host."""
+        k = np.ascontiguousarray(np.frombuffer(keys64, np.uint8) if isinstance(keys64, (bytes, bytearray))
+                                 else keys64, dtype=np.uint8).reshape(-1, 64)
+        out = np.zeros((len(k), 28), np.uint8)
+        self.check(self.L.praos_byron_key_hash(self.h, ptr(k), len(k), ptr(out)))
+        return out
+
+    @staticmethod
+    def pbft_params(window_size, threshold, epoch_slots, protocol_magic):
+        return PbftParams(int(window_size), int(threshold), int(epoch_slots), int(protocol_magic), 0)
+
+    @staticmethod
+    def _pbft_delegs(delegs):
+        """delegs: list of (genesis key hash 28, delegate key hash 28) -> u8[n, 56]"""
+        d = np.zeros((len(delegs), 56), np.uint8)
+        for k, (g, h) in enumerate(delegs):
+            d[k, :28] = np.frombuffer(bytes(g), np.uint8)
+            d[k, 28:] = np.frombuffer(bytes(h), np.uint8)
+        return d
+
+    @staticmethod
+    def _pbft_out(H):
+        o = PbftOut()
+        for name, dt, _ in PBFT_OUT_FIELDS:
+            setattr(o, name, ptr(H[name], i32p if dt is np.int32 else _CT[dt]) if name in H else None)
+        return o
+
+    def verify_pbft_headers(self, arena, off, length, is_ebb, params, delegs, delegate_hash=False):
+        """The per-header half of Byron header validation (praos_verify_pbft_headers): returns a
+        dict of the columns bits, gk_idx, slot, block_no, prev_hash, prev_is_genesis, header_hash
+        and, with delegate_hash=True, delegate_hash (hashVerKey of each header's delegate: the
+        payload of PBftNotGenesisDelegate; the fold reads gk_idx, not this column)."""
+        arena, off, length = self._chunk(arena, off, length)
+        n = len(off)
+        ebb = np.ascontiguousarray(is_ebb, dtype=np.uint8)
+        assert len(ebb) == n
+        H = {name: np.zeros((n,) + shp, dt) for name, dt, shp in PBFT_OUT_FIELDS
+             if delegate_hash or name != "delegate_hash"}
+        hb = self.header_bytes_struct(arena, off, length)
+        d = self._pbft_delegs(delegs)
+        o = self._pbft_out(H)
+        self.check(self.L.praos_verify_pbft_headers(self.h, ctypes.byref(hb), ptr(ebb), ctypes.byref(params), ptr(d),
+                                                    len(d), ctypes.byref(o)))
+        return H
+
+    def pbft_stats(self):
+        """Which kernels the last verify_pbft_headers ran (praos_pbft_stats): dict of cache (bool),
+        keys_cached, cached_verifies, uncached_verifies."""
+        o = np.zeros(4, np.uint32)
+        self.check(self.L.praos_pbft_stats(self.h, ptr(o, u32p)))
+        return {"cache": bool(o[0]), "keys_cached": int(o[1]), "cached_verifies": int(o[2]),
+                "uncached_verifies": int(o[3])}
+
+    def pbft_update_chain_dep_state(self, H, is_ebb, params, delegs, tip=None, state=()):
+        """The sequential half (praos_pbft_update_chain_dep_state) over verify_pbft_headers' columns.
+        tip: None (Origin) or (slot, block_no, hash32, is_ebb); state: the window's signers, oldest
+        first, as (slot, genesis key hash 28).  Returns (verdict u8[n], aux u64[n], chain_stop,
+        tip, state) with tip and state those at chain_stop."""
+        n = len(H["bits"])
+        ebb = np.ascontiguousarray(is_ebb, dtype=np.uint8)
+        d = self._pbft_delegs(delegs)
+        o = self._pbft_out(H)
+        t = PbftTip()
+        t.origin = 1
+        if tip is not None:
+            t.origin, t.slot, t.block_no, t.is_ebb = 0, int(tip[0]), int(tip[1]), int(bool(tip[3]))
+            ctypes.memmove(t.hash, bytes(tip[2]), 32)
+        state = list(state)
+        cap = max(int(params.window_size), len(state), 1)
+        ss = np.zeros(cap, np.uint64)
+        sh = np.zeros((cap, 28), np.uint8)
+        for k, (s, g) in enumerate(state):
+            ss[k] = s
+            sh[k] = np.frombuffer(bytes(g), np.uint8)
+        st = PbftStateC(cap, len(state), ptr(ss, u64p), ptr(sh))
+        verdict = np.zeros(n, np.uint8)
+        aux = np.zeros(n, np.uint64)
+        stop = ctypes.c_size_t(0)
+        self.check(self.L.praos_pbft_update_chain_dep_state(self.h, n, ctypes.byref(o), ptr(ebb), ctypes.byref(params),
+                                                            ptr(d), len(d), ctypes.byref(t), ctypes.byref(st),
+                                                            ptr(verdict), ptr(aux, u64p), ctypes.byref(stop)))
+        new_tip = None if t.origin else (int(t.slot), int(t.block_no), bytes(t.hash), int(t.is_ebb))
+        new_state = [(int(ss[k]), bytes(sh[k])) for k in range(int(st.n))]
+        return verdict, aux, int(stop.value), new_tip, new_state
+
+    def validate_pbft_headers(self, arena, off, length, is_ebb, params, delegs, tip=None, state=()):
+        """Verify, then fold, carrying the state: (columns, verdict, aux, chain_stop, tip, state)."""
+        H = self.verify_pbft_headers(arena, off, length, is_ebb, params, delegs)
+        v, aux, stop, tip, state = self.pbft_update_chain_dep_state(H, is_ebb, params, delegs, tip, state)
+        return H, v, aux, stop, tip, state
+
+    @staticmethod
+    def pbft_state_encode(state):
+        """encodePBftState of [(slot, genesis key hash 28)] (oldest first) -> bytes"""
+        L = load()
+        state = list(state)
+        cap = max(len(state), 1)
+        ss = np.zeros(cap, np.uint64)
+        sh = np.zeros((cap, 28), np.uint8)
+        for k, (s, g) in enumerate(state):
+            ss[k] = s
+            sh[k] = np.frombuffer(bytes(g), np.uint8)
+        st = PbftStateC(cap, len(state), ptr(ss, u64p), ptr(sh))
+        ln = ctypes.c_size_t(0)
+        L.praos_pbft_state_encode(ctypes.byref(st), None, 0, ctypes.byref(ln))
+        out = np.zeros(max(ln.value, 1), np.uint8)
+        if L.praos_pbft_state_encode(ctypes.byref(st), ptr(out), len(out), ctypes.byref(ln)) != 0:
+            raise PraosError("praos_pbft_state_encode failed")
+        return bytes(out[:ln.value])
+
+    @staticmethod
+    def pbft_state_decode(data):
+        """decodePBftState -> [(slot, genesis key hash 28)], oldest first"""
+        L = load()
+        buf = np.frombuffer(bytes(data), np.uint8).copy()
+        cap = max(len(buf), 1)                     # every signer takes at least one byte
+        ss = np.zeros(cap, np.uint64)
+        sh = np.zeros((cap, 28), np.uint8)
+        st = PbftStateC(cap, 0, ptr(ss, u64p), ptr(sh))
+        if L.praos_pbft_state_decode(ptr(buf) if len(buf) else None, len(buf), ctypes.byref(st)) != 0:
+            raise PraosError("praos_pbft_state_decode: not a PBftState")
+        return [(int(ss[k]), bytes(sh[k])) for k in range(int(st.n))]
 
     def validate_chunk(self, chunk, expected_crc=None, block_off=None, slots_per_kes_period=129600, cap=None,
                        byron=None):

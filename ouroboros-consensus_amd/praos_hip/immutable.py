@@ -225,3 +225,37 @@ def validate_immutable(ctx, path, slots_per_kes_period, parse=None, byron=None):
         if row["outcome"] != 0 or not row["fits"]:
             break
     return rows
+
+
+def validate_byron_headers(ctx, path, params, delegs, state=None, tip=None):
+    """Byron header validation (validateHeader: the envelope, then PBFT updateChainDepState) over
+    a database directory, one verify + fold per chunk (Context.validate_pbft_headers), state and tip
+    carried across chunks.  Header spans come from the secondary index (blockOffset + headerOffset,
+    headerSize); the EBB flag from the stored block's two prefix bytes (82 00 an EBB, 82 01 a main
+    block: the nested context of Byron/Ledger/Serialisation.hs).  params: Context.pbft_params;
+    delegs: [(genesis key hash, delegate key hash)], one delegation map per call (the caller splits
+    at a re-delegation).  Stops at the first invalid header.  Returns a dict: headers (validated),
+    stop (None, or (chunk, index in the chunk, verdict, aux) of the first invalid header), tip and
+    state (those before it), rows (per chunk: chunk, headers, chain_stop)."""
+    chunks = sorted(int(f[:5]) for f in os.listdir(path) if f.endswith(".chunk"))
+    state = list(state or ())
+    out = {"headers": 0, "stop": None, "rows": []}
+    for c in chunks:
+        data = np.fromfile(os.path.join(path, f"{c:05d}.chunk"), np.uint8)
+        ents = read_secondary(path, c)
+        if not ents:
+            continue
+        off = np.array([e["block_offset"] + e["header_offset"] for e in ents], np.uint64)
+        ln = np.array([e["header_size"] for e in ents], np.uint32)
+        boff = np.array([e["block_offset"] for e in ents], np.int64)
+        if (boff + 2 > len(data)).any():
+            raise ValueError(f"chunk {c}: a block offset of the secondary index is outside the chunk file")
+        is_ebb = (data[boff + 1] == 0).astype(np.uint8)
+        _, v, aux, stop, tip, state = ctx.validate_pbft_headers(data, off, ln, is_ebb, params, delegs, tip, state)
+        out["rows"].append({"chunk": c, "headers": len(ents), "chain_stop": stop})
+        out["headers"] += stop
+        if stop != len(ents):
+            out["stop"] = (c, stop, int(v[stop]), int(aux[stop]))
+            break
+    out["tip"], out["state"] = tip, state
+    return out
