@@ -1074,6 +1074,49 @@ int praos_debug_leader512(praos_ctx* ctx, size_t n, const uint8_t* leader64, con
 /* Elligator2 hash-to-curve of the VRF suite: h(pk, alpha); out n*32 */
 int praos_debug_hash_to_curve(praos_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* alpha, uint8_t* out);
 
+/* ---- additions (ABI stays 15): self tests of the field products, the group formulas and the
+ * scalar-multiplication schedules.  Field elements are 32 bytes LE, any value below 2^256. ----
+ *
+ * praos_debug_fe, further ops: 9 neg, 10 chi (Legendre symbol z^((p-1)/2)), 11 predicates
+ * (byte 0 = fe_iszero | fe_isnegative << 1, other bytes 0), 12 mul with r the object a,
+ * 13 mul with r the object b, 14 sq with r the object a.
+ *
+ * praos_debug_fe_multi: the interleaved products.  in n*8*32: a1 b1 a2 b2 a3 b3 a4 b4; out n*4*32:
+ * r1 .. r4 (outputs an op does not have are 0).  op: 0 fe_mul2, 1 fe_sq2, 2 fe_mul3, 3 fe_mul4,
+ * 4 fe_sq4 (squarings read a only); op | 8: the aliased form, in which output m is the very object
+ * that product (m + 1) mod M reads as its b (multiplies) or its a (squarings). */
+int praos_debug_fe_multi(praos_ctx* ctx, int op, size_t n, const uint8_t* in, uint8_t* out);
+/* One group formula per item on raw coordinates.  build: 0 the default formulas (fe_mul2 / fe_sq2),
+ * 1 the ILP-4 module's (fe_mul3 / fe_mul4 / fe_sq4).  p, q, out: n*128 bytes, four field elements:
+ * p3 and p1p1 X,Y,Z,T; p2 X,Y,Z,(ignored / 0); cached YpX,YmX,Z,T2d; niels ypx,ymx,xy2d,(ignored / 0).
+ *   op 0 ge_p2_dbl          p p2                -> p1p1
+ *   op 1 ge_add             p p3, q cached      -> p1p1
+ *   op 2 ge_madd            p p3, q niels       -> p1p1
+ *   op 3 ge_p1p1_to_p2      p p1p1              -> p2
+ *   op 4 ge_p1p1_to_p3      p p1p1              -> p3
+ *   op 5 ge_p3_to_cached    p p3                -> cached
+ *   op 6 ge_p3_dbl_to_p3    p p3                -> p3
+ *   op 7 build_cached_table(p) then select_cached with the digit d in [-8, 7]   -> cached ([d]p)
+ *   op 8 select_niels over the context's table {1..128} 256^t B, d in [-128, 127], t < 32 -> niels
+ * Ops 7 and 8 read d (int32 LE) from q's bytes 0..3 and t (uint32 LE) from bytes 4..7; a digit or
+ * table out of range is PRAOS_E_ARG.  q is ignored by the other unary ops. */
+int praos_debug_ge(praos_ctx* ctx, int build, int op, size_t n, const uint8_t* p, const uint8_t* q, uint8_t* out);
+/* The scalar-multiplication chains with the product code's templates and arguments; out n*32, the
+ * encoding of each item's result.  P, Q: n*32 point encodings (decoded as the product decodes
+ * them); sp, sq, sb: n*32 scalars LE.  The product tables hold -A and -Y, so do these:
+ *   variant 0  [sb]B - [sp]P   STRAUS<64,64,0,32,false>   (ed25519_verify_core)
+ *   variant 1  [sb]B - [sp]P   STRAUS<33,33,0,16,true>    (uncached VRF U), sp < 2^128
+ *   variant 2  [sp]P - [sq]Q   STRAUS<64,64,33,0,false>   (VRF V), sq < 2^128
+ *   variant 3  [sb]B - [sp]P   straus_comb<16,false> over key tables of kind 0 and the 2^16 comb
+ *   variant 4  [sb]B - [sp]P   straus_comb<8,true> over key tables of kind 1, sp < 2^128
+ *   variant 5  [sp]P           ge_scalarmult_var
+ * Variants 3 and 4 build their tables with the key cache's own precompute (entry e = key e; its
+ * first pass from the ILP-4 module when build = 1).  Arguments a variant does not use may be
+ * null.  A scalar outside the recodings' range (sp, sb < 2^253; sq, and sp where noted, < 2^128)
+ * is PRAOS_E_ARG. */
+int praos_debug_msm(praos_ctx* ctx, int variant, int build, size_t n, const uint8_t* P, const uint8_t* Q,
+                    const uint8_t* sp, const uint8_t* sq, const uint8_t* sb, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,8 +92,8 @@ FE_INLINE void fe_reduce512(fe& r, const uint32_t t[16]) {
 #endif
 #include "fe_cols.hpp"
 
-// 2 t[0 .. 16) + the diagonal squares a_i^2, reduced: the square from its cross products
-FE_INLINE void fe_sq_finish(fe& r, uint32_t (&t)[16], const fe& a) {
+// t <- 2 t[0 .. 16) + the diagonal squares a_i^2: the 512-bit square from its cross products
+FE_INLINE void fe_sq_diag(uint32_t (&t)[16], const fe& a) {
 #pragma unroll
   for (int i = 15; i > 0; i--) t[i] = (t[i] << 1) | (t[i - 1] >> 31);
   t[0] = 0;
@@ -104,6 +104,10 @@ FE_INLINE void fe_sq_finish(fe& r, uint32_t (&t)[16], const fe& a) {
     t[2 * i] = addc(t[2 * i], (uint32_t)d, c, &c);
     t[2 * i + 1] = addc(t[2 * i + 1], (uint32_t)(d >> 32), c, &c);
   }
+}
+// the same, reduced
+FE_INLINE void fe_sq_finish(fe& r, uint32_t (&t)[16], const fe& a) {
+  fe_sq_diag(t, a);
   fe_reduce512(r, t);
 }
 
@@ -260,8 +264,10 @@ FE_INLINE void fe_sq2(fe& r1, const fe& a1, fe& r2, const fe& a2) {
 #if PRAOS_ILP2 && PRAOS_MACG
   uint32_t t1[16], t2[16];
   fe_cross2_g(t1, t2, a1, a2);
-  fe_sq_finish(r1, t1, a1);
-  fe_sq_finish(r2, t2, a2);
+  fe_sq_diag(t1, a1);                                // both inputs are read to the end before a result
+  fe_sq_diag(t2, a2);                                // is written: r1 may be the object a2
+  fe_reduce512(r1, t1);
+  fe_reduce512(r2, t2);
 #elif PRAOS_ILP2
   uint32_t t1[16], t2[16];
   uint64_t acc1 = 0, acc2 = 0;

@@ -235,3 +235,17 @@ void launch_pbft_sig_ck(hipStream_t stream, size_t n, const uint32_t* list, cons
 void launch_pbft_keyhash(hipStream_t stream, size_t n, const uint8_t* keys64, uint8_t* out28);
 // replay: nonce contribution of each header's certified VRF output (k_misc.hip)
 void launch_vrf_nonce(hipStream_t stream, size_t n, const uint8_t* vrf_out, int tpraos, uint8_t* nonce_out);
+// self-test kernels of the field / group / scalar-multiplication layers (k_selftest.hip; the
+// launch_selftest4_* forms come from the ILP-4 build, k_selftest4.hip)
+void launch_selftest_fe_multi(hipStream_t stream, int op, size_t n, const uint8_t* in, uint8_t* out);
+void launch_selftest_fe(hipStream_t stream, int op, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* r);
+void launch_selftest_ge(hipStream_t stream, int op, size_t n, const uint8_t* p, const uint8_t* q, uint8_t* out,
+                        const ge_niels* gbtab);
+void launch_selftest4_ge(hipStream_t stream, int op, size_t n, const uint8_t* p, const uint8_t* q, uint8_t* out,
+                         const ge_niels* gbtab);
+void launch_selftest_msm(hipStream_t stream, int variant, size_t n, const uint8_t* P, const uint8_t* Q,
+                         const uint8_t* sp, const uint8_t* sq, const uint8_t* sb, const ge_niels* gbtab,
+                         const ge_niels* comb, ge_cached* tabs, const ge_cached* ktab, uint8_t* out);
+void launch_selftest4_msm(hipStream_t stream, int variant, size_t n, const uint8_t* P, const uint8_t* Q,
+                          const uint8_t* sp, const uint8_t* sq, const uint8_t* sb, const ge_niels* gbtab,
+                          const ge_niels* comb, ge_cached* tabs, const ge_cached* ktab, uint8_t* out);

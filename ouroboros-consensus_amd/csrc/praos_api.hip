@@ -4304,7 +4304,8 @@ int praos_debug_fe(praos_ctx* c, int op, size_t n, const uint8_t* a, const uint8
   auto db = s.up(b ? b : a, 32 * n);
   auto dr = s.zeros<uint8_t>(32 * n);
   if (!s.ok) return PRAOS_E_OOM;
-  launch_debug_fe(dim3(nblocks(n, 64)), dim3(64), c->stream, op, n, da, db, dr);
+  if (op >= 9 && op <= 14) launch_selftest_fe(c->stream, op, n, da, db, dr);   // k_selftest.hip
+  else launch_debug_fe(dim3(nblocks(n, 64)), dim3(64), c->stream, op, n, da, db, dr);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(r, dr, 32 * n, hipMemcpyDeviceToHost));
@@ -4443,6 +4444,106 @@ int praos_debug_hash_to_curve(praos_ctx* c, size_t n, const uint8_t* pk, const u
   auto dout = s.zeros<uint8_t>(32 * n);
   if (!s.ok) return PRAOS_E_OOM;
   launch_debug_h2c(dim3(nblocks(n, 64)), dim3(64), c->stream, n, dpk, dal, dout);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, dout, 32 * n, hipMemcpyDeviceToHost));
+  return PRAOS_OK;
+}
+
+int praos_debug_fe_multi(praos_ctx* c, int op, size_t n, const uint8_t* in, uint8_t* out) {
+  if (!c || !in || !out || op < 0 || (op & 7) > 4 || op > 12) return PRAOS_E_ARG;
+  if (n == 0) return PRAOS_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  Scratch s(c);
+  auto di = s.up(in, 256 * n);
+  auto dout = s.zeros<uint8_t>(128 * n);
+  if (!s.ok) return PRAOS_E_OOM;
+  launch_selftest_fe_multi(c->stream, op, n, di, dout);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, dout, 128 * n, hipMemcpyDeviceToHost));
+  return PRAOS_OK;
+}
+
+int praos_debug_ge(praos_ctx* c, int build, int op, size_t n, const uint8_t* p, const uint8_t* q, uint8_t* out) {
+  if (!c || !p || !q || !out || build < 0 || build > 1 || op < 0 || op > 8) return PRAOS_E_ARG;
+  if (n == 0) return PRAOS_OK;
+  if (op == 7 || op == 8) {                          // the selects index tables with the digit
+    for (size_t i = 0; i < n; i++) {
+      int32_t d;
+      uint32_t t;
+      std::memcpy(&d, q + 128 * i, 4);
+      std::memcpy(&t, q + 128 * i + 4, 4);
+      if (op == 7 ? (d < -8 || d > 7) : (d < -128 || d > 127 || t >= BCOMB_TABLES)) return PRAOS_E_ARG;
+    }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  Scratch s(c);
+  auto dp = s.up(p, 128 * n);
+  auto dq = s.up(q, 128 * n);
+  auto dout = s.zeros<uint8_t>(128 * n);
+  if (!s.ok) return PRAOS_E_OOM;
+  if (build) launch_selftest4_ge(c->stream, op, n, dp, dq, dout, c->btab);
+  else launch_selftest_ge(c->stream, op, n, dp, dq, dout, c->btab);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, dout, 128 * n, hipMemcpyDeviceToHost));
+  return PRAOS_OK;
+}
+
+// every 32-byte little-endian scalar of s[0 .. n) is below 2^bits
+static bool scalars_below(const uint8_t* s, size_t n, int bits) {
+  for (size_t i = 0; i < n; i++)
+    for (int k = bits / 8; k < 32; k++)
+      if (k == bits / 8 ? (s[32 * i + k] >> (bits % 8)) != 0 : s[32 * i + k] != 0) return false;
+  return true;
+}
+
+int praos_debug_msm(praos_ctx* c, int variant, int build, size_t n, const uint8_t* P, const uint8_t* Q,
+                    const uint8_t* sp, const uint8_t* sq, const uint8_t* sb, uint8_t* out) {
+  if (!c || !out || variant < 0 || variant > 5 || build < 0 || build > 1 || !P || !sp) return PRAOS_E_ARG;
+  const bool use_q = variant == 2, use_b = variant != 2 && variant != 5, cached = variant == 3 || variant == 4;
+  if ((use_q && (!Q || !sq)) || (use_b && !sb)) return PRAOS_E_ARG;
+  if (n == 0) return PRAOS_OK;
+  if (n > (1u << 20)) return PRAOS_E_ARG;
+  // the recodings' documented ranges (scalarmult.hpp)
+  if (!scalars_below(sp, n, (variant == 1 || variant == 4) ? 128 : 253)) return PRAOS_E_ARG;
+  if (use_q && !scalars_below(sq, n, 128)) return PRAOS_E_ARG;
+  if (use_b && !scalars_below(sb, n, 253)) return PRAOS_E_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (cached) {
+    const int rc = ensure_bcomb16(c);
+    if (rc != PRAOS_OK) return rc;
+  }
+  Scratch s(c);
+  auto dP = s.up(P, 32 * n);
+  auto dQ = use_q ? s.up(Q, 32 * n) : (uint8_t*)nullptr;
+  auto dsp = s.up(sp, 32 * n);
+  auto dsq = use_q ? s.up(sq, 32 * n) : (uint8_t*)nullptr;
+  auto dsb = use_b ? s.up(sb, 32 * n) : (uint8_t*)nullptr;
+  auto dout = s.zeros<uint8_t>(32 * n);
+  ge_cached* tabs = nullptr;
+  ge_cached* ktab = nullptr;
+  if (cached) {
+    // the key tables as the product builds them: entry e is key e, both passes of k_keys.hip
+    // (pass 1 from k_keys4.hip when build = 1)
+    constexpr size_t KT_BYTES = 16 * 8 * CACHED_BYTES;   // KT_STRIDE entries per key (scalarmult.hpp)
+    std::vector<uint32_t> rep(n);
+    for (size_t i = 0; i < n; i++) rep[i] = (uint32_t)i;
+    const uint32_t cnt[4] = {(uint32_t)n, 0, 0, 0};
+    auto drep = s.up(rep.data(), 4 * n);
+    auto dcnt = s.up(cnt, sizeof cnt);
+    auto kinfo = s.zeros<uint32_t>(9 * 4 * n);
+    ktab = s.zeros<ge_cached>(KT_BYTES * n);
+    if (!s.ok) return PRAOS_E_OOM;
+    launch_key_precompute(variant == 3 ? 0 : 1, c->stream, dcnt, (uint32_t)n, drep, dP, ktab, kinfo, 0, nullptr,
+                          (uint32_t)n, build);
+  } else {
+    tabs = s.zeros<ge_cached>(LT_VRF_B * n);
+  }
+  if (!s.ok) return PRAOS_E_OOM;
+  if (build) launch_selftest4_msm(c->stream, variant, n, dP, dQ, dsp, dsq, dsb, c->btab, c->bcomb16, tabs, ktab, dout);
+  else launch_selftest_msm(c->stream, variant, n, dP, dQ, dsp, dsq, dsb, c->btab, c->bcomb16, tabs, ktab, dout);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(out, dout, 32 * n, hipMemcpyDeviceToHost));

@@ -417,6 +417,10 @@ SIGNATURES = {
     "praos_debug_leader": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, u8p, u8p, u8p, i32p]),
     "praos_debug_leader512": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, u8p, u8p, u8p, i32p]),
     "praos_debug_hash_to_curve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, u8p, u8p, u8p]),
+    "praos_debug_fe_multi": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, u8p, u8p]),
+    "praos_debug_ge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, u8p, u8p, u8p]),
+    "praos_debug_msm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, u8p, u8p, u8p,
+                                       u8p, u8p, u8p]),
 }
 
 _lib = None
@@ -1363,6 +1367,32 @@ class Context:
     def debug_hash_to_curve(self, pk, alpha):
         out = np.zeros((len(pk), 32), np.uint8)
         self.check(self.L.praos_debug_hash_to_curve(self.h, len(pk), ptr(pk), ptr(alpha), ptr(out)))
+        return out
+
+    def debug_fe_multi(self, op, ins):
+        """ins (n, 8, 32): a1 b1 .. a4 b4 -> (n, 4, 32); op 0..4 (fe_mul2, fe_sq2, fe_mul3, fe_mul4, fe_sq4), | 8 aliased"""
+        ins = np.ascontiguousarray(ins, np.uint8)
+        n = len(ins)
+        out = np.zeros((n, 4, 32), np.uint8)
+        self.check(self.L.praos_debug_fe_multi(self.h, op, n, ptr(ins), ptr(out)))
+        return out
+
+    def debug_ge(self, build, op, p, q=None):
+        """p, q (n, 128) raw coordinates -> (n, 128); the ops and layouts are in praos_hip.h"""
+        p = np.ascontiguousarray(p, np.uint8)
+        q = np.ascontiguousarray(q, np.uint8) if q is not None else np.zeros_like(p)
+        n = len(p)
+        out = np.zeros((n, 128), np.uint8)
+        self.check(self.L.praos_debug_ge(self.h, build, op, n, ptr(p), ptr(q), ptr(out)))
+        return out
+
+    def debug_msm(self, variant, build, P, sp, Q=None, sq=None, sb=None):
+        """P, Q (n, 32) encodings, sp, sq, sb (n, 32) scalars -> (n, 32) encodings of the variant's result"""
+        n = len(P)
+        a = [np.ascontiguousarray(x, np.uint8) if x is not None else None for x in (P, Q, sp, sq, sb)]
+        out = np.zeros((n, 32), np.uint8)
+        self.check(self.L.praos_debug_msm(self.h, variant, build, n, *[ptr(x) if x is not None else None for x in a],
+                                          ptr(out)))
         return out
 
 

@@ -220,3 +220,18 @@ def test_db_analyser_patch_wires_the_analysis():
                    "validateEpochHeadersTPraos", "instance CardanoHardForkConstraints c => HasHeaderBatch (CardanoBlock c)",
                    "praosHostRegister"):
         assert needle in mod, needle
+
+
+def test_selftest_entry_points_declared_and_bound():
+    """The self tests of the field products, group formulas and scalar-multiplication schedules are
+    declared next to the other praos_debug_* functions, bound, and reachable from Context; the
+    ABI version did not move for them."""
+    from praos_hip import abi
+    names = _declared()
+    for n, method in (("praos_debug_fe_multi", "debug_fe_multi"), ("praos_debug_ge", "debug_ge"),
+                      ("praos_debug_msm", "debug_msm")):
+        assert n in names and n in abi.SIGNATURES and callable(getattr(abi.Context, method)), n
+    assert len(abi.SIGNATURES["praos_debug_ge"][1]) == 7 and len(abi.SIGNATURES["praos_debug_msm"][1]) == 10
+    hdr = open(abi.HEADER_PATH).read()
+    assert hdr.index("praos_debug_hash_to_curve(") < hdr.index("praos_debug_fe_multi(") < hdr.index("praos_debug_msm(")
+    assert int(re.search(r"#define PRAOS_ABI_VERSION (\d+)", hdr).group(1)) == 15

@@ -5,15 +5,10 @@ import hashlib
 import numpy as np
 import pytest
 
+from field_cases import edge_values as _edge_values, rare_fold_pairs as _rare_fold_pairs, ring_pairs
 from helpers import L, P, arr, b2b, rbytes, rng
 
 pytestmark = pytest.mark.gpu
-
-
-def _edge_values():
-    v = [0, 1, 2, 19, P - 1, P, P + 1, 2 * P - 1, 2 * P, 2 ** 255 - 1, 2 ** 255, 2 ** 256 - 1, 2 ** 256 - 38,
-         2 ** 256 - 39, 38, 2 ** 32 - 1, 2 ** 224]
-    return [x % 2 ** 256 for x in v]
 
 
 def _fe_inputs(seed, n):
@@ -33,26 +28,15 @@ def _from(a):
 
 @pytest.mark.parametrize("op", ["mul", "sq", "add", "sub"])
 def test_fe_ring_ops(ctx, op):
-    xs, ys = _fe_inputs(1, 400)
+    """Every pair of edge values (17 x 17, so (2^256 - 1)(2^256 - 1) too), then 400 random pairs."""
+    pairs = ring_pairs(1, 400)
+    xs, ys = [x for x, _ in pairs], [y for _, y in pairs]
     code = {"mul": 0, "sq": 1, "add": 2, "sub": 3}[op]
     out = _from(ctx.debug_fe(code, _to(xs), _to(ys)))
+    assert len(out) == len(pairs) == 17 * 17 + 400
     for x, y, z in zip(xs, ys, out):
         want = {"mul": x * y, "sq": x * x, "add": x + y, "sub": x - y}[op] % P
         assert z < 2 ** 256 and z % P == want, (op, hex(x), hex(y))
-
-
-def _rare_fold_pairs():
-    """(op, x, y) pairs whose second 2^256 fold carries (add, mul) or borrows (sub) out of limb 0,
-    the branch fe25519.hpp takes with probability < 2^-21 on random operands (PRAOS_RED_BRANCH)."""
-    m = 2 ** 256
-    pairs = [("add", m - 1, 2 ** 32 - 9), ("add", m - 1, m - 9), ("add", m - 1, m - 1),
-             ("add", m - 38, m - 1), ("sub", 3, 2 ** 32), ("sub", 0, m - 5), ("sub", 37, m - 1),
-             ("sub", 0, 1), ("sub", 0, m - 1)]
-    # (2^256 - 1) b folds to 37 b - 38 (b < 2^256 / 37): limb 0 = 2^32 - 1 for b = 2^32 j + 1, and
-    # 37 b - 38 >= 2^256 - 38 (the carry runs through every limb) for b = ceil(2^256 / 37)
-    pairs += [("mul", m - 1, 2 ** 32 * j + 1) for j in (1, 2, 3, 2 ** 64, 2 ** 190)]
-    pairs += [("mul", m - 1, -(-m // 37)), ("mul", -(-m // 37), m - 1)]
-    return pairs
 
 
 def test_fe_rare_fold_carry(ctx):
