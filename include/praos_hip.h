@@ -1117,6 +1117,31 @@ int praos_debug_ge(praos_ctx* ctx, int build, int op, size_t n, const uint8_t* p
 int praos_debug_msm(praos_ctx* ctx, int variant, int build, size_t n, const uint8_t* P, const uint8_t* Q,
                     const uint8_t* sp, const uint8_t* sq, const uint8_t* sb, uint8_t* out);
 
+/* ---- addition (ABI stays 15): self test of the hashes over stored bytes.  The arena is uploaded
+ * as the product paths upload theirs (length rounded up to 8, then 16 zero bytes); every kind
+ * runs the product routine on it, one digest per item.  off / len are the item table:
+ *   kind 0  b2b256_range(arena, off[i], len[i])                                   out n*32
+ *   kind 1  b2b256_pre(arena, off[i], len[i], npre, pre): Blake2b-256 of the npre literal bytes
+ *           followed by the range.  aux n*4: byte 0 npre (0..2), bytes 1..2 the literal bytes,
+ *           byte 3 ignored.  off[i] >= npre (the routine overwrites the bytes before the range
+ *           in registers)                                                        out n*32
+ *   kind 2  the block check's own segment-hash kernel: off / len are seg_off / seg_len, 4n
+ *           entries segment-major ([k][i]), aux n bytes nseg (0..4); slot (k, i) is hashed when
+ *           k < nseg[i]                                out 4n*32, segment-major, 0 where inactive
+ *   kind 3  the SHA-512 register stream (Byron's signed message), then its finalisation  out n*64
+ *   kind 4  the Blake2b-256 register stream (Byron's witness hash)                        out n*32
+ * Kinds 3 and 4: item i is the concatenation of parts off[i] .. off[i] + len[i] - 1 of the part
+ * table, n_parts pairs of 64-bit words (a, b): b < 2^63 is the arena range [a, a + b) (b = 0: an
+ * empty part); b = 2^63 | k, k in 1..8, is a literal, the k low bytes of a in little-endian order.
+ * Parts are fed 8 bytes at a time and then the rest, as the Byron kernels feed theirs.
+ * aux is unused by kinds 0, 3, 4 and parts by kinds 0 .. 2; either may be null there.
+ * PRAOS_E_ARG, with nothing launched: an unknown kind, a range or segment that does not lie inside
+ * [0, arena_len), kind 1 with npre > 2 or off < npre, nseg > 4, a part index outside the table, a
+ * literal length outside 1..8, a part longer than the arena.  PRAOS_E_STATE on a host-only context. */
+int praos_debug_hash_bytes(praos_ctx* ctx, int kind, size_t n, const uint8_t* arena, size_t arena_len,
+                           const uint64_t* off, const uint32_t* len, const uint8_t* aux, const uint64_t* parts,
+                           size_t n_parts, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,17 @@ struct Hs {
       if (k) w >>= 8 * r;
     }
   }
+  // SHA-512 only: the padding (80, zeros, the bit length in the block's last word -- a second
+  // block when fewer than 16 bytes are left after the 80) and the digest words
+  __device__ __forceinline__ void sha512_finish(uint32_t out[16]) {
+    put(0x80, 1);
+    const uint64_t nbits = (total - 1) * 8;
+    for (bool done = false; !done;) {
+      if (fill <= 112) { m[15] = bswap64(nbits); done = true; }
+      compress(false);
+    }
+    sha512_digest_words(out, h);
+  }
 };
 
 // 09 || CBOR(pm) || 85 (the sign tag's magic and the ToSign list head) as the little-endian

@@ -108,44 +108,6 @@ H_INLINE void sha512_digest_words(uint32_t out[16], const uint64_t H[8]) {
 // load big-endian message word from 8 little-endian bytes given as two u32
 H_INLINE uint64_t be_word(uint32_t lo, uint32_t hi) { return bswap64(((uint64_t)hi << 32) | lo); }
 
-// SHA-512 of (prefix[0..64) || msg[0..len)), msg 8-byte aligned in global
-// memory and readable up to round_up(len, 8).  Returns digest words.
-// Lanes may have different lengths (the loop runs to the wave's maximum).
-H_INLINE void sha512_prefix64_msg(uint32_t out[16], const uint32_t prefix[16],
-                                  const uint8_t* __restrict__ msg, uint32_t len) {
-  uint64_t H[8];
-  sha512_init(H);
-  const uint32_t total = 64u + len;
-  const uint32_t nblocks = (total + 17u + 127u) >> 7;
-  for (uint32_t blk = 0; blk < nblocks; blk++) {
-    uint64_t W[16];
-#pragma unroll
-    for (int w = 0; w < 16; w++) {
-      const uint32_t off = blk * 128u + 8u * w;            // stream offset
-      uint64_t v;
-      if (blk == 0 && w < 8) {
-        v = be_word(prefix[2 * w], prefix[2 * w + 1]);
-      } else {
-        const uint32_t m = off - 64u;                      // message offset
-        uint64_t raw = 0;
-        if (m < len) raw = *(const uint64_t*)(msg + m);
-        // bytes >= len are zero; byte at len is 0x80
-        const uint32_t valid = len > m ? (len - m) : 0u;   // bytes of message in this word
-        if (valid < 8) {
-          const uint64_t keep = valid == 0 ? 0ULL : (~0ULL >> (64 - 8 * valid));
-          raw &= keep;
-          if (len >= m && len < m + 8) raw |= 0x80ULL << (8 * (len - m));
-        }
-        v = bswap64(raw);
-      }
-      W[w] = v;
-    }
-    if (blk == nblocks - 1) W[15] = (uint64_t)total * 8u;
-    sha512_block(H, W);
-  }
-  sha512_digest_words(out, H);
-}
-
 // ---------------------------------------------------------------- BLAKE2b
 __device__ __constant__ static const uint64_t B2B_IV[8] = {
   0x6a09e667f3bcc908ULL, 0xbb67ae8584caa73bULL, 0x3c6ef372fe94f82bULL, 0xa54ff53a5f1d36f1ULL,

@@ -214,7 +214,7 @@ __global__ void __launch_bounds__(NT) k_byron_integrity(size_t n, const uint8_t*
     Hs<true> s;
     s.init();
 #pragma nounroll
-    for (uint32_t p = 0; p < 11; p++) {
+    for (uint32_t p = 0; p < 10; p++) {
       uint64_t pos = 0, len = 0, lit = 0;
       switch (p) {
         case 0: pos = A(BS_SIG); len = 32; break;
@@ -226,10 +226,9 @@ __global__ void __launch_bounds__(NT) k_byron_integrity(size_t n, const uint8_t*
         case 6: pos = A(BS_PROOF_O); len = S(BS_PROOF_L); break;
         case 7: pos = A(BS_SID_O); len = S(BS_SID_L); break;
         case 8: pos = A(BS_DIFF_O); len = S(BS_DIFF_L); break;
-        case 9: pos = A(BS_EXTRA_O); len = S(BS_EXTRA_L); break;
-        default: lit = 0x80; len = 1; break;                        // the padding's first byte
+        default: pos = A(BS_EXTRA_O); len = S(BS_EXTRA_L); break;
       }
-      const bool is_lit = p == 2 || p == 4 || p == 10;
+      const bool is_lit = p == 2 || p == 4;
       while (len) {
         const uint32_t k = len < 8 ? (uint32_t)len : 8u;
         s.put(is_lit ? lit : ld64u(arena, pos), k);
@@ -237,12 +236,7 @@ __global__ void __launch_bounds__(NT) k_byron_integrity(size_t n, const uint8_t*
         len -= k;
       }
     }
-    const uint64_t nbits = (s.total - 1) * 8;
-    for (bool done = false; !done;) {
-      if (s.fill <= 112) { s.m[15] = bswap64(nbits); done = true; }
-      s.compress(false);
-    }
-    sha512_digest_words(hram, s.h);
+    s.sha512_finish(hram);
   }
   uint32_t pk[8], sg[16];
   ld_bytes32(pk, arena, A(BS_DELEG));

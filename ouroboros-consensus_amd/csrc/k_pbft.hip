@@ -196,7 +196,7 @@ __device__ bool pbft_decode_one(const PbftDec& a, size_t i) {
   Hs<true> s;
   s.init();
 #pragma nounroll
-  for (uint32_t p = 0; p < 11; p++) {
+  for (uint32_t p = 0; p < 10; p++) {
     uint64_t pos = 0, len = 0, lit = 0;
     switch (p) {
       case 0: pos = sig_at; len = 32; break;
@@ -208,10 +208,9 @@ __device__ bool pbft_decode_one(const PbftDec& a, size_t i) {
       case 6: pos = proof_o; len = proof_l; break;
       case 7: pos = sid_o; len = sid_l; break;
       case 8: pos = diff_o; len = diff_l; break;
-      case 9: pos = extra_o; len = extra_l; break;
-      default: lit = 0x80; len = 1; break;                        // the padding's first byte
+      default: pos = extra_o; len = extra_l; break;
     }
-    const bool is_lit = p == 2 || p == 4 || p == 10;
+    const bool is_lit = p == 2 || p == 4;
     while (len) {
       const uint32_t k = len < 8 ? (uint32_t)len : 8u;
       s.put(is_lit ? lit : ld64u(arena, pos), k);
@@ -219,13 +218,8 @@ __device__ bool pbft_decode_one(const PbftDec& a, size_t i) {
       len -= k;
     }
   }
-  const uint64_t nbits = (s.total - 1) * 8;
-  for (bool done = false; !done;) {
-    if (s.fill <= 112) { s.m[15] = bswap64(nbits); done = true; }
-    s.compress(false);
-  }
   uint32_t hr[16];
-  sha512_digest_words(hr, s.h);
+  s.sha512_finish(hr);
   store_words(a.hram + 64 * i, hr, 16);
   return true;
 }

@@ -249,3 +249,7 @@ void launch_selftest_msm(hipStream_t stream, int variant, size_t n, const uint8_
 void launch_selftest4_msm(hipStream_t stream, int variant, size_t n, const uint8_t* P, const uint8_t* Q,
                           const uint8_t* sp, const uint8_t* sq, const uint8_t* sb, const ge_niels* gbtab,
                           const ge_niels* comb, ge_cached* tabs, const ge_cached* ktab, uint8_t* out);
+// self-test kernels of the stored-byte hashes (k_selftest_hash.hip): praos_debug_hash_bytes kinds
+// 0, 1, 3, 4 (kind 2 is launch_seg_hash); the tables are praos_hip.h's
+void launch_selftest_hash(hipStream_t stream, int kind, size_t n, const uint8_t* arena, const uint64_t* off,
+                          const uint32_t* len, const uint8_t* aux, const uint64_t* parts, uint8_t* out);

@@ -4550,4 +4550,60 @@ int praos_debug_msm(praos_ctx* c, int variant, int build, size_t n, const uint8_
   return PRAOS_OK;
 }
 
+int praos_debug_hash_bytes(praos_ctx* c, int kind, size_t n, const uint8_t* arena, size_t arena_len,
+                           const uint64_t* off, const uint32_t* len, const uint8_t* aux, const uint64_t* parts,
+                           size_t n_parts, uint8_t* out) {
+  if (!c || kind < 0 || kind > 4 || (!arena && arena_len) || n > (1u << 24) || n_parts > (1u << 26))
+    return PRAOS_E_ARG;
+  if (n == 0) return PRAOS_OK;
+  const bool stream = kind >= 3;
+  const size_t items = kind == 2 ? 4 * n : n, out_len = kind == 3 ? 64 : 32;
+  if (!off || !len || !out || ((kind == 1 || kind == 2) && !aux) || (stream && !parts && n_parts)) return PRAOS_E_ARG;
+  auto bad = [&](const std::string& what, size_t i) {
+    c->err = "praos_debug_hash_bytes: " + what + " " + std::to_string(i);
+    return PRAOS_E_ARG;
+  };
+  auto inside = [&](uint64_t o, uint64_t l) { return o <= arena_len && l <= arena_len - o; };
+  if (stream) {
+    for (size_t i = 0; i < n; i++)
+      if (off[i] > n_parts || len[i] > n_parts - off[i]) return bad("part list outside the table, item", i);
+    for (size_t p = 0; p < n_parts; p++) {
+      const uint64_t a = parts[2 * p], b = parts[2 * p + 1];
+      if (b >> 63) {
+        const uint64_t k = b & ~(1ull << 63);
+        if (k < 1 || k > 8) return bad("literal length outside 1..8, part", p);
+      } else if (!inside(a, b)) {
+        return bad("range outside the arena, part", p);
+      }
+    }
+  } else {
+    for (size_t j = 0; j < items; j++)
+      if (!inside(off[j], len[j])) return bad("range outside the arena, item", j);
+    for (size_t i = 0; i < n && kind == 1; i++)
+      if (aux[4 * i] > 2 || off[i] < aux[4 * i]) return bad("literal prefix longer than 2 or than the offset, item", i);
+    for (size_t i = 0; i < n && kind == 2; i++)
+      if (aux[i] > 4) return bad("more than 4 segments, block", i);
+  }
+  if (c->device < 0) { c->err = "host-only context: no HIP device"; return PRAOS_E_STATE; }
+  HIPCHK(c, hipSetDevice(c->device));
+  // the arena as arena_upload leaves it: the bytes, then zeros to the next multiple of 8 and 16 more
+  const size_t padded = ((arena_len + 7) & ~(size_t)7) + 16;
+  std::vector<uint8_t> host(padded, 0);
+  if (arena_len) std::memcpy(host.data(), arena, arena_len);
+  Scratch s(c);
+  auto da = s.up(host.data(), padded);
+  auto doff = s.up(off, 8 * items);
+  auto dlen = s.up(len, 4 * items);
+  auto daux = kind == 1 ? s.up(aux, 4 * n) : kind == 2 ? s.up(aux, n) : (uint8_t*)nullptr;
+  auto dparts = stream ? s.up(parts, 16 * n_parts) : (uint64_t*)nullptr;
+  auto dout = s.zeros<uint8_t>(out_len * items);
+  if (!s.ok) return PRAOS_E_OOM;
+  if (kind == 2) launch_seg_hash(dim3(nblocks(4 * n, NT)), dim3(NT), c->stream, n, da, doff, dlen, daux, dout);
+  else launch_selftest_hash(c->stream, kind, n, da, doff, dlen, daux, dparts, dout);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, dout, out_len * items, hipMemcpyDeviceToHost));
+  return PRAOS_OK;
+}
+
 }  // extern "C"

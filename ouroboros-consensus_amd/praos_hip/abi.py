@@ -421,6 +421,8 @@ SIGNATURES = {
     "praos_debug_ge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, u8p, u8p, u8p]),
     "praos_debug_msm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, u8p, u8p, u8p,
                                        u8p, u8p, u8p]),
+    "praos_debug_hash_bytes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, u8p, ctypes.c_size_t,
+                                              u64p, u32p, u8p, u64p, ctypes.c_size_t, u8p]),
 }
 
 _lib = None
@@ -1393,6 +1395,22 @@ class Context:
         out = np.zeros((n, 32), np.uint8)
         self.check(self.L.praos_debug_msm(self.h, variant, build, n, *[ptr(x) if x is not None else None for x in a],
                                           ptr(out)))
+        return out
+
+    def debug_hash_bytes(self, kind, arena, off, length, aux=None, parts=None):
+        """The stored-byte hashes on a caller's arena (kinds and tables: praos_hip.h).  arena: bytes;
+        off, length: the item table; aux: (n, 4) npre / pre bytes (kind 1) or nseg (kind 2);
+        parts: (n_parts, 2) uint64 (kinds 3, 4).  Returns (items, 32) digests, (n, 64) for kind 3."""
+        a = np.frombuffer(bytes(arena), np.uint8)
+        off = np.ascontiguousarray(off, np.uint64)
+        length = np.ascontiguousarray(length, np.uint32)
+        aux = np.ascontiguousarray(aux, np.uint8) if aux is not None else None
+        parts = np.ascontiguousarray(parts, np.uint64) if parts is not None else None
+        n = len(aux) if kind == 2 else len(off)
+        out = np.zeros((4 * n if kind == 2 else n, 64 if kind == 3 else 32), np.uint8)
+        self.check(self.L.praos_debug_hash_bytes(self.h, kind, n, ptr(a) if len(a) else None, len(a), ptr(off, u64p),
+                                                 ptr(length, u32p), ptr(aux), ptr(parts, u64p),
+                                                 len(parts) if parts is not None else 0, ptr(out)))
         return out
 
 

@@ -62,11 +62,12 @@ def rand_segments(r, big=False, pad=0):
     return [bodies, wits, aux, inval]
 
 
-def make_block(r, spkp, era=6, slot=None, c0=None, big=False, wrapped=True, pad=0):
+def make_block(r, spkp, era=6, slot=None, c0=None, big=False, wrapped=True, pad=0, segs=None):
     """-> (block bytes, header fields, KES seed).  era 2..5: a TPraos block (15-field
-    BHBody; 3 segments for Shelley/Allegra/Mary, 4 for Alonzo); 6/7: Praos."""
+    BHBody; 3 segments for Shelley/Allegra/Mary, 4 for Alonzo); 6/7: Praos.  segs: the
+    four segments (each one CBOR item) instead of random ones."""
     tp = era in bi.TPRAOS_ERAS
-    segs = rand_segments(r, big, pad)
+    segs = rand_segments(r, big, pad) if segs is None else list(segs)
     if era in (2, 3, 4):
         segs = segs[:3]
     bh = bi._b2b(b"".join(bi._b2b(s) for s in segs))

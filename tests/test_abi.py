@@ -235,3 +235,69 @@ def test_selftest_entry_points_declared_and_bound():
     hdr = open(abi.HEADER_PATH).read()
     assert hdr.index("praos_debug_hash_to_curve(") < hdr.index("praos_debug_fe_multi(") < hdr.index("praos_debug_msm(")
     assert int(re.search(r"#define PRAOS_ABI_VERSION (\d+)", hdr).group(1)) == 15
+
+
+def test_hash_bytes_entry_point_and_argument_checks():
+    """praos_debug_hash_bytes is declared after the other self tests, bound with its 11 arguments and
+    reachable from Context; the ABI version did not move; its argument checks need no device and
+    come before anything is uploaded or launched; its kernels are a module of their own."""
+    import numpy as np
+    from praos_hip import abi
+    assert "praos_debug_hash_bytes" in _declared() and callable(abi.Context.debug_hash_bytes)
+    assert len(abi.SIGNATURES["praos_debug_hash_bytes"][1]) == 11
+    hdr = open(abi.HEADER_PATH).read()
+    assert hdr.index("praos_debug_msm(") < hdr.index("praos_debug_hash_bytes(")
+    assert int(re.search(r"#define PRAOS_ABI_VERSION (\d+)", hdr).group(1)) == 15
+    mk = open(os.path.join(os.path.dirname(abi.LIB_PATH), "csrc", "Makefile")).read()
+    assert re.search(r"^MODS := .*\bk_selftest_hash\b", mk, flags=re.M)
+    E_STATE = -4
+    LIT = 1 << 63
+    c = abi.Context(abi.HOST_ONLY)
+    try:
+        arena = np.arange(1, 65, dtype=np.uint8)
+        u64 = lambda *v: np.array(v, np.uint64)
+        u32 = lambda *v: np.array(v, np.uint32)
+        u8 = lambda *v: np.array(v, np.uint8)
+        out = np.zeros(4 * 64, np.uint8)
+
+        def call(kind, n, off, ln, aux=None, parts=None, h=c.h, a=arena, alen=64):
+            return c.L.praos_debug_hash_bytes(h, kind, n, abi.ptr(a), alen, abi.ptr(off, abi.u64p), abi.ptr(ln, abi.u32p),
+                                              abi.ptr(aux), abi.ptr(parts, abi.u64p),
+                                              len(parts) // 2 if parts is not None else 0, abi.ptr(out))
+
+        assert call(0, 1, u64(0), u32(64), h=None) == abi.E_ARG
+        for kind in (-1, 5):
+            assert call(kind, 1, u64(0), u32(64)) == abi.E_ARG
+        assert call(0, 1, u64(0), u32(64), a=None) == abi.E_ARG               # no arena, but a length
+        # well-formed calls get as far as the device check
+        assert call(0, 1, u64(0), u32(64)) == E_STATE
+        assert call(0, 1, u64(64), u32(0)) == E_STATE
+        assert call(1, 1, u64(2), u32(62), aux=u8(2, 9, 9, 0)) == E_STATE
+        assert call(2, 1, u64(0, 8, 16, 63), u32(8, 8, 8, 1), aux=u8(4)) == E_STATE
+        assert call(3, 1, u64(0), u32(2), parts=u64(0, 64, 0x11, LIT | 8)) == E_STATE
+        assert call(4, 1, u64(2), u32(0), parts=u64(0, 64, 0x11, LIT | 1)) == E_STATE   # the empty message
+        # off + len > arena_len
+        assert call(0, 2, u64(0, 60), u32(64, 5)) == abi.E_ARG
+        assert call(0, 1, u64(65), u32(0)) == abi.E_ARG
+        assert call(0, 1, u64(2 ** 64 - 1), u32(2)) == abi.E_ARG              # no wrap-around
+        assert call(1, 1, u64(60), u32(5), aux=u8(0, 0, 0, 0)) == abi.E_ARG
+        assert call(2, 1, u64(0, 8, 16, 63), u32(8, 8, 8, 2), aux=u8(4)) == abi.E_ARG
+        # kind 1: off < npre, npre > 2, no aux
+        assert call(1, 1, u64(1), u32(5), aux=u8(2, 9, 9, 0)) == abi.E_ARG
+        assert call(1, 1, u64(0), u32(5), aux=u8(1, 9, 0, 0)) == abi.E_ARG
+        assert call(1, 1, u64(8), u32(5), aux=u8(3, 9, 9, 9)) == abi.E_ARG
+        assert call(1, 1, u64(8), u32(5)) == abi.E_ARG
+        # kind 2: more than 4 segments
+        assert call(2, 1, u64(0, 8, 16, 24), u32(8, 8, 8, 8), aux=u8(5)) == abi.E_ARG
+        # kinds 3, 4: a part longer than the arena or outside it, a literal of 0 or 9 bytes, a part
+        # list outside the table
+        for kind in (3, 4):
+            assert call(kind, 1, u64(0), u32(1), parts=u64(0, 65)) == abi.E_ARG
+            assert call(kind, 1, u64(0), u32(1), parts=u64(1, 64)) == abi.E_ARG
+            assert call(kind, 1, u64(0), u32(1), parts=u64(7, LIT)) == abi.E_ARG
+            assert call(kind, 1, u64(0), u32(1), parts=u64(7, LIT | 9)) == abi.E_ARG
+            assert call(kind, 1, u64(1), u32(1), parts=u64(0, 8)) == abi.E_ARG
+            assert call(kind, 1, u64(0), u32(2), parts=u64(0, 8)) == abi.E_ARG
+        assert b"praos_debug_hash_bytes" in c.L.praos_last_error(c.h)
+    finally:
+        c.close()

@@ -86,6 +86,32 @@ def test_random_blocks_and_clamp(ctx):
     assert (res == 0).sum() >= 80
 
 
+def _bstr(r, total):
+    """A CBOR byte string whose encoding is `total` bytes long (non-zero content)."""
+    n = total - (1 if total <= 24 else 2)
+    assert 0 <= n < 256 and total != 25
+    return bc.H(2, n) + bytes(r.randrange(1, 256) for _ in range(n))
+
+
+def test_segment_length_edges_at_every_offset(ctx):
+    """Segments of 1, 2, 127, 128, 129, 255, 256 and 257 bytes (both sides of the Blake2b block
+    and of k_seg_hash's staged block), each length in each of the four positions, every block at
+    every arena offset 0..7 between non-zero bytes; the last block ends the arena."""
+    r = random.Random(0x5E6)
+    lens = [1, 2, 127, 128, 129, 255, 256, 257]
+    arena, off, ln = bytearray(), [], []
+    for rot in range(8):
+        blk, _, _ = bc.make_block(r, SPKP, segs=[_bstr(r, lens[(rot + k) % 8]) for k in range(4)])
+        for o in range(8):
+            arena += bytes(r.randrange(1, 256) for _ in range((o - len(arena)) % 8))
+            off.append(len(arena))
+            ln.append(len(blk))
+            arena += blk
+    assert sorted({o % 8 for o in off}) == list(range(8)) and off[-1] + ln[-1] == len(arena)
+    res = _check(ctx, bytes(arena), off, ln)
+    assert not res.any()
+
+
 def test_device_resident_rerun_and_ranges(ctx):
     r = random.Random(9)
     blocks = [bc.make_block(r, SPKP)[0] for _ in range(40)]

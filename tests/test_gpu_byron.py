@@ -359,6 +359,34 @@ def test_direct_entry_equals_the_model(ctx, chain, mutations, golden):
     assert {abi.BYRON_W_DLG, abi.BYRON_W_UPD, abi.BYRON_W_NTX, abi.BYRON_W_WIT, abi.BYRON_W_ROOT} <= seen
 
 
+@pytest.fixture(scope="module")
+def residues(oracle):
+    """An EBB and 128 main blocks: the SHA-512 stream's input (64 + signed message) takes every
+    length modulo 128, the witness stream 2 + 12 n bytes for n = 0..12 transactions."""
+    plan = [[{"tx_sizes": tuple(5 + j for j in range(k % 13)), "fit": (k, 64), "indef": k % 2 == 1}
+             for k in range(128)]]
+    blocks = bc.make_chain(rng(0x0128), plan)
+    assert [(64 + len(b.message)) % 128 for b in blocks[1:]] == list(range(128))
+    want = [bm.integrity(b.bytes, bc.PM) for b in blocks]
+    assert want == [(0, 0)] * 129
+    return blocks, want
+
+
+@pytest.mark.parametrize("shift", range(8))
+def test_every_message_residue_at_every_offset(ctx, residues, shift):
+    """Those blocks with every one at arena offset `shift` + its own place, between non-zero
+    bytes: over the eight shifts every block sits at every offset 0..7."""
+    blocks, want = residues
+    fill = np.random.default_rng(shift).integers(1, 256, 16, dtype=np.uint8).tobytes()
+    arena, off = bytearray(fill[:shift]), []
+    for i, b in enumerate(blocks):
+        arena += fill[:i % 3]
+        off.append(len(arena))
+        arena += b.bytes
+    res, which = ctx.verify_byron_integrity(bytes(arena), off, [len(b.bytes) for b in blocks], bc.EPOCH_SLOTS, bc.PM)
+    assert [(int(a), int(b)) for a, b in zip(res, which)] == want
+
+
 def test_harness_phase_over_the_golden_pair(ctx, golden, tmp_path):
     """ffi_harness --validate-chunk-byron (the foreign-call sequence of Batch.hs validateChunkBatch
     with the Byron parameters) prints what the binding returns."""

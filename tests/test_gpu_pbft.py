@@ -134,6 +134,36 @@ def test_signed_message_lengths(ctx, forged):
     assert not H["bits"].any()
 
 
+@pytest.fixture(scope="module")
+def residues(oracle):
+    """one epoch of 128 main headers, three delegates in turn: the SHA-512 stream's input (64 +
+    signed message) takes every length modulo 128"""
+    r = rng(0x0128)
+    D = [bc.Delegate(r) for _ in range(3)]
+    mains = pc.make_chain(r, 128, lambda k: D[k % 3], epochs=1, fit={k: k for k in range(128)})[1:]
+    delegs = pc.delegation(r, D)
+    return mains, delegs, pc.model_rows(mains, delegs)
+
+
+@pytest.mark.parametrize("shift", range(8))
+def test_every_message_residue_at_every_offset(ctx, residues, shift):
+    """the 128 residues with every header at arena offset `shift` + its own place, between
+    non-zero bytes: over the eight shifts every header sits at every offset 0..7"""
+    mains, delegs, rows = residues
+    assert [(64 + len(b.message)) % 128 for b in mains] == list(range(128))
+    fill = np.random.default_rng(shift).integers(1, 256, 16, dtype=np.uint8).tobytes()
+    arena, off = bytearray(fill[:8 + shift]), []
+    for i, b in enumerate(mains):
+        arena += fill[:i % 3]
+        off.append(len(arena))
+        arena += b.header
+    H = ctx.verify_pbft_headers(np.frombuffer(bytes(arena), np.uint8).copy(), np.array(off, np.uint64),
+                                np.array([len(b.header) for b in mains], np.uint32), np.zeros(128, np.uint8), params(),
+                                delegs, delegate_hash=True)
+    same(H, rows, shift)
+    assert not H["bits"].any()
+
+
 def _mutations(forged):
     base = forged["blocks"][6]                    # a main header of delegate D[2] (in the map)
     ebb = forged["blocks"][0]

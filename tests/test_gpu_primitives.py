@@ -78,7 +78,7 @@ def test_fe_invert_gcd_vs_fermat(ctx):
 
 def test_sha512_stream(ctx):
     r = rng(3)
-    lens = list(range(0, 140)) + [300, 397, 461, 511, 512, 1000]
+    lens = list(range(0, 401)) + [461, 511, 512, 1000]
     msgs = [rbytes(r, n) for n in lens]
     pre = [rbytes(r, 64) for _ in lens]
     out = ctx.debug_sha512(arr(pre, 64), msgs)
