@@ -229,12 +229,33 @@ void praos_batch_free(praos_ctx* ctx, praos_batch* b);
  * are identical either way. */
 #define PRAOS_OPT_KES_NOCACHE 8
 int praos_set_option(praos_ctx* ctx, int opt, int value);
+/* The wide tier of the VRF key cache.  min_uses (default -1 = automatic): a cached VRF key used
+ * by at least this many headers of a batch gets, instead of its chunk tables, a table for every
+ * 6-bit digit position of the challenge (22 x 32 points, 88 KB), and the U chains of its headers
+ * are 22 additions without a doubling.  0 = no wide tier.  Automatic: 43 uses (the break-even of the
+ * tables' cost) in batches of 300,000 headers or more.  max_keys (default 4096; < 1 = the
+ * default): at most this many wide keys per batch (and never more than batch size / min_uses);
+ * further keys stay in the chunk tier.  A run that uses the pool-key store (PRAOS_OPT_POOL_KEYS)
+ * has no wide tier: the store's entries are chunk-tier entries.  An explicit min_uses applies at
+ * every batch size; below 300,000 headers it can be slower than 0, because the key tables are on
+ * that step's critical path and the wide hits run the plain stage-U kernel while the chunk tier's
+ * run the ILP-4 build.  Memory: a batch allocates its wide buffers (88 KB per wide key, at most
+ * max_keys, plus a second hit list) in the first run that uses the tier and keeps them; a later
+ * run that needs more keys (a lower min_uses, a higher max_keys) allocates a larger set, and the
+ * smaller one stays owned by the batch until it is freed.  Verdicts and outputs are identical
+ * either way.  Environment: PRAOS_VRF_WIDE,
+ * PRAOS_VRF_WIDE_CAP at praos_open.  Returns 0. */
+int praos_set_vrf_wide(praos_ctx* ctx, int min_uses, int max_keys);
 /* Key-cache statistics of the last praos_batch_run (after praos_batch_sync):
  * out[0..2] = cold keys cached, OCert items on cached keys, OCert items
  * uncached; out[3..5] = the same for VRF keys; out[6..8] for the KES leaf keys
  * (the Ed25519 key each Sum6KES signature ends on).  With the pool-key store on
  * (PRAOS_OPT_POOL_KEYS) out[0] / out[3] count the store's entries after the run.  Returns 0. */
 int praos_batch_stats(praos_ctx* ctx, praos_batch* b, uint32_t out[9]);
+/* The wide tier of the VRF key cache in the last praos_batch_run: out[0] = wide keys, out[1] =
+ * VRF items on wide keys (counted in praos_batch_stats out[4] as well).  Every wide key's tables
+ * are built by the run that uses them.  Both 0 when the tier was off.  Returns 0. */
+int praos_batch_wide_stats(praos_ctx* ctx, praos_batch* b, uint32_t out[2]);
 /* OCert dedup of the last praos_batch_run: out[0] = distinct OCert tuples verified,
  * out[1] = headers (out[0] = 0 when the dedup did not run).  Returns 0. */
 int praos_batch_dedup_stats(praos_ctx* ctx, praos_batch* b, uint32_t out[2]);
@@ -1110,6 +1131,8 @@ int praos_debug_ge(praos_ctx* ctx, int build, int op, size_t n, const uint8_t* p
  *   variant 3  [sb]B - [sp]P   straus_comb<16,false> over key tables of kind 0 and the 2^16 comb
  *   variant 4  [sb]B - [sp]P   straus_comb<8,true> over key tables of kind 1, sp < 2^128
  *   variant 5  [sp]P           ge_scalarmult_var
+ *   variant 6  [sb]B - [sp]P   straus_pos over the wide tables of kind 1 and the 2^16 comb,
+ *                              sp < 2^128, n <= 4096
  * Variants 3 and 4 build their tables with the key cache's own precompute (entry e = key e; its
  * first pass from the ILP-4 module when build = 1).  Arguments a variant does not use may be
  * null.  A scalar outside the recodings' range (sp, sb < 2^253; sq, and sp where noted, < 2^128)

@@ -18,6 +18,12 @@
 //                    misses to the miss list in item order (wave-aggregated)
 //   k_key_precompute per entry: checks, decode, tables (and Y's encoding)
 //
+// Wide tier (VRF keys): a key used by at least wide_min headers of the batch gets the positional
+// tables of scalarmult.hpp (WT_POS x {1..32} 64^k (-Y), 88 KB) instead of chunk tables, and its
+// headers' U chains read those (straus_pos: no doublings).  k_key_assign decides
+// per entry from the use counts it already has, up to wide_cap keys per batch (the rest stay
+// in the chunk tier); the wide keys' hits go to a hit list of their own, grouped by key.
+//
 // Pool-key store (PRAOS_OPT_POOL_KEYS, cold and VRF keys): the entries and tables persist
 // across runs of a context.  k_key_insert first probes the store (keys compared byte for
 // byte) and a key found there is a hit on its stored entry without entering the batch's
@@ -81,9 +87,14 @@ __global__ void k_key_insert(size_t n, const uint32_t* __restrict__ list, const 
 // atomic each (ids and hit-list ranges follow the lanes' order inside the wave).  One atomic
 // per entry on the two shared counters serialised on their addresses: 0.74 ms for the 173k
 // leaf keys of configs[3] (profiles/r04c4_rocprof.txt).
+// Wide tier (wide_min > 0): wcnt: [0] wide keys claimed (those below wide_cap get tables),
+// [1] wide hits, [2] wide hit-list ranges handed out; entry_wide[e] = the entry's wide index or
+// -1, wide_ent its inverse.  A wide key's range lies in the wide hit list.
 __global__ void k_key_assign(uint32_t cap, const uint32_t* __restrict__ slot_rep, const uint32_t* __restrict__ slot_cnt,
                              uint32_t min_count, uint32_t max_entries, int32_t* __restrict__ slot_entry,
-                             uint32_t* __restrict__ entry_rep, uint32_t* __restrict__ entry_pos, uint32_t* counters) {
+                             uint32_t* __restrict__ entry_rep, uint32_t* __restrict__ entry_pos, uint32_t* counters,
+                             uint32_t wide_min, uint32_t wide_cap, int32_t* __restrict__ entry_wide,
+                             uint32_t* __restrict__ wide_ent, uint32_t* wcnt) {
   const uint32_t h = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = h < cap;                           // every lane stays for the ballot and the scan
   const uint32_t rep = in ? slot_rep[h] : 0u;
@@ -102,22 +113,38 @@ __global__ void k_key_assign(uint32_t cap, const uint32_t* __restrict__ slot_rep
   // only the keys that get an entry claim a range of the hit list, so it has no holes
   const uint32_t k = e_base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
   const bool got = take && k < max_entries;
-  // exclusive prefix sum of the cached keys' use counts over the wave
-  uint32_t incl = got ? cnt : 0u;
+  // the wide tier's keys, claimed the same way (wave-uniform wide_min)
+  bool wide = false;
+  uint32_t wi = 0;
+  if (wide_min) {
+    const bool wtake = got && cnt >= wide_min;
+    const uint64_t wm = __ballot(wtake);
+    uint32_t w_base = 0;
+    if (lane == 0 && wm) w_base = atomicAdd(&wcnt[0], (uint32_t)__popcll(wm));
+    w_base = __shfl(w_base, 0);
+    wi = w_base + (uint32_t)__popcll(wm & ((1ull << lane) - 1ull));
+    wide = wtake && wi < wide_cap;
+  }
+  // exclusive prefix sum of the cached keys' use counts over the wave (chunk tier | wide tier)
+  uint32_t incl = got && !wide ? cnt : 0u, wincl = wide ? cnt : 0u;
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t v = __shfl_up(incl, d);
-    if (lane >= (uint32_t)d) incl += v;
+    const uint32_t v = __shfl_up(incl, d), wv = __shfl_up(wincl, d);
+    if (lane >= (uint32_t)d) { incl += v; wincl += wv; }
   }
-  const uint32_t total = __shfl(incl, 63);
-  uint32_t p_base = 0;
+  const uint32_t total = __shfl(incl, 63), wtotal = __shfl(wincl, 63);
+  uint32_t p_base = 0, wp_base = 0;
   if (lane == 0 && total) p_base = atomicAdd(&counters[3], total);
+  if (lane == 0 && wtotal) wp_base = atomicAdd(&wcnt[2], wtotal);
   p_base = __shfl(p_base, 0);
+  wp_base = __shfl(wp_base, 0);
   int32_t e = -1;
   if (got) {
     e = (int32_t)k;
     entry_rep[k] = rep - 1u;
-    entry_pos[k] = p_base + incl - cnt;              // this key's range of the hit list
+    entry_pos[k] = wide ? wp_base + wincl - cnt : p_base + incl - cnt;   // this key's range of its hit list
+    if (entry_wide) entry_wide[k] = wide ? (int32_t)wi : -1;
+    if (wide) wide_ent[wi] = k;
   }
   if (in) slot_entry[h] = e;
 }
@@ -165,7 +192,9 @@ __global__ void k_key_partition(size_t n, const uint32_t* __restrict__ list, con
                                 const int32_t* __restrict__ item_slot, const int32_t* __restrict__ slot_entry,
                                 int32_t* __restrict__ item_entry, uint32_t* __restrict__ entry_pos,
                                 uint32_t* __restrict__ hit_list, uint32_t* __restrict__ miss_list,
-                                uint32_t* counters, uint32_t* __restrict__ spos) {
+                                uint32_t* counters, uint32_t* __restrict__ spos,
+                                const int32_t* __restrict__ entry_wide, uint32_t* __restrict__ wide_hit_list,
+                                uint32_t* wcnt) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = t < (list ? (size_t)*count : n);   // every lane stays for the ballots
   const size_t i = in ? (list ? list[t] : t) : 0;
@@ -173,10 +202,15 @@ __global__ void k_key_partition(size_t n, const uint32_t* __restrict__ list, con
   const bool stored = sl <= -2;
   const int32_t e = !in ? -1 : (stored ? -2 - sl : slot_entry[sl]);
   if (in) item_entry[i] = e;
-  if (in && e >= 0) hit_list[atomicAdd(stored ? &spos[e] : &entry_pos[e], 1u)] = (uint32_t)i;
-  const uint64_t hits = __ballot(in && e >= 0);
+  const bool wide = in && e >= 0 && entry_wide && entry_wide[e] >= 0;   // (the store's entries are chunk tier)
+  if (in && e >= 0)
+    (wide ? wide_hit_list : hit_list)[atomicAdd(stored ? &spos[e] : &entry_pos[e], 1u)] = (uint32_t)i;
+  const uint64_t hits = __ballot(in && e >= 0 && !wide);
   if (hits && __lane_id() == (uint32_t)(__ffsll((unsigned long long)hits) - 1))
     atomicAdd(&counters[1], (uint32_t)__popcll(hits));
+  const uint64_t whits = __ballot(wide);
+  if (whits && __lane_id() == (uint32_t)(__ffsll((unsigned long long)whits) - 1))
+    atomicAdd(&wcnt[1], (uint32_t)__popcll(whits));
   wave_append(in && e < 0, (uint32_t)i, &counters[2], miss_list);
 }
 
@@ -196,16 +230,48 @@ __global__ void __launch_bounds__(64) k_key_precompute(int kind, const uint32_t*
     key_precompute_entry(kind, e, entry_rep, keys, ktab, kinfo);
 }
 
-// pass 2: lane (entry, chunk) expands the chunk base into its 8-entry table
+// pass 2: lane (entry, chunk) expands the chunk base into its 8-entry table (not for a key of the
+// wide tier: every hit on it reads its positional tables)
 __global__ void __launch_bounds__(256) k_key_tables(int kind, const uint32_t* __restrict__ counters,
                                                     uint32_t max_entries, ge_cached* __restrict__ ktab,
-                                                    int wave_prio, const uint32_t* __restrict__ base) {
+                                                    int wave_prio, const uint32_t* __restrict__ base,
+                                                    const int32_t* __restrict__ entry_wide) {
   if (wave_prio) __builtin_amdgcn_s_setprio(3);
   const uint32_t e0 = base ? *base : 0u, ne = min(counters[0], max_entries);
   const uint32_t lanes = ne > e0 ? (ne - e0) * KT_CHUNKS : 0u;
   for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < lanes; t += gridDim.x * blockDim.x) {
     const uint32_t e = e0 + t / KT_CHUNKS, k = t % KT_CHUNKS;
-    if (k < (uint32_t)key_chunks(kind)) key_chunk_table(ktab + (size_t)e * KT_STRIDE + 8 * k);
+    if (k < (uint32_t)key_chunks(kind) && !(entry_wide && entry_wide[e] >= 0))
+      key_chunk_table(ktab + (size_t)e * KT_STRIDE + 8 * k);
+  }
+}
+
+// wide tier, pass 1: lane (wide key w < min(wcnt[0], wide_cap), chunk k < 8) reads its entry's chunk
+// base k (a p3 in entry 0 of the chunk table, so this runs between k_key_precompute and
+// k_key_tables) and writes the position bases that lie in the chunk's 16 bits
+__global__ void __launch_bounds__(64) k_key_wide_bases(const uint32_t* __restrict__ wcnt, uint32_t wide_cap,
+                                                        const uint32_t* __restrict__ wide_ent,
+                                                        const ge_cached* __restrict__ ktab,
+                                                        ge_cached* __restrict__ wbase, int wave_prio) {
+  if (wave_prio) __builtin_amdgcn_s_setprio(3);
+  const uint32_t lanes = min(wcnt[0], wide_cap) * 8u;
+  for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < lanes; t += gridDim.x * blockDim.x) {
+    const uint32_t w = t / 8u, k = t % 8u;
+    const ge_p3 Q = *(const ge_p3*)(ktab + (size_t)wide_ent[w] * KT_STRIDE + 8 * k);
+    key_pos_bases(wbase + (size_t)w * WT_POS, Q, (int)k);
+  }
+}
+// wide tier, pass 2: lane (half, key, position) expands the position base into one half of its
+// WT_N-entry table (the halves apart, so a wave's lanes run the same prologue)
+__global__ void __launch_bounds__(256) k_key_wide_tables(const uint32_t* __restrict__ wcnt, uint32_t wide_cap,
+                                                         const ge_cached* __restrict__ wbase,
+                                                         ge_cached* __restrict__ wtab, int wave_prio) {
+  if (wave_prio) __builtin_amdgcn_s_setprio(3);
+  const uint32_t tabs = min(wcnt[0], wide_cap) * WT_POS;
+  for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < 2u * tabs; t += gridDim.x * blockDim.x) {
+    const uint32_t half = t >= tabs ? 1u : 0u, p = t - half * tabs;
+    const ge_p3 Q = *(const ge_p3*)(wbase + p);
+    key_pos_table(wtab + (size_t)p * WT_N, Q, (int)half);
   }
 }
 
@@ -330,28 +396,37 @@ void launch_key_store_ranges(hipStream_t stream, uint32_t entries, const uint32_
 }
 void launch_key_assign(dim3 grid, dim3 block, hipStream_t stream, uint32_t cap, const uint32_t* slot_rep,
                        const uint32_t* slot_cnt, uint32_t min_count, uint32_t max_entries, int32_t* slot_entry,
-                       uint32_t* entry_rep, uint32_t* entry_pos, uint32_t* counters) {
+                       uint32_t* entry_rep, uint32_t* entry_pos, uint32_t* counters, const KeyWide& w) {
   hipLaunchKernelGGL(k_key_assign, grid, block, 0, stream, cap, slot_rep, slot_cnt, min_count, max_entries, slot_entry,
-                     entry_rep, entry_pos, counters);
+                     entry_rep, entry_pos, counters, w.min_uses, w.cap, w.min_uses ? w.entry_wide : nullptr, w.wide_ent,
+                     w.wcnt);   // (tier off: no entry_wide, whose size is the batch's own entry count)
 }
 void launch_key_partition(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint32_t* list,
                           const uint32_t* count, const int32_t* item_slot, const int32_t* slot_entry,
                           int32_t* item_entry, uint32_t* entry_pos, uint32_t* hit_list, uint32_t* miss_list,
-                          uint32_t* counters, uint32_t* spos) {
+                          uint32_t* counters, uint32_t* spos, const KeyWide& w) {
   hipLaunchKernelGGL(k_key_partition, grid, block, 0, stream, n, list, count, item_slot, slot_entry, item_entry,
-                     entry_pos, hit_list, miss_list, counters, spos);
+                     entry_pos, hit_list, miss_list, counters, spos, w.min_uses ? w.entry_wide : nullptr, w.hit,
+                     w.wcnt);
 }
 void launch_key_precompute(int kind, hipStream_t stream, const uint32_t* counters, uint32_t max_entries,
                            const uint32_t* entry_rep, const uint8_t* keys, ge_cached* ktab, uint32_t* kinfo,
-                           int wave_prio, const uint32_t* base, uint32_t span, int mode) {
+                           int wave_prio, const uint32_t* base, uint32_t span, int mode, const KeyWide& w) {
   if (mode == 1)
     launch_key_precompute4(kind, stream, counters, max_entries, entry_rep, keys, ktab, kinfo, wave_prio, base, span);
   else
     hipLaunchKernelGGL(k_key_precompute, dim3((span + 63) / 64), dim3(64), 0, stream, kind, counters, max_entries,
                        entry_rep, keys, ktab, kinfo, wave_prio, base);
+  if (w.min_uses) {   // (pass 1 reads the chunk bases' entry 0 before k_key_tables rewrites it)
+    const size_t wl = (size_t)w.cap * WT_POS * 2;
+    hipLaunchKernelGGL(k_key_wide_bases, dim3((w.cap * 8 + 63) / 64), dim3(64), 0, stream, w.wcnt, w.cap, w.wide_ent,
+                       ktab, w.wbase, wave_prio);
+    hipLaunchKernelGGL(k_key_wide_tables, dim3((unsigned)((wl + 255) / 256)), dim3(256), 0, stream, w.wcnt, w.cap,
+                       w.wbase, w.wtab, wave_prio);
+  }
   const size_t lanes = (size_t)span * KT_CHUNKS;
   hipLaunchKernelGGL(k_key_tables, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, kind, counters,
-                     max_entries, ktab, wave_prio, base);
+                     max_entries, ktab, wave_prio, base, w.min_uses ? w.entry_wide : nullptr);
 }
 void launch_pkey_reset(hipStream_t stream, uint32_t* count, int32_t* pentry, uint32_t slots, uint32_t limit, int force) {
   hipLaunchKernelGGL(k_pkey_decide, dim3(1), dim3(64), 0, stream, count, limit, force);

@@ -175,7 +175,9 @@ __global__ void __launch_bounds__(64) k_selftest_ge(int op, size_t n, const uint
 //   V 3: [sb]B - [sp]P   straus_comb<16, false> over key tables of kind 0 (ktab) and the comb
 //   V 4: [sb]B - [sp]P   straus_comb<8, true> over key tables of kind 1, sp < 2^128
 //   V 5: [sp]P           ge_scalarmult_var
-// tabs: 16 cached entries per lane (V 0 .. 2); ktab: KT_STRIDE entries per lane (V 3, 4).
+//   V 6: [sb]B - [sp]P   straus_pos over the wide tables of kind 1, sp < 2^128
+// tabs: 16 cached entries per lane (V 0 .. 2); ktab: KT_STRIDE entries per lane (V 3, 4),
+// WT_STRIDE entries per lane (V 6).
 template <int BUILD, int V>
 __global__ void __launch_bounds__(NT) k_selftest_msm(size_t n, const uint8_t* __restrict__ Penc,
                                                      const uint8_t* __restrict__ Qenc, const uint8_t* __restrict__ sp,
@@ -249,6 +251,12 @@ __global__ void __launch_bounds__(NT) k_selftest_msm(size_t n, const uint8_t* __
     sc_recode65536(w2, s2);
     straus_comb<8, true>(x, ktab + i * KT_STRIDE, w1, comb, w2);
     ge_p1p1_to_p2(R, x);
+  } else if constexpr (V == 6) {
+    load_words(s1, sp + 32 * i, 8);
+    load_words(s2, sb + 32 * i, 8);
+    sc_recode65536(w2, s2);
+    straus_pos(x, ktab + i * WT_STRIDE, s1, comb, w2);
+    ge_p1p1_to_p2(R, x);
   } else {
     load_words(pk, Penc + 32 * i, 8);
     load_words(s1, sp + 32 * i, 8);
@@ -283,6 +291,7 @@ void ST_LAUNCH(msm)(hipStream_t stream, int variant, size_t n, const uint8_t* P,
     ST_MSM(3);
     ST_MSM(4);
     ST_MSM(5);
+    ST_MSM(6);
     default: break;
   }
 #undef ST_MSM

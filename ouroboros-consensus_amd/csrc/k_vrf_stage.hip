@@ -32,7 +32,7 @@ __global__ void __launch_bounds__(NT, LB_VRF_V) k_vrf_v(size_t n, size_t i0, siz
 
 // stage F: pool lookup and key hash (Praos.hs:533-541), U + challenge + beta, the output
 // check and the range extension -- the same results vrf_item writes in header mode
-template <bool CACHED>
+template <int CACHED>
 __device__ __forceinline__ void vrf_fin_item(const VrfIn& a, size_t i, size_t stride, const uint4* __restrict__ mid,
                                              const ge_niels* __restrict__ btab, const ge_cached* __restrict__ ktab,
                                              const uint32_t* __restrict__ kinfo) {
@@ -100,6 +100,23 @@ __global__ void __launch_bounds__(NT, LB_VRF_J) k_vrf_fin(size_t stride, const u
   vrf_fin_item<true>(a, i, stride, mid, comb, ktab + e * KT_STRIDE, kinfo + 9 * e);
 }
 
+// keys of the wide tier (their own hit list): U from the key's positional tables, no doublings
+__global__ void __launch_bounds__(NT, LB_VRF_J) k_vrf_fin_w(size_t stride, const uint32_t* __restrict__ list,
+                                                          const uint32_t* __restrict__ count,
+                                                          const int32_t* __restrict__ item_entry,
+                                                          const int32_t* __restrict__ entry_wide,
+                                                          const ge_cached* __restrict__ wtab,
+                                                          const uint32_t* __restrict__ kinfo,
+                                                          const ge_niels* __restrict__ comb, VrfIn a,
+                                                          const uint4* __restrict__ mid) {
+  const size_t items = *count;
+  const size_t t = (size_t)blockIdx.x * NT + threadIdx.x;
+  if (t >= items) return;
+  const size_t i = list[t];
+  const size_t e = (size_t)item_entry[i];
+  vrf_fin_item<2>(a, i, stride, mid, comb, wtab + (size_t)entry_wide[e] * WT_STRIDE, kinfo + 9 * e);
+}
+
 // uncached keys (the miss list, or every header): U on a per-lane chain
 __global__ void __launch_bounds__(NT, LB_VRF_J) k_vrf_fin_nc(size_t n, const uint32_t* __restrict__ list,
                                                            const uint32_t* __restrict__ count,
@@ -132,6 +149,27 @@ __global__ void __launch_bounds__(NT, LB_VRF_F) k_vrf_u(size_t stride, const uin
   uint32_t pr[20];
   load_words(pr, vrf_proof + 80 * i, 20);
   vrf_u_core<true>(mid, stride, i, nullptr, pr + 8, pr + 12, comb, nullptr, ktab + e * KT_STRIDE, kinfo + 9 * e);
+}
+
+// U of a key of the wide tier (their own hit list): the key's positional tables
+__global__ void __launch_bounds__(NT, LB_VRF_F) k_vrf_u_w(size_t stride, const uint32_t* __restrict__ list,
+                                                        const uint32_t* __restrict__ count,
+                                                        const int32_t* __restrict__ item_entry,
+                                                        const int32_t* __restrict__ entry_wide,
+                                                        const ge_cached* __restrict__ wtab,
+                                                        const uint32_t* __restrict__ kinfo,
+                                                        const ge_niels* __restrict__ comb,
+                                                        const uint8_t* __restrict__ vrf_proof, uint4* __restrict__ mid,
+                                                        int prio) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)*count) return;
+  wave_setprio(prio);
+  const size_t i = list[t];
+  const size_t e = (size_t)item_entry[i];
+  uint32_t pr[20];
+  load_words(pr, vrf_proof + 80 * i, 20);
+  vrf_u_core<2>(mid, stride, i, nullptr, pr + 8, pr + 12, comb, nullptr, wtab + (size_t)entry_wide[e] * WT_STRIDE,
+                kinfo + 9 * e);
 }
 
 // U of an uncached key (the miss list, or every header): a per-lane chain; vt = an 8-entry
@@ -332,12 +370,15 @@ void launch_vrf_fin(hipStream_t stream, size_t n, const uint32_t* list, const ui
                     const uint8_t* vrf_proof, const uint32_t* pool_hash, const uint32_t* pool_vrf,
                     const int32_t* pool_map, uint32_t npools, int check_output, uint16_t* bits, int32_t* pool_idx,
                     int32_t* pool_sorted_idx, uint8_t* beta_out, uint8_t* leader_out, uint8_t* nonce_out,
-                    ge_cached* tabs, const void* mid) {
+                    ge_cached* tabs, const void* mid, const int32_t* entry_wide) {
   const VrfIn a = vrf_in(cold_vk, vrf_vk, vrf_out, vrf_proof, nullptr, nullptr, 0, nullptr, pool_hash, pool_vrf,
                          pool_map, npools, check_output, bits, pool_idx, pool_sorted_idx, beta_out, leader_out,
                          nonce_out, tabs);
   const dim3 g((unsigned)((n + NT - 1) / NT));
-  if (ktab)
+  if (entry_wide)
+    hipLaunchKernelGGL(k_vrf_fin_w, g, dim3(NT), 0, stream, n, list, count, item_entry, entry_wide, ktab, kinfo, comb,
+                       a, (const uint4*)mid);
+  else if (ktab)
     hipLaunchKernelGGL(k_vrf_fin, g, dim3(NT), 0, stream, n, list, count, item_entry, ktab, kinfo, comb, a,
                        (const uint4*)mid);
   else
@@ -346,10 +387,13 @@ void launch_vrf_fin(hipStream_t stream, size_t n, const uint32_t* list, const ui
 void launch_vrf_u(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count, const int32_t* item_entry,
                   const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* comb, const ge_niels* gbtab,
                   const uint8_t* vrf_vk, const uint8_t* vrf_proof, ge_cached* utabs, void* mid, int ilp4,
-                  int prio) {
+                  int prio, const int32_t* entry_wide) {
   const dim3 g((unsigned)((n + NT - 1) / NT));
   const unsigned bs = lat_block(n);
-  if (ktab && ilp4)
+  if (entry_wide)
+    hipLaunchKernelGGL(k_vrf_u_w, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, stream, n, list, count, item_entry,
+                       entry_wide, ktab, kinfo, comb, vrf_proof, (uint4*)mid, prio);
+  else if (ktab && ilp4)
     launch_vrf_u4(stream, n, list, count, item_entry, ktab, kinfo, comb, vrf_proof, mid, prio);
   else if (ktab)
     hipLaunchKernelGGL(k_vrf_u, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, stream, n, list, count, item_entry,

@@ -42,13 +42,23 @@ void launch_key_insert(dim3 grid, dim3 block, hipStream_t stream, size_t n, cons
 // stored entries' hit-list ranges (after the new keys'), from their uses this run
 void launch_key_store_ranges(hipStream_t stream, uint32_t entries, const uint32_t* scnt, uint32_t* spos,
                              uint32_t* counters);
+// The wide tier of a key cache (k_keys.hip; VRF keys): keys used >= min_uses times (0: tier off),
+// at most cap of them; entry_wide / wide_ent: entry <-> wide index; wcnt: [0] wide keys claimed,
+// [1] wide hits, [2] ranges handed out; hit: the wide keys' hit list; wtab: WT_STRIDE entries per key;
+// wbase: WT_POS entries per key (the position bases, between the two passes of the precompute).
+struct KeyWide {
+  uint32_t min_uses = 0, cap = 0;
+  int32_t* entry_wide = nullptr;
+  uint32_t *wide_ent = nullptr, *wcnt = nullptr, *hit = nullptr;
+  ge_cached *wtab = nullptr, *wbase = nullptr;
+};
 void launch_key_assign(dim3 grid, dim3 block, hipStream_t stream, uint32_t cap, const uint32_t* slot_rep,
                        const uint32_t* slot_cnt, uint32_t min_count, uint32_t max_entries, int32_t* slot_entry,
-                       uint32_t* entry_rep, uint32_t* entry_pos, uint32_t* counters);
+                       uint32_t* entry_rep, uint32_t* entry_pos, uint32_t* counters, const KeyWide& w = KeyWide());
 void launch_key_partition(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint32_t* list,
                           const uint32_t* count, const int32_t* item_slot, const int32_t* slot_entry,
                           int32_t* item_entry, uint32_t* entry_pos, uint32_t* hit_list, uint32_t* miss_list,
-                          uint32_t* counters, uint32_t* spos);
+                          uint32_t* counters, uint32_t* spos, const KeyWide& w = KeyWide());
 void launch_ocert_dedup(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint8_t* cold, const uint8_t* hot,
                         const uint64_t* on, const uint64_t* oc, const uint8_t* sig, uint32_t mask, uint32_t* slot_rep,
                         uint32_t* item_rep, uint32_t* reps, uint32_t* counters);
@@ -59,7 +69,8 @@ void launch_ocert_fanout(dim3 grid, dim3 block, hipStream_t stream, size_t n, co
 void launch_key_precompute(int kind, hipStream_t stream, const uint32_t* counters, uint32_t max_entries,
                            const uint32_t* entry_rep, const uint8_t* keys, ge_cached* ktab, uint32_t* kinfo,
                            int wave_prio, const uint32_t* base, uint32_t span,
-                           int mode);                      // 1: the chain from the ILP-4 build (k_keys4.hip)
+                           int mode,                       // 1: the chain from the ILP-4 build (k_keys4.hip)
+                           const KeyWide& w = KeyWide());
 void launch_key_precompute4(int kind, hipStream_t stream, const uint32_t* counters, uint32_t max_entries,
                             const uint32_t* entry_rep, const uint8_t* keys, ge_cached* ktab, uint32_t* kinfo,
                             int wave_prio, const uint32_t* base, uint32_t span);
@@ -153,14 +164,16 @@ void launch_vrf_fin(hipStream_t stream, size_t n, const uint32_t* list, const ui
                     const uint8_t* vrf_proof, const uint32_t* pool_hash, const uint32_t* pool_vrf,
                     const int32_t* pool_map, uint32_t npools, int check_output, uint16_t* bits, int32_t* pool_idx,
                     int32_t* pool_sorted_idx, uint8_t* beta_out, uint8_t* leader_out, uint8_t* nonce_out,
-                    ge_cached* tabs, const void* mid);
+                    ge_cached* tabs, const void* mid,
+                    const int32_t* entry_wide = nullptr);   // list = a wide hit list, ktab = the wide tables
 // three-kernel VRF: stage U (cached: ktab != null, k_vrf_u over the hit list; uncached: k_vrf_u_nc
 // over list[0 .. *count) or all n, 8-entry lane tables utabs) and the join over all n
 void launch_vrf_u(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count, const int32_t* item_entry,
                   const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* comb, const ge_niels* gbtab,
                   const uint8_t* vrf_vk, const uint8_t* vrf_proof, ge_cached* utabs, void* mid,
                   int ilp4 = 0,                            // cached keys: the ILP-4 build (k_vrf_v4.hip k_vrf_u4)
-                  int prio = 0);                           // cached keys: waves at s_setprio <prio>
+                  int prio = 0,                            // cached keys: waves at s_setprio <prio>
+                  const int32_t* entry_wide = nullptr);    // list = a wide hit list, ktab = the wide tables
 void launch_vrf_u4(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count, const int32_t* item_entry,
                    const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* comb, const uint8_t* vrf_proof,
                    void* mid, int prio = 0);

@@ -112,6 +112,9 @@ static constexpr size_t PIPE_MIN_CHUNK = 49152;     // headers per chunk at leas
 // Batches below this many headers (a strong-scaling shard of an epoch over 8 GPUs is 54k) leave
 // most wave slots empty and run latency-bound (PRAOS_VRF_PRIO = -1 raises stage V there)
 static constexpr size_t SMALL_BATCH = 80000;
+static constexpr size_t WIDE_BATCH = 300000;           // the VRF key cache's wide tier: batches from this size on
+static constexpr uint32_t WIDE_MIN_USES = 43;          // ... and keys with this many uses: the break-even of
+                                                       // W_KEY_VRF_WIDE against W_VRF_F_CK_WIDE (tools/workmodel.py)
 // below this many headers the key precomputes run at raised wave priority (PRAOS_KEY_PRIO -1):
 // they head the cached chains (profiles/r04/bb: 96k 3.66 -> 3.57 ms, 108k 4.14 -> 3.83, 160k
 // 5.19 -> 4.88, 300k 8.83 -> 8.67; 432k within noise)
@@ -267,6 +270,17 @@ struct praos_ctx {
   }
   int vrf3 = -1;                                       // VRF as V | U | join (1), V | U + join (0), -1 auto:
                                                        // the three-kernel form below 300k headers (latency)
+  // wide tier of the VRF key cache (praos_set_vrf_wide / PRAOS_VRF_WIDE): a key with this many uses
+  // in the batch gets positional tables (k_keys.hip); 0 off; -1 auto: WIDE_MIN_USES, the modelled
+  // break-even, in batches from WIDE_BATCH headers on (below it the longer key precompute is on the
+  // step's critical path and few keys reach the threshold)
+  int vrf_wide = -1;
+  int wide_prio = 1;                                   // the VRF key precompute at raised wave priority when it
+                                                       // builds wide tables (PRAOS_WIDE_PRIO 1 / 0)
+  int vrf_wide_cap = 4096;                             // wide keys per batch at most (PRAOS_VRF_WIDE_CAP)
+  uint32_t wide_min(size_t n) const {
+    return vrf_wide > 0 ? (uint32_t)vrf_wide : (vrf_wide < 0 && n >= WIDE_BATCH ? WIDE_MIN_USES : 0u);
+  }
   // chunked stored-bytes pipeline (praos_verify_header_bytes): a copy stream, per-chunk
   // events and persistent chunk batches (reused while they are large enough)
   int pipeline = 0;                                    // PRAOS_OPT_PIPELINE (0 = auto)
@@ -553,6 +567,10 @@ struct praos_batch {
     const uint32_t* ebase = nullptr;
     uint32_t emax = 0;
     int store = -1;
+    // the wide tier (VRF keys): buffers for wide_alloc keys, allocated when a run first uses it;
+    // wide.min_uses = this run's threshold (0: the tier is off and every hit is in `hit`)
+    KeyWide wide;
+    uint32_t wide_alloc = 0;
   } kc[3];                       // [2] KES leaf keys
   uint8_t* kes_leaf = nullptr;   // n*32: the leaf key of each header's KES signature
   bool kc_used = false;
@@ -609,6 +627,7 @@ struct praos_batch {
 };
 
 static constexpr size_t KT_BYTES = 16 * 8 * 4 * 32; // per cached key: 16 tables x 8 cached points
+static constexpr size_t WT_BYTES = 22 * 32 * 4 * 32; // per wide key: 22 positions x 32 cached points (WT_STRIDE)
 static constexpr uint32_t KC_MAX_ENTRIES = 1u << 20;   // a key used twice already pays for its tables
 
 #define HIPCHK(ctx, x)                                                                    \
@@ -700,6 +719,9 @@ static bool open_streams(praos_ctx* c) {
   if (const char* e = std::getenv("PRAOS_KES_DEDUP")) c->kes_dedup = std::atoi(e);
   if (const char* e = std::getenv("PRAOS_POOL_KEYS")) (void)praos_set_option(c, PRAOS_OPT_POOL_KEYS, std::atoi(e));
   if (const char* e = std::getenv("PRAOS_VRF_KEYS_FIRST")) c->vrf_keys_first = std::atoi(e);
+  if (const char* e = std::getenv("PRAOS_VRF_WIDE")) (void)praos_set_vrf_wide(c, std::atoi(e), c->vrf_wide_cap);
+  if (const char* e = std::getenv("PRAOS_WIDE_PRIO")) c->wide_prio = std::atoi(e);
+  if (const char* e = std::getenv("PRAOS_VRF_WIDE_CAP")) (void)praos_set_vrf_wide(c, c->vrf_wide, std::atoi(e));
   if (const char* e = std::getenv("PRAOS_PRE_JOIN")) c->pre_join = std::atoi(e);
   if (const char* e = std::getenv("PRAOS_V_MAIN")) c->v_main = std::atoi(e);
   if (const char* e = std::getenv("PRAOS_STREAM_CHUNK_V")) c->stream_chunk_v = std::atoi(e);
@@ -1369,8 +1391,8 @@ static bool ensure_pks(praos_ctx* c, int t, hipStream_t st) {
   return true;
 }
 
-static int kc_lists(praos_ctx* c, praos_batch::KeyCache& k, size_t n, const uint8_t* keys, hipStream_t st,
-                    const uint32_t* list, const uint32_t* count, int which) {
+static int kc_lists(praos_ctx* c, praos_batch* b, praos_batch::KeyCache& k, size_t n, const uint8_t* keys,
+                    hipStream_t st, const uint32_t* list, const uint32_t* count, int which) {
   int min_uses = c->kc_min[which] > 0 ? c->kc_min[which] : c->keycache;
   // small batches: no KES leaf key is cached (every item a miss, KES_NOCACHE_BATCH); the batch size
   // is the caller's n (the lists of the KES pass run over every header)
@@ -1396,21 +1418,49 @@ static int kc_lists(praos_ctx* c, praos_batch::KeyCache& k, size_t n, const uint
     k.ebase = ps->base; k.store = which;
     min_uses = 1;
   }
+  // wide tier: VRF keys of this batch's own cache (the pool-key store's entries stay in the chunk tier)
+  k.wide.min_uses = 0;
+  if (which == 1 && !ps && c->wide_min(n) > 0) {
+    const uint32_t wmin = std::max(c->wide_min(n), (uint32_t)std::max(min_uses, 1));
+    const uint32_t need = (uint32_t)std::min<size_t>((size_t)std::max(c->vrf_wide_cap, 1), n / wmin + 1);
+    // allocated by the first run that uses the tier, for the batch's capacity, and kept; a later run
+    // that needs more keys allocates a larger set (the smaller one stays owned until the batch is freed)
+    if (k.wide_alloc < need) {
+      const size_t cap_n = std::max(n, b->cap_n);
+      const uint32_t wcap = (uint32_t)std::min<size_t>((size_t)std::max(c->vrf_wide_cap, 1), cap_n / wmin + 1);
+      KeyWide w;
+      if (dalloc(b, &w.entry_wide, 4 * (size_t)k.max_entries) != hipSuccess ||
+          dalloc(b, &w.wide_ent, 4 * (size_t)wcap) != hipSuccess || dalloc(b, &w.wcnt, 16) != hipSuccess ||
+          dalloc(b, &w.hit, 4 * cap_n) != hipSuccess ||
+          dalloc(b, (uint8_t**)&w.wtab, WT_BYTES * (size_t)wcap) != hipSuccess ||
+          dalloc(b, (uint8_t**)&w.wbase, WT_BYTES / 32 * (size_t)wcap) != hipSuccess)
+        return PRAOS_E_OOM;
+      k.wide = w;
+      k.wide_alloc = wcap;
+    }
+    k.wide.min_uses = wmin;
+    k.wide.cap = need;
+    HIPCHK(c, hipMemsetAsync(k.wide.wcnt, 0, 16, st));
+  }
   launch_key_insert(g, blk, st, n, list, count, keys, k.cap - 1, k.slot_rep, k.slot_cnt, k.item_slot,
                     ps ? ps->pentry : nullptr, ps ? ps->pkey : nullptr, ps ? ps->slots - 1 : 0u,
                     ps ? ps->scnt : nullptr);
   launch_key_assign(dim3(nblocks(k.cap, NT)), blk, st, k.cap, k.slot_rep, k.slot_cnt, (uint32_t)min_uses,
-                    k.emax, k.slot_entry, k.erep, k.epos, k.counters);
+                    k.emax, k.slot_entry, k.erep, k.epos, k.counters, k.wide);
   if (ps) launch_key_store_ranges(st, ps->cap, ps->scnt, ps->spos, k.counters);
   launch_key_partition(g, blk, st, n, list, count, k.item_slot, k.slot_entry, k.item_entry, k.epos, k.hit, k.miss,
-                       k.counters, ps ? ps->spos : nullptr);
+                       k.counters, ps ? ps->spos : nullptr, k.wide);
   return PRAOS_OK;
 }
 static void kc_precompute(praos_ctx* c, praos_batch::KeyCache& k, const uint8_t* keys, int kind, hipStream_t st, size_t n) {
-  const int prio = c->key_wave_prio > 0 || (c->key_wave_prio < 0 && n < KEY_PRIO_BATCH);
+  // (with a wide tier the tables' chain -- decode, chunk bases, position bases, tables -- is longer
+  // than stage V leaves room for in a large batch, and the U chains wait for it: raised wave
+  // priority, as in a small batch; 432k 10.24 -> 10.09 ms, profiles/r07_wide_ab.json)
+  const bool wide = k.wide.min_uses != 0;
+  const int prio = c->key_wave_prio > 0 || (c->key_wave_prio < 0 && (n < KEY_PRIO_BATCH || (wide && c->wide_prio)));
   if (k.store < 0) {
     launch_key_precompute(kind, st, k.counters, k.max_entries, k.entry_rep, keys, k.ktab, k.kinfo, prio, nullptr,
-                          k.max_entries, c->key_mode(n));
+                          k.max_entries, c->key_mode(n), k.wide);
     return;
   }
   praos_ctx::PoolKeyStore& ps = c->pks[k.store];
@@ -1549,7 +1599,7 @@ static int batch_run_impl(praos_ctx* c, praos_batch* b) {
   };
   auto keycache_lists = [&](praos_batch::KeyCache& k, const uint8_t* keys, hipStream_t st,
                             const uint32_t* list = nullptr, const uint32_t* count = nullptr) -> int {
-    return kc_lists(c, k, n, keys, st, list, count, (int)(&k - b->kc));
+    return kc_lists(c, b, k, n, keys, st, list, count, (int)(&k - b->kc));
   };
   auto keycache_precompute = [&](praos_batch::KeyCache& k, const uint8_t* keys, int kind, hipStream_t st) {
     kc_precompute(c, k, keys, kind, st, n);
@@ -1576,6 +1626,9 @@ static int batch_run_impl(praos_ctx* c, praos_batch* b) {
     keycache_precompute(k, b->vrf_vk, 1, sv);
     launch_vrf_u(sv, n, k.hit, k.counters + 1, k.item_entry, k.kt, k.ki, c->bcomb16, c->btab, b->vrf_vk,
                  b->vrf_proof, b->tab_vrfu, b->vrf_mid, c->use_u4(n), 0);
+    if (k.wide.min_uses)
+      launch_vrf_u(sv, n, k.wide.hit, k.wide.wcnt + 1, k.item_entry, k.wide.wtab, k.ki, c->bcomb16, c->btab,
+                   b->vrf_vk, b->vrf_proof, b->tab_vrfu, b->vrf_mid, 0, 0, k.wide.entry_wide);
     // (v_main 2: the main stream waits for u_ev itself, before the join)
     if (sm_[2] != sv && !(v_main && vm_mode == 2)) HIPCHK(c, hipStreamWaitEvent(sv, c->u_ev, 0));
     vrf_keys_queued = true;
@@ -1735,9 +1788,13 @@ static int batch_run_impl(praos_ctx* c, praos_batch* b) {
                      proof[q], b->tab_vrfu, mid[q]);
       if (sm_[2] != sv) HIPCHK(c, hipEventRecord(c->u_ev, sm_[2]));
       keycache_precompute(k, b->vrf_vk, 1, sv);
-      for (int q = 0; q < 2; q++)
+      for (int q = 0; q < 2; q++) {
         launch_vrf_u(sv, n, k.hit, k.counters + 1, k.item_entry, k.kt, k.ki, c->bcomb16, c->btab, b->vrf_vk,
                      proof[q], b->tab_vrfu, mid[q], c->use_u4(n));
+        if (k.wide.min_uses)
+          launch_vrf_u(sv, n, k.wide.hit, k.wide.wcnt + 1, k.item_entry, k.wide.wtab, k.ki, c->bcomb16, c->btab,
+                       b->vrf_vk, proof[q], b->tab_vrfu, mid[q], 0, 0, k.wide.entry_wide);
+      }
       if (sm_[2] != sv) HIPCHK(c, hipStreamWaitEvent(sv, c->u_ev, 0));
     } else {
       for (int q = 0; q < 2; q++)
@@ -1775,11 +1832,13 @@ static int batch_run_impl(praos_ctx* c, praos_batch* b) {
       if (b->v_done) HIPCHK(c, hipStreamWaitEvent(st, c->v2_ev, 0));
       return PRAOS_OK;
     };
-    auto fin = [&](hipStream_t st, const uint32_t* list, const uint32_t* count, const praos_batch::KeyCache* k) {
-      launch_vrf_fin(st, n, list, count, k ? k->item_entry : nullptr, k ? k->kt : nullptr, k ? k->ki : nullptr,
-                     c->bcomb16, c->btab, b->cold_vk, b->vrf_vk, b->vrf_out, b->vrf_proof, c->d_pool_hash,
-                     c->d_pool_vrf, c->d_pool_map, c->npools, (int)P.vrf_check_output, bv, b->pool_idx,
-                     b->pool_sorted, b->beta, b->leader, b->nonce, b->tab_vrf, b->vrf_mid);
+    auto fin = [&](hipStream_t st, const uint32_t* list, const uint32_t* count, const praos_batch::KeyCache* k,
+                   bool wide = false) {
+      launch_vrf_fin(st, n, list, count, k ? k->item_entry : nullptr, k ? (wide ? k->wide.wtab : k->kt) : nullptr,
+                     k ? k->ki : nullptr, c->bcomb16, c->btab, b->cold_vk, b->vrf_vk, b->vrf_out, b->vrf_proof,
+                     c->d_pool_hash, c->d_pool_vrf, c->d_pool_map, c->npools, (int)P.vrf_check_output, bv, b->pool_idx,
+                     b->pool_sorted, b->beta, b->leader, b->nonce, b->tab_vrf, b->vrf_mid,
+                     wide ? k->wide.entry_wide : nullptr);
     };
     auto stage_u = [&](hipStream_t st, const uint32_t* list, const uint32_t* count, const praos_batch::KeyCache* k) {
       launch_vrf_u(st, n, list, count, k ? k->item_entry : nullptr, k ? k->kt : nullptr, k ? k->ki : nullptr,
@@ -1820,8 +1879,21 @@ static int batch_run_impl(praos_ctx* c, praos_batch* b) {
       if (r != PRAOS_OK) return r;
       fin(sm_[2], k.miss, k.counters + 2, nullptr);
       keycache_precompute(k, b->vrf_vk, 1, sv);
-      if ((r = after_v(sv)) != PRAOS_OK) return r;
-      fin(sv, k.hit, k.counters + 1, &k);
+      if (k.wide.min_uses && sm_[2] != sv) {
+        // two hit lists, and this is the step's tail: the chunk tier's few waves run beside the wide
+        // tier's on the miss stream (which waited for stage V above) once the tables exist, instead
+        // of trailing them as a launch of their own (432k: 10.106 -> 10.041 ms, medians of six
+        // alternating runs, lower in every pair; profiles/r07_wide_ab.json)
+        HIPCHK(c, hipEventRecord(c->u_ev, sv));
+        HIPCHK(c, hipStreamWaitEvent(sm_[2], c->u_ev, 0));
+        fin(sm_[2], k.hit, k.counters + 1, &k);
+        if ((r = after_v(sv)) != PRAOS_OK) return r;
+        fin(sv, k.wide.hit, k.wide.wcnt + 1, &k, true);
+      } else {
+        if ((r = after_v(sv)) != PRAOS_OK) return r;
+        if (k.wide.min_uses) fin(sv, k.wide.hit, k.wide.wcnt + 1, &k, true);
+        fin(sv, k.hit, k.counters + 1, &k);
+      }
     } else {
       const int r = after_v(sv);
       if (r != PRAOS_OK) return r;
@@ -2280,7 +2352,7 @@ int praos_verify_pbft_headers(praos_ctx* c, const praos_header_bytes* in, const 
     if (cached) {
       const bool pk = c->pk_on;
       c->pk_on = false;                                  // the batch's own entries, not the pool-key store
-      const int r = kc_lists(c, k, n, d_keys, st, d_vlist, d_vcount, 0);
+      const int r = kc_lists(c, b, k, n, d_keys, st, d_vlist, d_vcount, 0);
       if (r == PRAOS_OK) kc_precompute(c, k, d_keys, 0, st, n);
       c->pk_on = pk;
       if (r != PRAOS_OK) return r;
@@ -2582,7 +2654,26 @@ int praos_batch_stats(praos_ctx* c, praos_batch* b, uint32_t out[9]) {
     out[3 * t] = std::min(cnt[0], b->kc[t].emax ? b->kc[t].emax : b->kc[t].max_entries);
     out[3 * t + 1] = cnt[1];
     out[3 * t + 2] = cnt[2];
+    if (b->kc[t].wide.min_uses) {      // the wide tier's hits are hits too
+      uint32_t w[4] = {0, 0, 0, 0};
+      HIPCHK(c, hipMemcpy(w, b->kc[t].wide.wcnt, 16, hipMemcpyDeviceToHost));
+      out[3 * t + 1] += w[1];
+    }
   }
+  return PRAOS_OK;
+}
+
+int praos_batch_wide_stats(praos_ctx* c, praos_batch* b, uint32_t out[2]) {
+  if (!c || !b || !out) return PRAOS_E_ARG;
+  out[0] = out[1] = 0;
+  const praos_batch::KeyCache& k = b->kc[1];
+  if (!b->kc_used || !k.wide.min_uses) return PRAOS_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  uint32_t w[4] = {0, 0, 0, 0};
+  HIPCHK(c, hipMemcpy(w, k.wide.wcnt, 16, hipMemcpyDeviceToHost));
+  out[0] = std::min(w[0], k.wide.cap);
+  out[1] = w[1];
   return PRAOS_OK;
 }
 
@@ -2612,6 +2703,13 @@ int praos_set_option(praos_ctx* c, int opt, int value) {
     return PRAOS_OK;
   }
   return PRAOS_E_ARG;
+}
+
+int praos_set_vrf_wide(praos_ctx* c, int min_uses, int max_keys) {
+  if (!c) return PRAOS_E_ARG;
+  c->vrf_wide = min_uses < 0 ? -1 : min_uses;
+  c->vrf_wide_cap = max_keys < 1 ? 4096 : std::min(max_keys, 1 << 16);
+  return PRAOS_OK;
 }
 
 int praos_batch_sync(praos_ctx* c) {
@@ -4501,13 +4599,15 @@ static bool scalars_below(const uint8_t* s, size_t n, int bits) {
 
 int praos_debug_msm(praos_ctx* c, int variant, int build, size_t n, const uint8_t* P, const uint8_t* Q,
                     const uint8_t* sp, const uint8_t* sq, const uint8_t* sb, uint8_t* out) {
-  if (!c || !out || variant < 0 || variant > 5 || build < 0 || build > 1 || !P || !sp) return PRAOS_E_ARG;
-  const bool use_q = variant == 2, use_b = variant != 2 && variant != 5, cached = variant == 3 || variant == 4;
+  if (!c || !out || variant < 0 || variant > 6 || build < 0 || build > 1 || !P || !sp) return PRAOS_E_ARG;
+  const bool use_q = variant == 2, use_b = variant != 2 && variant != 5;
+  const bool wide = variant == 6, cached = variant == 3 || variant == 4 || wide;
+  if (wide && n > 4096) return PRAOS_E_ARG;            // 88 KB of tables per lane
   if ((use_q && (!Q || !sq)) || (use_b && !sb)) return PRAOS_E_ARG;
   if (n == 0) return PRAOS_OK;
   if (n > (1u << 20)) return PRAOS_E_ARG;
   // the recodings' documented ranges (scalarmult.hpp)
-  if (!scalars_below(sp, n, (variant == 1 || variant == 4) ? 128 : 253)) return PRAOS_E_ARG;
+  if (!scalars_below(sp, n, (variant == 1 || variant == 4 || wide) ? 128 : 253)) return PRAOS_E_ARG;
   if (use_q && !scalars_below(sq, n, 128)) return PRAOS_E_ARG;
   if (use_b && !scalars_below(sb, n, 253)) return PRAOS_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
@@ -4535,9 +4635,19 @@ int praos_debug_msm(praos_ctx* c, int variant, int build, size_t n, const uint8_
     auto dcnt = s.up(cnt, sizeof cnt);
     auto kinfo = s.zeros<uint32_t>(9 * 4 * n);
     ktab = s.zeros<ge_cached>(KT_BYTES * n);
+    KeyWide w;                                           // variant 6: every key in the wide tier, wide index = entry
+    if (wide) {
+      w.min_uses = 1;
+      w.cap = (uint32_t)n;
+      w.wide_ent = drep;
+      w.wcnt = dcnt;
+      w.wtab = s.zeros<ge_cached>(WT_BYTES * n);
+      w.wbase = s.zeros<ge_cached>(WT_BYTES / 32 * n);
+    }
     if (!s.ok) return PRAOS_E_OOM;
     launch_key_precompute(variant == 3 ? 0 : 1, c->stream, dcnt, (uint32_t)n, drep, dP, ktab, kinfo, 0, nullptr,
-                          (uint32_t)n, build);
+                          (uint32_t)n, build, w);
+    if (wide) ktab = w.wtab;
   } else {
     tabs = s.zeros<ge_cached>(LT_VRF_B * n);
   }

@@ -551,9 +551,10 @@ FE_INLINE void vrf_v_core(uint4* __restrict__ mid, size_t stride, size_t i, cons
 }
 
 // Stage F: U, the batched inversion of U.Z V.Z (8 Gamma).Z H.Z, the challenge, beta.
-// CACHED: kinfo / ktab of k_keys.hip and btab = the global radix-2^16 comb; otherwise Y is
-// decoded per lane ({1..8}(-Y) in vt) and btab = the LDS tables {B, 2^128 B}.
-template <bool CACHED>
+// CACHED: kinfo / ktab of k_keys.hip and btab = the global radix-2^16 comb (1: ktab = the key's
+// chunk tables; 2: its wide tables, straus_pos); otherwise Y is decoded per lane ({1..8}(-Y) in
+// vt) and btab = the LDS tables {B, 2^128 B}.
+template <int CACHED>
 FE_INLINE bool vrf_fin_core(uint32_t beta[16], bool& gamma_ok, const uint4* __restrict__ mid, size_t stride,
                             size_t i, const uint32_t pk[8], const uint32_t c4[4], const uint32_t s8[8],
                             const ge_niels* __restrict__ btab, ge_cached* __restrict__ vt,
@@ -571,7 +572,8 @@ FE_INLINE bool vrf_fin_core(uint32_t beta[16], bool& gamma_ok, const uint4* __re
     ok = (kinfo[0] & 1u) != 0;
     sc_recode65536(sw, s);
     ge_p1p1 x;
-    straus_comb<8, true>(x, ktab, cw, btab, sw);
+    if constexpr (CACHED == 2) straus_pos(x, ktab, c4, btab, sw);
+    else straus_comb<8, true>(x, ktab, cw, btab, sw);
     ge_p1p1_to_p2(U, x);
   } else {
     ge_p3 Y;
@@ -625,9 +627,10 @@ FE_INLINE bool vrf_fin_core(uint32_t beta[16], bool& gamma_ok, const uint4* __re
 }
 
 // Stage U: U = [s]B - [c]Y into planes VRF_MID_U.., vrf_validate_key into VRF_MID_KEY.
-// CACHED: kinfo / ktab of k_keys.hip and btab = the global radix-2^16 comb; otherwise Y is
-// decoded per lane ({1..8}(-Y) in the lane's 8-entry table vt) and btab = LDS {B, 2^128 B}.
-template <bool CACHED>
+// CACHED: kinfo / ktab of k_keys.hip and btab = the global radix-2^16 comb (1: chunk tables,
+// 2: wide tables); otherwise Y is decoded per lane ({1..8}(-Y) in the lane's 8-entry table vt)
+// and btab = LDS {B, 2^128 B}.
+template <int CACHED>
 FE_INLINE void vrf_u_core(uint4* __restrict__ mid, size_t stride, size_t i, const uint32_t pk[8], const uint32_t c4[4],
                           const uint32_t s8[8], const ge_niels* __restrict__ btab, ge_cached* __restrict__ vt,
                           const ge_cached* __restrict__ ktab, const uint32_t* __restrict__ kinfo) {
@@ -643,7 +646,8 @@ FE_INLINE void vrf_u_core(uint4* __restrict__ mid, size_t stride, size_t i, cons
   if constexpr (CACHED) {
     ok = (kinfo[0] & 1u) != 0;
     sc_recode65536(sw, s);
-    straus_comb<8, true>(x, ktab, cw, btab, sw);
+    if constexpr (CACHED == 2) straus_pos(x, ktab, c4, btab, sw);
+    else straus_comb<8, true>(x, ktab, cw, btab, sw);
   } else {
     ge_p3 Y;
     ok = !ge_has_small_order(pk);

@@ -353,6 +353,94 @@ FE_INLINE void straus_comb(ge_p1p1& out, const ge_cached* __restrict__ ktab, con
   out = x;
 }
 
+// ---------------------------------------------------------------- wide (positional) tier
+// A VRF key used by dozens of headers of a batch (k_keys.hip: the wide tier) holds a table
+// for every digit position of the challenge c < 2^128: WT_POS tables {1..32} 64^k P, so
+// [c]P is WT_POS additions and no doubling.  Digits: w = c + sum_k 32 * 64^k (exact: w < 2^132);
+// digit k is the 6-bit field k of w minus 32, in [-32, 31]; digit 21 holds only the
+// recoding carry and bits 126-127 of c.
+#define WT_POS 22                      // digit positions
+#define WT_N 32                        // entries per position
+#define WT_STRIDE (WT_POS * WT_N)      // ge_cached entries per wide key (88 KB)
+
+FE_INLINE void sc_recode64(uint32_t w[5], const uint32_t c[4]) {
+  uint32_t cy = 0;
+  w[0] = addc(c[0], 0x20820820u, cy, &cy);   // bit 6k + 5 of every field k < 22
+  w[1] = addc(c[1], 0x08208208u, cy, &cy);
+  w[2] = addc(c[2], 0x82082082u, cy, &cy);
+  w[3] = addc(c[3], 0x20820820u, cy, &cy);
+  w[4] = 8u + cy;
+}
+
+// out = [p] P + [b] B (as p1p1) with P in the wide tier (wtab: WT_POS tables of P), p < 2^128
+// in words p[0..4); b as in straus_comb.  No doublings, so the terms are added in ascending
+// position and the digit register shifts right.
+FE_INLINE void straus_pos(ge_p1p1& out, const ge_cached* __restrict__ wtab, const uint32_t p[4],
+                          const ge_niels* __restrict__ comb, const uint32_t fw[8]) {
+  uint32_t w[5];
+  sc_recode64(w, p);
+  ge_p1p1 x;
+  ge_p1p1_identity(x);
+#pragma clang loop unroll(disable)
+  for (int k = 0; k < WT_POS; k++) {
+    add_cached_sel(x, wtab + WT_N * k, (int)(w[0] & 63u) - 32);
+#pragma unroll
+    for (int i = 0; i < 4; i++) w[i] = __builtin_amdgcn_alignbit(w[i + 1], w[i], 6);
+    w[4] >>= 6;
+  }
+#pragma clang loop unroll(disable)
+  for (int j = 0; j < C16_T; j++) {
+    const uint32_t d = word_sel<8>(fw, j >> 1);                     // 16-bit digit j
+    add_niels_sel(x, comb + (size_t)C16_N * j, (int)((d >> (16 * (j & 1))) & 0xffffu) - 32768);
+  }
+  out = x;
+}
+
+// Wide tables in two passes, neither a long chain (both are on the path to the cached U chains).
+// Pass 1, one lane per key and chunk k < 8: from the chunk base Q = 2^(16k) P (key_chunk_bases)
+// the position bases 64^j P with 16k <= 6j < 16k + 16, as p3 into wbase[j]: 15 doublings.  Pass 2,
+// one lane per key, position and half h: entries (16h + 1 .. 16h + 16) 64^j P of that position's
+// table, stored as they are made.
+FE_INLINE void key_pos_bases(ge_cached* __restrict__ wbase, const ge_p3& Qk, int k) {
+  ge_p3 Q = Qk;
+#pragma clang loop unroll(disable)
+  for (int d = 0; d < 16; d++) {
+    const int bit = 16 * k + d, j = bit / 6;
+    if (bit == 6 * j && j < WT_POS) *(ge_p3*)(wbase + j) = Q;
+    if (d < 15) {
+      ge_p3 R;
+      ge_p3_dbl_to_p3(R, Q);
+      Q = R;
+    }
+  }
+}
+FE_INLINE void key_pos_table(ge_cached* __restrict__ tab, const ge_p3& Q, int half) {
+  ge_cached c1, ck;
+  ge_p3_to_cached(c1, Q);
+  ge_p3 acc = Q;
+  if (half) {                                                    // 17 Q = 2^4 Q + Q
+    ge_p2 q;
+    ge_p1p1 t;
+    ge_p3_to_p2(q, Q);
+#pragma clang loop unroll(disable)
+    for (int d = 0; d < 3; d++) { ge_p2_dbl(t, q); ge_p1p1_to_p2(q, t); }
+    ge_p2_dbl(t, q);
+    ge_p1p1_to_p3(acc, t);
+    ge_add(t, acc, c1);
+    ge_p1p1_to_p3(acc, t);
+  }
+#pragma clang loop unroll(disable)
+  for (int k = 0; k < WT_N / 2; k++) {
+    ge_p3_to_cached(ck, acc);
+    tab[(WT_N / 2) * half + k] = ck;
+    if (k + 1 < WT_N / 2) {
+      ge_p1p1 t;
+      ge_add(t, acc, c1);
+      ge_p1p1_to_p3(acc, t);
+    }
+  }
+}
+
 // Key tables in two passes (k_keys.hip), so no lane runs the whole precompute: pass 1
 // (one lane per key) writes the chunk bases Q_k = 2^(16k) P as p3 into entry 0 of
 // each chunk table (a p3 and a cached point are both 4 field elements); pass 2 (one

@@ -260,6 +260,8 @@ SIGNATURES = {
     "praos_batch_kernel_ms": (ctypes.c_float, [ctypes.c_void_p, ctypes.c_int]),
     "praos_set_option": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
     "praos_batch_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u32p]),
+    "praos_batch_wide_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u32p]),
+    "praos_set_vrf_wide": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
     "praos_batch_dedup_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u32p]),
     "praos_verify_ocert": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, u8p, u8p, u64p, u64p, u8p, u8p]),
     "praos_verify_kes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, u8p, u32p, u8p, u64p, u32p, u8p,
@@ -649,13 +651,21 @@ class Context:
     def set_option(self, opt, value):
         self.check(self.L.praos_set_option(self.h, opt, value))
 
+    def set_vrf_wide(self, min_uses=-1, max_keys=0):
+        """Wide tier of the VRF key cache: keys with min_uses uses in a batch (-1 automatic, 0 off),
+        at most max_keys of them per batch (0: the default)."""
+        self.check(self.L.praos_set_vrf_wide(self.h, min_uses, max_keys))
+
     def batch_stats(self, b):
         """Key-cache statistics of the last run: dict of cold/vrf/kes entries, hits, misses."""
         out = np.zeros(9, np.uint32)
         self.check(self.L.praos_batch_stats(self.h, b, ptr(out, u32p)))
+        w = np.zeros(2, np.uint32)
+        self.check(self.L.praos_batch_wide_stats(self.h, b, ptr(w, u32p)))
         return {"cold_keys": int(out[0]), "cold_hits": int(out[1]), "cold_misses": int(out[2]),
                 "vrf_keys": int(out[3]), "vrf_hits": int(out[4]), "vrf_misses": int(out[5]),
-                "kes_keys": int(out[6]), "kes_hits": int(out[7]), "kes_misses": int(out[8])}
+                "kes_keys": int(out[6]), "kes_hits": int(out[7]), "kes_misses": int(out[8]),
+                "vrf_wide_keys": int(w[0]), "vrf_wide_hits": int(w[1])}
 
     def dedup_stats(self, b):
         """OCert dedup of the last run: distinct OCert tuples verified, headers."""

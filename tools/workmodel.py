@@ -75,6 +75,21 @@ def straus_comb(npc, p_top):
     return w
 
 
+def straus_pos():
+    """Wide tier (scalarmult.hpp straus_pos): 22 position adds, no doubling, + the 16 comb madds."""
+    return 22 * (TO_P3 + ADD + CNEG) + 16 * (TO_P3 + MADD + CNEG)
+
+
+def key_precompute_wide():
+    """A wide key (k_key_wide_bases / k_key_wide_tables): decode and the 9 chunk bases as for any VRF
+    key, no chunk tables; position bases from 8 chunk bases (15 p3 doublings each); 22 tables of 32
+    in two halves (the upper one starts from 16 Q + Q)."""
+    bases = 8 * 15 * (DBL + TO_P3)
+    half0 = 16 * (M + 2 * A) + 15 * (ADD + TO_P3)
+    half1 = half0 + 3 * (DBL + TO_P2) + (DBL + TO_P3) + (ADD + TO_P3)
+    return DECODE + 8 * 16 * (DBL + TO_P2) + bases + 22 * (half0 + half1)
+
+
 def key_precompute(nchunks):
     """k_key_precompute: decode, nchunks tables, 16 doublings between chunks."""
     return DECODE + nchunks * TABLE8 + (nchunks - 1) * 16 * (DBL + TO_P2)
@@ -106,11 +121,15 @@ W_TP_HEADER = W_OCERT + W_KES + W_VRF_TP + W_LEADER_TP
 W_KEY_COLD = key_precompute(16)
 W_KEY_KES = key_precompute(16)                       # leaf keys: same tables as cold keys
 W_KEY_VRF = key_precompute(9) + CANON
+# wide tier of the VRF key cache: per header on a wide key, per wide key (use with the counts of
+# praos_batch_wide_stats: wide hits, wide keys; the other hits and keys keep W_VRF_F_CK / W_KEY_VRF)
+W_VRF_F_CK_WIDE = _FIN + straus_pos()
+W_KEY_VRF_WIDE = key_precompute_wide() + CANON
 
 if __name__ == "__main__":
     for k, v in (("ocert", W_OCERT), ("kes", W_KES), ("vrf", W_VRF), ("leader", W_LEADER),
                  ("ocert_ck", W_OCERT_CK), ("vrf_ck", W_VRF_CK), ("kes_ck", W_KES_CK), ("key_cold", W_KEY_COLD), ("key_vrf", W_KEY_VRF),
                  ("vrf_v", W_VRF_V), ("vrf_f_ck", W_VRF_F_CK), ("vrf_f", W_VRF_F), ("vrf_tp", W_VRF_TP),
-                 ("tp_hdr", W_TP_HEADER)):
-        print(f"W_{k:7s} {v:>10,d} int32 ops / item")
+                 ("tp_hdr", W_TP_HEADER), ("vrf_f_ck_wide", W_VRF_F_CK_WIDE), ("key_vrf_wide", W_KEY_VRF_WIDE)):
+        print(f"W_{k:13s} {v:>10,d} int32 ops / item")
     print(f"W_header  {W_OCERT + W_KES + W_VRF + W_LEADER:>10,d}")
