@@ -939,6 +939,104 @@ int praos_replay_immutable_tpraos(praos_ctx* ctx, const char* dir, const praos_p
                                   size_t batch_max, uint8_t* verdicts, uint16_t* failures, size_t verdicts_cap,
                                   praos_replay_stats* stats);
 
+/* ---- headers as the ChainSync client receives them (call stack 3) ----
+ * A header arrives in the node-to-node encoding, not as a chunk-file span:
+ *   Shelley-based eras  [eraIndex, #6.24(bytes)]  (decodeNS,
+ *       HardFork/Combinator/Serialisation/Common.hs:451-463; Shelley/Node/Serialisation.hs:110-112)
+ *   Byron               [0, [[kind, sizeHint], #6.24(bytes)]]  (Byron/Node/Serialisation.hs:83-99,
+ *       version 2; kind 0 = EBB, 1 = main header)
+ * The wire era index is not the disk tag (Babbage: 5 on the wire, 6 on disk).
+ * praos_unwrap_wire_headers finds the inner header bytes of each item of `items` (spans are wire
+ * items) on the device: status, era (the wire index, 0xff when not read), byron_kind (0 / 1, 0xff
+ * outside Byron), size_hint (Byron), the inner span (off, len: into the same arena) and, when
+ * header_hash is not NULL, the header hash: Blake2b-256 of the inner bytes for a Shelley-based item,
+ * Blake2b-256(82 0k || header) for a Byron one (what praos_verify_pbft_headers reports).  Items
+ * that do not unwrap have zero span and hash.  Heads of any width are taken (cborg's decoders
+ * accept non-shortest forms); lists and the byte string must be definite; the tag must be 24; an
+ * era index >= n_eras (7 for the reference's CardanoBlock) is PRAOS_WIRE_ERA; bytes after the item
+ * inside its span are PRAOS_WIRE_TRAILING; Byron: kind 0 or 1, the hint fits 32 bits.  A TPraos or
+ * Byron caller passes the inner spans on to praos_verify_tpraos_header_bytes /
+ * praos_verify_pbft_headers. */
+#define PRAOS_WIRE_OK       0
+#define PRAOS_WIRE_RANGE    1 /* span outside the arena */
+#define PRAOS_WIRE_SYNTAX   2 /* truncated, wrong type / length / tag, indefinite, kind > 1, hint > 32 bits */
+#define PRAOS_WIRE_ERA      3 /* era index >= n_eras */
+#define PRAOS_WIRE_TRAILING 4 /* bytes after the item within its span */
+typedef struct {
+  uint8_t* status;                /* n: PRAOS_WIRE_* */
+  uint8_t* era;                   /* n */
+  uint8_t* byron_kind;            /* n */
+  uint32_t* size_hint;            /* n */
+  uint64_t* off;                  /* n: inner header = bytes[off[i], off[i] + len[i]) */
+  uint32_t* len;                  /* n */
+  uint8_t* header_hash;           /* n*32, may be NULL */
+} praos_wire_out;
+int praos_unwrap_wire_headers(praos_ctx* ctx, const praos_header_bytes* items, uint32_t n_eras, praos_wire_out* out);
+
+/* K candidate fragments of wire headers, each from its own HeaderState, in one call: what the
+ * ChainSync clients of K peers do header by header (MiniProtocol/ChainSync/Client.hs:794-812:
+ * the DoesntFit check against the fragment's head, then validateHeader).  The items are unwrapped
+ * and hashed on the device, byte-identical headers (same era, same Blake2b-256) are found there,
+ * and the header crypto runs once per distinct (header, epoch nonce) pair -- a row; each
+ * fragment is then folded on the host from its own state, reading rows through the item-to-row
+ * map.  One ledger view per call: the pools and parameters of praos_set_epoch, the limits below.
+ *   verdict[i]: PRAOS_V_DOESNT_FIT when the header's prevHash is not the fragment's head hash
+ *   (checked before the envelope, so never PRAOS_V_ENV_PREV_HASH); else validateHeader's verdict as
+ *   praos_validate_headers_nonces gives it; PRAOS_V_INPUT for an item that did not unwrap, is of
+ *   an era outside praos_eras or did not decode.  The client disconnects at the first failure:
+ *   items after a fragment's chain_stop are PRAOS_V_NOT_REACHED, and so are the items from the
+ *   first header with slot >= view_end_slot on (the forecast does not reach them: the client
+ *   waits).  processed = items judged (through the stop, or up to the forecast horizon);
+ *   chain_stop = first invalid item, or processed when none.  Each fragment's tip and state are
+ *   those at its chain_stop.
+ * Rows are numbered in order of first appearance (a header's first nonce takes the row of its
+ * first item; a further nonce for the same bytes appends an extra row), so outputs do not depend
+ * on scheduling.  PRAOS_E_ARG: rows_cap too small (n_rows = the count needed); more than 256
+ * distinct epoch nonces (n_etas = the count). */
+#define PRAOS_V_DOESNT_FIT  25  /* ChainSync DoesntFit: prevHash is not the candidate's head */
+#define PRAOS_V_NOT_REACHED 255 /* after the fragment's stop, or beyond the forecast horizon */
+#define PRAOS_NO_ROW 0xffffffffu
+typedef struct {
+  praos_header_bytes items;       /* N wire items, fragment after fragment */
+  uint32_t n_eras;                /* eras of the block type (7) */
+  uint32_t praos_eras;            /* bit mask of the wire indices judged here; 0 = (1 << 5) | (1 << 6) */
+  uint64_t view_end_slot;         /* first slot the ledger view does not cover */
+  praos_epoch_info ei;
+  uint64_t max_major_pv;          /* the envelope limits (praos_envelope) */
+  uint64_t lv_prot_major;
+  uint64_t max_header_size;
+  uint64_t max_body_size;
+} praos_candidates_in;
+typedef struct {
+  int32_t tip_is_origin;          /* the fragment's head before the call (in / out) */
+  uint64_t tip_slot;
+  uint64_t tip_block_no;
+  uint8_t tip_hash[32];
+  praos_chain_state state;        /* in / out; counter arrays with room (cap) */
+  size_t chain_stop;              /* out: relative to the fragment's first item */
+  size_t processed;               /* out */
+} praos_fragment;
+typedef struct {
+  size_t k;
+  const size_t* frag_first;       /* k + 1: fragment j = items [frag_first[j], frag_first[j + 1]) */
+  praos_fragment* frag;           /* k */
+} praos_fragments;
+typedef struct {
+  uint8_t* wire_status;           /* N: PRAOS_WIRE_* */
+  uint32_t* row;                  /* N: the item's row, PRAOS_NO_ROW when it has none */
+  uint8_t* verdict;               /* N */
+  size_t rows_cap;
+  size_t n_rows;                  /* out */
+  praos_out rows;                 /* rows_cap per array (bits may be NULL here) */
+  praos_decoded dec;              /* rows_cap per array */
+  uint8_t* eta_idx;               /* rows_cap, may be NULL: the row's nonce, index into etas */
+  praos_nonce* etas;              /* 256, may be NULL */
+  uint32_t n_etas;                /* out */
+  uint64_t stats[5];              /* out: items, unwrapped Praos items, distinct headers, rows, extra rows */
+} praos_candidates_out;
+int praos_validate_candidates(praos_ctx* ctx, const praos_candidates_in* in, praos_fragments* frags,
+                              praos_candidates_out* out);
+
 /* ---- several GPUs from one process ----
  * A group = one context per entry of devices[] (a device may repeat: several
  * contexts on one GPU), each driven by its own host thread.  Batch calls split the

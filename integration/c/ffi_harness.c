@@ -9,6 +9,17 @@
  *   ffi_harness --validate-chunk <immutable dir> <chunk no> <slots per KES period>
  *   ffi_harness --validate-chunk-byron <immutable dir> <chunk no> <slots per KES period> <byron epoch slots> <pm>
  *   ffi_harness --pbft-headers <immutable dir> <window> <threshold> <byron epoch slots> <pm> <delegs file>
+ *   ffi_harness --candidates <immutable dir> <epoch file> <fragments file>
+ *
+ * --candidates: the ChainSync candidates call as Batch.hs validateCandidateFragments runs it.  The
+ *   database's headers are wrapped in the node-to-node encoding here ([5, #6.24(bytes)], the Babbage
+ *   wire index) and handed to praos_validate_candidates as the fragments the file lists, one per line:
+ *     frag <first header> <count> <state: PraosState CBOR hex> <tip: origin | slot:block_no:hash hex>
+ *     view_end <slot>                    (optional) the forecast horizon
+ *   after praos_set_epoch with the epoch file's pools (the call carries every nonce itself).  Prints
+ *   one JSON object: per fragment the verdicts, chain_stop, processed, the tip and the PraosState CBOR
+ *   at the stop; the stats; and praos_unwrap_wire_headers' inner spans of the same items relative to
+ *   each item's start.
  *
  * --validate-chunk: parseChunkFile as one call, as Batch.hs validateChunkBatch runs it: the chunk
  *   file as read, the secondary index's checksums and block offsets when the index is there and
@@ -1113,6 +1124,124 @@ static int pbft_headers_main(const char* dir, uint64_t window, uint64_t threshol
   return 0;
 }
 
+/* --candidates (see the head of this file) */
+static int candidates_main(const char* dir, const char* epoch_file, const char* frag_file) {
+  read_epoch_file(epoch_file);
+  chain_t ch;
+  read_chain(dir, &ch);
+  enum { MAXF = 16 };
+  static state_buf sb[MAXF];
+  praos_fragment* fr = calloc(MAXF, sizeof *fr);
+  size_t first[MAXF + 1], from[MAXF], count[MAXF], K = 0, N = 0;
+  uint64_t view_end = ~0ull;
+  FILE* f = fopen(frag_file, "r");
+  if (!f) DIE("cannot open %s", frag_file);
+  static char line[1 << 20], st_hex[1 << 20], tip[256];
+  while (fgets(line, sizeof line, f)) {
+    unsigned long long a, b;
+    if (sscanf(line, "view_end %llu", &a) == 1) { view_end = a; continue; }
+    if (sscanf(line, "frag %llu %llu %1048575s %255s", &a, &b, st_hex, tip) != 4) continue;
+    if (K == MAXF) DIE("too many fragments");
+    if (a + b > ch.n) DIE("fragment %zu outside the chain", K);
+    from[K] = (size_t)a;
+    count[K] = (size_t)b;
+    genesis_state(&sb[K]);
+    const size_t sl = strlen(st_hex) / 2;
+    uint8_t* enc = malloc(sl + 1);
+    hex_in(st_hex, enc, sl);
+    if (praos_state_decode(enc, sl, &sb[K].st) != PRAOS_OK) DIE("fragment %zu: praos_state_decode", K);
+    free(enc);
+    fr[K].state = sb[K].st;
+    if (strcmp(tip, "origin") == 0) {
+      fr[K].tip_is_origin = 1;
+    } else {
+      unsigned long long ts, tb;
+      char hh[128];
+      if (sscanf(tip, "%llu:%llu:%120s", &ts, &tb, hh) != 3) DIE("fragment %zu: tip", K);
+      fr[K].tip_slot = ts;
+      fr[K].tip_block_no = tb;
+      hex_in(hh, fr[K].tip_hash, 32);
+    }
+    N += count[K];
+    K++;
+  }
+  fclose(f);
+  uint8_t* arena = malloc(1);
+  size_t alen = 0, acap = 1, i = 0;
+  uint64_t* ioff = calloc(N + 1, 8);
+  uint32_t* ilen = calloc(N + 1, 4);
+  first[0] = 0;
+  /* the wire items: 82 05 d8 18 59 hh ll <header> (headers here are 256..65535 bytes long) */
+  for (size_t j = 0; j < K; j++) {
+    for (size_t h = from[j]; h < from[j] + count[j]; h++, i++) {
+      const uint32_t hl = ch.hlen[h];
+      if (hl < 256 || hl > 65535) DIE("header %zu: %u bytes", h, hl);
+      if (alen + hl + 7 > acap) {
+        acap = 2 * (alen + hl + 7);
+        arena = realloc(arena, acap);
+      }
+      const uint8_t pre[7] = {0x82, 0x05, 0xd8, 0x18, 0x59, (uint8_t)(hl >> 8), (uint8_t)hl};
+      memcpy(arena + alen, pre, 7);
+      memcpy(arena + alen + 7, ch.bytes + ch.off[h], hl);
+      ioff[i] = alen;
+      ilen[i] = hl + 7;
+      alen += hl + 7;
+    }
+    first[j + 1] = i;
+  }
+  praos_ctx* ctx = praos_open(0);
+  if (!ctx) DIE("praos_open(0)");
+  CK(ctx, praos_set_epoch(ctx, g_eta0, g_pools, g_npools, &g_params));
+  praos_candidates_in in;
+  memset(&in, 0, sizeof in);
+  in.items.n = N; in.items.bytes = arena; in.items.bytes_len = alen; in.items.off = ioff; in.items.len = ilen;
+  in.n_eras = 7;
+  in.view_end_slot = view_end;
+  in.ei = g_ei;
+  in.max_major_pv = g_env0.max_major_pv; in.lv_prot_major = g_env0.lv_prot_major;
+  in.max_header_size = g_env0.max_header_size; in.max_body_size = g_env0.max_body_size;
+  praos_fragments fs = {K, first, fr};
+  praos_candidates_out out;
+  memset(&out, 0, sizeof out);
+  out.wire_status = calloc(N + 1, 1);
+  out.row = calloc(N + 1, 4);
+  out.verdict = calloc(N + 1, 1);
+  out.rows_cap = N;
+  CK(ctx, praos_validate_candidates(ctx, &in, &fs, &out));
+  /* the stand-alone unwrap of the same items */
+  praos_wire_out wo = {calloc(N + 1, 1), calloc(N + 1, 1), calloc(N + 1, 1), calloc(N + 1, 4), calloc(N + 1, 8),
+                       calloc(N + 1, 4), NULL};
+  CK(ctx, praos_unwrap_wire_headers(ctx, &in.items, 7, &wo));
+  int spans_ok = 1;
+  for (size_t q = 0; q < N; q++)
+    spans_ok &= wo.status[q] == PRAOS_WIRE_OK && wo.era[q] == 5 && wo.byron_kind[q] == 0xff &&
+                wo.off[q] == ioff[q] + 7 && wo.len[q] + 7 == ilen[q] && out.wire_status[q] == PRAOS_WIRE_OK;
+  printf("{\"phase\": \"candidates\", \"items\": %zu, \"spans_ok\": %d, \"n_rows\": %zu, \"n_etas\": %u, \"stats\": "
+         "[%llu, %llu, %llu, %llu, %llu], \"fragments\": [", N, spans_ok, out.n_rows, out.n_etas,
+         (unsigned long long)out.stats[0], (unsigned long long)out.stats[1], (unsigned long long)out.stats[2],
+         (unsigned long long)out.stats[3], (unsigned long long)out.stats[4]);
+  static uint8_t buf[64 + 48 * CAP];
+  for (size_t j = 0; j < K; j++) {
+    size_t len = 0;
+    if (praos_state_encode(&fr[j].state, buf, sizeof buf, &len) != PRAOS_OK) DIE("state_encode");
+    printf("%s{\"chain_stop\": %zu, \"processed\": %zu, \"tip_origin\": %d, \"tip_slot\": %llu, \"tip_block_no\": %llu, "
+           "\"tip_hash\": \"", j ? ", " : "", fr[j].chain_stop, fr[j].processed, fr[j].tip_is_origin,
+           (unsigned long long)fr[j].tip_slot, (unsigned long long)fr[j].tip_block_no);
+    hex_out(fr[j].tip_hash, 32);
+    printf("\", \"state_cbor\": \"");
+    hex_out(buf, len);
+    printf("\", \"verdicts\": [");
+    for (size_t q = first[j]; q < first[j + 1]; q++) printf("%s%u", q > first[j] ? ", " : "", out.verdict[q]);
+    printf("], \"rows\": [");
+    for (size_t q = first[j]; q < first[j + 1]; q++) printf("%s%u", q > first[j] ? ", " : "", out.row[q]);
+    printf("]}");
+  }
+  printf("]}\n");
+  fflush(stdout);
+  praos_close(ctx);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (praos_abi_version() != PRAOS_ABI_VERSION) DIE("ABI version %d, header %d", praos_abi_version(), PRAOS_ABI_VERSION);
   if (argc == 6 && strcmp(argv[1], "--chunk") == 0)
@@ -1131,10 +1260,12 @@ int main(int argc, char** argv) {
     return pbft_headers_main(argv[2], strtoull(argv[3], NULL, 10), strtoull(argv[4], NULL, 10), es,
                              (uint32_t)strtoul(argv[6], NULL, 10), argv[7]);
   }
+  if (argc == 5 && strcmp(argv[1], "--candidates") == 0) return candidates_main(argv[2], argv[3], argv[4]);
   if (argc != 4) DIE("usage: %s <immutable dir> <epoch file> <threads> | --chunk <dir> <chunk> <spkp> <members>"
                      " | --validate-chunk <dir> <chunk> <spkp>"
                      " | --validate-chunk-byron <dir> <chunk> <spkp> <byron epoch slots> <protocol magic>"
-                     " | --pbft-headers <dir> <window> <threshold> <byron epoch slots> <protocol magic> <delegs file>",
+                     " | --pbft-headers <dir> <window> <threshold> <byron epoch slots> <protocol magic> <delegs file>"
+                     " | --candidates <dir> <epoch file> <fragments file>",
                      argv[0]);
   read_epoch_file(argv[2]);
   chain_t ch;

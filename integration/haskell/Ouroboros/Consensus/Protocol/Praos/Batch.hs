@@ -67,6 +67,13 @@ module Ouroboros.Consensus.Protocol.Praos.Batch
   , PBftTipC
   , PBftBatchResult (..)
   , validatePBftHeaderBatch
+    -- * Headers as the ChainSync client receives them (node-to-node encoding)
+  , WireHeader (..)
+  , unwrapWireHeaders
+  , CandidateFragment (..)
+  , CandidateLimits (..)
+  , CandidatesResult (..)
+  , validateCandidateFragments
     -- * Error reconstruction (typed constructors: module Batch.Errors)
   , verdictToError
   ) where
@@ -213,6 +220,18 @@ foreign import ccall safe "praos_pbft_state_encode" c_pbft_state_encode
   :: Ptr () -> Ptr Word8 -> CSize -> Ptr CSize -> IO CInt
 foreign import ccall safe "praos_pbft_state_decode" c_pbft_state_decode
   :: Ptr Word8 -> CSize -> Ptr () -> IO CInt
+-- additive as well (ABI version unchanged): wire headers and the ChainSync candidates call.  The
+-- structs unwrapWireHeaders and validateCandidateFragments poke and peek (checked against the C
+-- compiler by tests/test_candidates_abi.py; "layout-wire"):
+-- layout-wire praos_wire_out (56 bytes): status@0 era@8 byron_kind@16 size_hint@24 off@32 len@40 header_hash@48
+-- layout-wire praos_candidates_in (120 bytes): items@0 n_eras@40 praos_eras@44 view_end_slot@48 ei@56 max_major_pv@88 lv_prot_major@96 max_header_size@104 max_body_size@112
+-- layout-wire praos_fragment (304 bytes): tip_is_origin@0 tip_slot@8 tip_block_no@16 tip_hash@24 state@56 chain_stop@288 processed@296
+-- layout-wire praos_fragments (24 bytes): k@0 frag_first@8 frag@16
+-- layout-wire praos_candidates_out (312 bytes): wire_status@0 row@8 verdict@16 rows_cap@24 n_rows@32 rows@40 dec@80 eta_idx@248 etas@256 n_etas@264 stats@272
+foreign import ccall safe "praos_unwrap_wire_headers" c_unwrap_wire_headers
+  :: Ptr PraosCtx -> Ptr () -> Word32 -> Ptr () -> IO CInt
+foreign import ccall safe "praos_validate_candidates" c_validate_candidates
+  :: Ptr PraosCtx -> Ptr () -> Ptr () -> Ptr () -> IO CInt
 
 abiVersion :: CInt
 abiVersion = 15
@@ -1238,6 +1257,180 @@ validatePBftHeaderBatch ctx@(PraosBatchCtx p) PBftParamsC{pbWindowSize, pbThresh
     , pbrState = enc
     , pbrTip = tip' }
 
+-- ---------------------------------------------------------------- wire headers, ChainSync candidates
+
+-- | One unwrapped node-to-node header (praos_unwrap_wire_headers): the wrapper of decodeNS
+-- (HardFork/Combinator/Serialisation/Common.hs:451-463) around CBOR-in-CBOR bytes
+-- (Shelley/Node/Serialisation.hs:110-112), or Byron's @[0, [[kind, sizeHint], #6.24(bytes)]]@
+-- (Byron/Node/Serialisation.hs:83-99).  'whEra' is the wire index (Babbage 5), not the disk tag.
+data WireHeader = WireHeader
+  { whStatus    :: !Word8            -- ^ PRAOS_WIRE_*: 0 OK, 1 range, 2 syntax, 3 era, 4 trailing bytes
+  , whEra       :: !Word8
+  , whByronKind :: !Word8            -- ^ 0 EBB, 1 main header, 0xff outside Byron
+  , whSizeHint  :: !Word32
+  , whSpan      :: !(Word64, Word32) -- ^ the inner header in the same arena (offset, length)
+  , whHash      :: !BS.ByteString    -- ^ the header hash (32 bytes; zeros unless 'whStatus' is 0)
+  }
+
+-- | Unwrap @items@ (offset, length of each wire item in @arena@) on the GPU.  @nEras@ = 7 for the
+-- reference's CardanoBlock.  TPraos and Byron callers pass 'whSpan' on to
+-- 'praosValidateTPraosHeaderSpans' / 'validatePBftHeaderBatch'.
+unwrapWireHeaders :: PraosBatchCtx -> Word32 -> BS.ByteString -> [(Word64, Word32)] -> IO [WireHeader]
+unwrapWireHeaders (PraosBatchGroup _ _ _) _ _ _ =
+  throwIO (PraosBatchError (-2) "unwrapWireHeaders: one context, not a group")
+unwrapWireHeaders ctx@(PraosBatchCtx p) nEras arena items = do
+  let n = length items
+      m = max 1 n
+      offs = VS.fromList (map fst items)
+      lens = VS.fromList (map snd items)
+  stv <- VSM.replicate m 0 :: IO (VSM.IOVector Word8)
+  erv <- VSM.replicate m 0 :: IO (VSM.IOVector Word8)
+  kdv <- VSM.replicate m 0 :: IO (VSM.IOVector Word8)
+  hnv <- VSM.replicate m 0 :: IO (VSM.IOVector Word32)
+  iov <- VSM.replicate m 0 :: IO (VSM.IOVector Word64)
+  ilv <- VSM.replicate m 0 :: IO (VSM.IOVector Word32)
+  hhv <- VSM.replicate (32 * m) 0 :: IO (VSM.IOVector Word8)
+  BSU.unsafeUseAsCStringLen arena $ \(ap, alen) ->
+    VS.unsafeWith offs $ \offp -> VS.unsafeWith lens $ \lenp ->
+    VSM.unsafeWith stv $ \stp -> VSM.unsafeWith erv $ \erp -> VSM.unsafeWith kdv $ \kdp ->
+    VSM.unsafeWith hnv $ \hnp -> VSM.unsafeWith iov $ \iop -> VSM.unsafeWith ilv $ \ilp ->
+    VSM.unsafeWith hhv $ \hhp -> allocaBytes 40 $ \hb -> allocaBytes 56 $ \wo -> do
+      pokeByteOff hb 0 (fromIntegral n :: CSize) >> pokeByteOff hb 8 ap
+      pokeByteOff hb 16 (fromIntegral alen :: CSize) >> pokeByteOff hb 24 offp >> pokeByteOff hb 32 lenp
+      pokeByteOff wo 0 stp >> pokeByteOff wo 8 erp >> pokeByteOff wo 16 kdp >> pokeByteOff wo 24 hnp
+      pokeByteOff wo 32 iop >> pokeByteOff wo 40 ilp >> pokeByteOff wo 48 hhp
+      check ctx (c_unwrap_wire_headers p (castPtr hb) nEras (castPtr wo))
+  st <- VS.unsafeFreeze stv
+  er <- VS.unsafeFreeze erv
+  kd <- VS.unsafeFreeze kdv
+  hn <- VS.unsafeFreeze hnv
+  io <- VS.unsafeFreeze iov
+  il <- VS.unsafeFreeze ilv
+  hh <- VS.unsafeFreeze hhv
+  pure [ WireHeader (st VS.! i) (er VS.! i) (kd VS.! i) (hn VS.! i) (io VS.! i, il VS.! i)
+                    (BS.pack (VS.toList (VS.slice (32 * i) 32 hh)))
+       | i <- [0 .. n - 1] ]
+
+-- | One peer's candidate: its wire headers (spans in the call's arena), the head of the fragment
+-- ('Nothing' = Origin, else slot, block number, header hash) and the PraosState CBOR there.
+data CandidateFragment = CandidateFragment
+  { cfItems :: ![(Word64, Word32)]
+  , cfTip   :: !(Maybe (Word64, Word64, BS.ByteString))
+  , cfState :: !BS.ByteString
+  }
+
+-- | The envelope limits of the call's ledger view and how far its forecast reaches.
+data CandidateLimits = CandidateLimits
+  { clMaxMajorPV    :: !Word64
+  , clProtMajor     :: !Word64
+  , clMaxHeaderSize :: !Word64
+  , clMaxBodySize   :: !Word64
+  , clViewEndSlot   :: !Word64   -- ^ first slot the ledger view does not cover ('maxBound': no horizon)
+  }
+
+data CandidatesResult = CandidatesResult
+  { crVerdicts  :: ![[Word8]]    -- ^ per fragment, per item: PRAOS_V_* (25 DoesntFit, 255 not reached)
+  , crStops     :: ![(Int, Int)] -- ^ per fragment: (chain_stop, processed)
+  , crTips      :: ![Maybe (Word64, Word64, BS.ByteString)] -- ^ the head at each fragment's stop
+  , crStates    :: ![BS.ByteString]                         -- ^ the PraosState CBOR there
+  , crStats     :: !(Word64, Word64, Word64, Word64, Word64) -- ^ items, unwrapped, distinct headers, rows, extra rows
+  }
+
+-- | What the ChainSync clients of K peers do header by header
+-- (MiniProtocol/ChainSync/Client.hs:794-812: the DoesntFit check, then validateHeader), in one
+-- call: the items are unwrapped, hashed and deduplicated on the GPU, the header crypto runs once
+-- per distinct (header, epoch nonce) pair, each fragment is folded from its own state.  The pools
+-- and parameters are those of 'praosSetEpoch'.  The service that collects headers from the
+-- client threads into such calls is not part of this module.
+validateCandidateFragments :: PraosBatchCtx -> (Word64, Word64, Word64, Word64) -> CandidateLimits
+                           -> BS.ByteString -> [CandidateFragment] -> IO CandidatesResult
+validateCandidateFragments (PraosBatchGroup _ _ _) _ _ _ _ =
+  throwIO (PraosBatchError (-2) "validateCandidateFragments: one context, not a group")
+validateCandidateFragments ctx@(PraosBatchCtx p) (baseSlot, baseNo, epochLen, window) lim arena frs = do
+  let k = length frs
+      items = concatMap cfItems frs
+      n = length items
+      m = max 1 n
+      counts = map (length . cfItems) frs
+      firsts = VS.fromList (map fromIntegral (scanl (+) 0 counts) :: [CSize])
+      offs = VS.fromList (map fst items)
+      lens = VS.fromList (map snd items)
+      -- room in each fragment's counter map: the pools a state can name (65536, as withChainState
+      -- sizes it) plus one new issuer per item of that fragment; the fragments' arrays lie back to
+      -- back at the running offsets capOffs
+      caps = map (\c -> 65536 + c) counts :: [Int]
+      capOffs = scanl (+) 0 caps
+      capTotal = max 1 (sum caps)
+  wsv <- VSM.replicate m 0 :: IO (VSM.IOVector Word8)
+  rwv <- VSM.replicate m 0 :: IO (VSM.IOVector Word32)
+  vdv <- VSM.replicate m 0 :: IO (VSM.IOVector Word8)
+  allocaBytes (304 * max 1 k) $ \fr -> allocaBytes (28 * capTotal) $ \hks ->
+    allocaBytes (8 * capTotal) $ \ctrs -> do
+    fillBytes fr 0 (304 * max 1 k)
+    forM_ (zip3 [0 ..] frs (zip caps capOffs)) $ \(j, f, (cap, capOff)) -> do
+      let fp = fr `plusPtr` (304 * j) :: Ptr ()
+          st = fp `plusPtr` 56 :: Ptr ()
+      case cfTip f of
+        Nothing -> pokeByteOff fp 0 (1 :: Int32)
+        Just (s, b, h) -> do
+          pokeByteOff fp 0 (0 :: Int32) >> pokeByteOff fp 8 s >> pokeByteOff fp 16 b
+          BSU.unsafeUseAsCStringLen (BS.take 32 (h <> BS.replicate 32 0)) $ \(hp, _) ->
+            copyBytes (castPtr fp `plusPtr` 24) hp 32
+      -- praos_chain_state: the counter arrays of fragment j, then the decoded state
+      pokeByteOff st 16 (hks `plusPtr` (28 * capOff) :: Ptr Word8)
+      pokeByteOff st 24 (ctrs `plusPtr` (8 * capOff) :: Ptr Word64)
+      pokeByteOff st 40 (fromIntegral cap :: CSize)
+      BSU.unsafeUseAsCStringLen (cfState f) $ \(src, sl) -> do
+        rc <- c_state_decode (castPtr src) (fromIntegral sl) st
+        when (rc /= 0) $ throwIO (PraosBatchError (fromIntegral rc) "praos_state_decode")
+    stats <- BSU.unsafeUseAsCStringLen arena $ \(ap, alen) ->
+      VS.unsafeWith firsts $ \ffp -> VS.unsafeWith offs $ \offp -> VS.unsafeWith lens $ \lenp ->
+      VSM.unsafeWith wsv $ \wsp -> VSM.unsafeWith rwv $ \rwp -> VSM.unsafeWith vdv $ \vdp ->
+      allocaBytes 120 $ \cin -> allocaBytes 24 $ \fs -> allocaBytes 312 $ \out -> do
+        fillBytes cin 0 120 >> fillBytes out 0 312
+        -- praos_candidates_in: items (praos_header_bytes), n_eras, praos_eras (0: 5 and 6), horizon,
+        -- epoch info, limits
+        pokeByteOff cin 0 (fromIntegral n :: CSize) >> pokeByteOff cin 8 ap
+        pokeByteOff cin 16 (fromIntegral alen :: CSize) >> pokeByteOff cin 24 offp >> pokeByteOff cin 32 lenp
+        pokeByteOff cin 40 (7 :: Word32) >> pokeByteOff cin 44 (0 :: Word32)
+        pokeByteOff cin 48 (clViewEndSlot lim)
+        pokeByteOff cin 56 baseSlot >> pokeByteOff cin 64 baseNo >> pokeByteOff cin 72 epochLen
+        pokeByteOff cin 80 window
+        pokeByteOff cin 88 (clMaxMajorPV lim) >> pokeByteOff cin 96 (clProtMajor lim)
+        pokeByteOff cin 104 (clMaxHeaderSize lim) >> pokeByteOff cin 112 (clMaxBodySize lim)
+        pokeByteOff fs 0 (fromIntegral k :: CSize) >> pokeByteOff fs 8 ffp >> pokeByteOff fs 16 fr
+        -- praos_candidates_out: the per-item arrays; no per-row outputs are asked for (rows_cap = n
+        -- bounds the rows, every rows / dec pointer stays NULL)
+        pokeByteOff out 0 wsp >> pokeByteOff out 8 rwp >> pokeByteOff out 16 vdp
+        pokeByteOff out 24 (fromIntegral n :: CSize)
+        check ctx (c_validate_candidates p (castPtr cin) (castPtr fs) (castPtr out))
+        s0 <- peekByteOff out 272
+        s1 <- peekByteOff out 280
+        s2 <- peekByteOff out 288
+        s3 <- peekByteOff out 296
+        s4 <- peekByteOff out 304
+        pure (s0, s1, s2, s3, s4)
+    vd <- VS.freeze vdv
+    res <- mapM (\j -> do
+      let fp = fr `plusPtr` (304 * j) :: Ptr ()
+      origin <- peekByteOff fp 0 :: IO Int32
+      tip <- if origin /= 0 then pure Nothing else do
+        s <- peekByteOff fp 8
+        b <- peekByteOff fp 16
+        h <- BS.packCStringLen (castPtr fp `plusPtr` 24, 32)
+        pure (Just (s, b, h))
+      enc <- encodeChainState (fp `plusPtr` 56)
+      stop <- peekByteOff fp 288 :: IO CSize
+      done <- peekByteOff fp 296 :: IO CSize
+      pure (tip, enc, (fromIntegral stop, fromIntegral done))) [0 .. k - 1]
+    let starts = scanl (+) 0 counts
+    pure CandidatesResult
+      { crVerdicts = [VS.toList (VS.slice a c vd) | (a, c) <- zip starts counts]
+      , crStops = [x | (_, _, x) <- res]
+      , crTips = [t | (t, _, _) <- res]
+      , crStates = [e | (_, e, _) <- res]
+      , crStats = stats }
+
 -- ---------------------------------------------------------------- errors
 
 -- | The reference error a verdict stands for, by name (logs, traces).  The typed
@@ -1273,4 +1466,5 @@ verdictToError v bits = case v of
   22 -> Just "PBftNotGenesisDelegate"
   23 -> Just "PBftExceededSignThreshold"
   24 -> Just "UnexpectedEBBInSlot"
+  25 -> Just "DoesntFit"
   _  -> Just ("unknown verdict " ++ show v)

@@ -27,6 +27,7 @@ module Ouroboros.Consensus.Protocol.Praos.Batch.Errors
   , verdictToChainPredicateFailure
   , verdictToPBftValidationErr
   , verdictToByronEnvelopeError
+  , verdictToChainSyncDoesntFit
   ) where
 
 import           Cardano.Crypto.VRF (CertifiedVRF (certifiedOutput), getOutputVRFNatural, hashVerKeyVRF)
@@ -65,6 +66,11 @@ import           Ouroboros.Consensus.Byron.Ledger.HeaderValidation (ByronOtherHe
 import           Ouroboros.Consensus.Protocol.PBFT (PBftLedgerView, PBftValidationErr (..))
 import           Ouroboros.Consensus.Protocol.PBFT.Crypto (PBftCrypto (PBftVerKeyHash))
 import qualified Data.Text as Text
+import           Ouroboros.Consensus.MiniProtocol.ChainSync.Client (ChainSyncClientException (DoesntFit), Our,
+                     Their)
+import           Ouroboros.Network.Block (Tip)
+import           Ouroboros.Consensus.Block (StandardHash)
+import           Data.Typeable (Typeable)
 
 -- | A protocol verdict (PRAOS_V_KES_BEFORE_START .. PRAOS_V_LEADER_TOO_BIG = 1..11) as
 -- the 'PraosValidationErr' the reference throws for that header.
@@ -318,4 +324,17 @@ verdictToByronEnvelopeError v aux actualBlockNo actualSlot oldTip prevHash = cas
   14 -> Just (UnexpectedSlotNo (SlotNo aux) actualSlot)
   15 -> Just (UnexpectedPrevHash oldTip prevHash)
   24 -> Just (OtherHeaderEnvelopeError (UnexpectedEBBInSlot actualSlot))
+  _  -> Nothing
+
+-- | Verdict 25 (PRAOS_V_DOESNT_FIT) of validateCandidateFragments as the exception the ChainSync
+-- client disconnects with (MiniProtocol/ChainSync/Client.hs:794-803): DoesntFit, with the
+-- header's own prevHash, the head hash of the candidate fragment it was meant to extend, and the
+-- two tips the client holds at that moment.  Checked before validateHeader, so a header that does
+-- not fit never yields UnexpectedPrevHash (15) there.
+verdictToChainSyncDoesntFit
+  :: (Typeable blk, StandardHash blk)
+  => Word8 -> ChainHash blk -> ChainHash blk -> Our (Tip blk) -> Their (Tip blk)
+  -> Maybe ChainSyncClientException
+verdictToChainSyncDoesntFit v actualPrevHash expectPrevHash ourTip theirTip = case v of
+  25 -> Just (DoesntFit actualPrevHash expectPrevHash ourTip theirTip)
   _  -> Nothing

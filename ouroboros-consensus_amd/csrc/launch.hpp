@@ -266,3 +266,15 @@ void launch_selftest4_msm(hipStream_t stream, int variant, size_t n, const uint8
 // 0, 1, 3, 4 (kind 2 is launch_seg_hash); the tables are praos_hip.h's
 void launch_selftest_hash(hipStream_t stream, int kind, size_t n, const uint8_t* arena, const uint64_t* off,
                           const uint32_t* len, const uint8_t* aux, const uint64_t* parts, uint8_t* out);
+// wire headers (k_wire.hip): unwrap + header hash of n wire items (hash may be NULL), and the
+// header dedup of praos_validate_candidates -- slot_item / slot_min: (mask + 1) words each, zeroed
+// / set to 0xff by the caller; blk: one word per block of NT items; *total = distinct headers;
+// row_off / row_len: the representatives' inner spans in order of first appearance (rows <
+// rows_cap); item_row: each item's row (0xffffffff: none)
+void launch_wire_split(hipStream_t stream, size_t n, const uint8_t* arena, uint64_t arena_len, const uint64_t* off,
+                       const uint32_t* len, uint32_t n_eras, uint8_t* status, uint8_t* era, uint8_t* kind,
+                       uint32_t* hint, uint64_t* ioff, uint32_t* ilen, uint8_t* hash);
+void launch_hdr_dedup(hipStream_t stream, size_t n, const uint8_t* status, const uint8_t* era, const uint8_t* hash,
+                      uint32_t era_mask, uint32_t mask, uint32_t* slot_item, uint32_t* slot_min, uint32_t* item_slot,
+                      uint32_t* item_rep, uint32_t* blk, uint32_t* total, const uint64_t* ioff, const uint32_t* ilen,
+                      uint32_t rows_cap, uint64_t* row_off, uint32_t* row_len, uint32_t* rep_row, uint32_t* item_row);

@@ -289,6 +289,8 @@ struct praos_ctx {
   hipStream_t decstream = nullptr;                     // submitted calls: each landed chunk's decode (off the
                                                        // copy stream, whose next upload must not wait for it)
   praos_batch* rp_keep[RP_SLOTS] = {};                 // replay batches kept between calls
+  uint8_t* cand_scratch = nullptr;                     // praos_validate_candidates: wire arena, item
+  size_t cand_scratch_sz = 0;                          // buffers and hash set, kept between calls
   hipEvent_t up_ev[PIPE_MAX] = {}, done_ev[PIPE_MAX] = {};
   praos_batch* pipe[PIPE_MAX] = {};
   // praos_verify_header_bytes_submit: up to PIPE_CALLS calls in flight, on pipe[0 .. PIPE_CALLS) in turn
@@ -873,6 +875,7 @@ void praos_close(praos_ctx* c) {
   if (c->kc1_ev) (void)hipEventDestroy(c->kc1_ev);
   if (c->cstream) (void)hipStreamSynchronize(c->cstream);
   for (int k = 0; k < RP_SLOTS; k++) rp_batch_destroy(c, c->rp_keep[k]);
+  if (c->cand_scratch) (void)hipFree(c->cand_scratch);
   for (int k = 0; k < PIPE_MAX; k++) {
     if (c->pipe[k]) {
       for (void* p : c->pipe[k]->owned) (void)hipFree(p);
@@ -3068,6 +3071,64 @@ int rp_download_results(praos_ctx* c, praos_batch* b, uint16_t* bits, int32_t* p
   return PRAOS_OK;
 }
 
+// ---- the candidates call (praos_candidates.hip): the wire arena, the item buffers and the hash
+// set live in one device buffer the context keeps between calls (like its replay batches); the
+// header dedup writes the distinct headers' spans there, and the decode of a replay batch reads
+// arena and spans from it, over those rows only
+int rp_device(const praos_ctx* c) { return c ? c->device : -1; }
+hipStream_t rp_copy_stream(praos_ctx* c) { return c->cstream; }
+bool rp_have_epoch(const praos_ctx* c) { return c && c->have_epoch; }
+
+uint8_t* rp_scratch(praos_ctx* c, size_t bytes) {
+  if (!c || c->device < 0) return nullptr;
+  if (c->cand_scratch && c->cand_scratch_sz >= bytes) return c->cand_scratch;
+  (void)hipSetDevice(c->device);
+  if (c->cand_scratch) (void)hipFree(c->cand_scratch);
+  c->cand_scratch = nullptr;
+  c->cand_scratch_sz = 0;
+  const size_t sz = bytes + bytes / 8 + 4096;
+  if (hipMalloc((void**)&c->cand_scratch, sz) != hipSuccess) { c->cand_scratch = nullptr; return nullptr; }
+  c->cand_scratch_sz = sz;
+  return c->cand_scratch;
+}
+
+// the spans' concatenation to dst (room for the bytes rounded up to 8, plus 16: ld64u's pad, zeroed)
+// through the pinned staging buffers, on the copy stream
+int rp_upload_bytes(praos_ctx* c, uint8_t* dst, const praos_span* spans, size_t nspans) {
+  size_t bytes = 0;
+  for (size_t j = 0; j < nspans; j++) bytes += spans[j].len;
+  if (!c || !dst) return PRAOS_E_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t pad = ((bytes + 7) & ~(size_t)7) + 16 - bytes;
+  HIPCHK(c, zero_pad(c, dst + bytes, pad, c->cstream));
+  if (bytes) HIPCHK(c, h2d_gather(c, dst, spans, nspans, bytes, c->cstream));
+  return PRAOS_OK;
+}
+
+// k_decode_praos and k_vrf_nonce over rows [first, n) of a replay batch, from the device span arrays
+// hoff / hlen into arena (copy stream); the batch then holds n rows
+int rp_decode_rows(praos_ctx* c, praos_batch* b, const uint8_t* arena, size_t arena_len, const uint64_t* hoff,
+                   const uint32_t* hlen, size_t first, size_t n) {
+  if (!c || !b || !arena || !hoff || !hlen || first > n || n > b->cap_n) return PRAOS_E_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (first == 0) HIPCHK(c, hipStreamWaitEvent(c->cstream, b->run_ev, 0));   // the batch's previous run reads the rows
+  b->n = n;
+  b->arena_len = 0;
+  b->body_bytes_len = (size_t)b->signed_stride * n;
+  b->decoded = true;
+  if (n > first) {
+    launch_decode_praos(dim3(nblocks(n - first, NT)), dim3(NT), c->cstream, n, arena, arena_len, hoff, hlen,
+                        b->slot, b->cold_vk, b->vrf_vk, b->vrf_out, b->vrf_proof, b->hot_vk, b->ocert_sig, b->kes_sig,
+                        b->ocert_n, b->ocert_c0, b->body_off, b->body_len, b->body, b->block_no, b->prev_hash,
+                        b->prev_genesis, b->body_size, b->body_hash, b->prot_major, b->prot_minor, b->header_hash,
+                        b->dec_status, b->tp_only ? 2 : 0, b->signed_stride, b->lead_out, b->lead_proof, first);
+    launch_vrf_nonce(c->cstream, n - first, b->vrf_out + 64 * first, b->tp_only ? 1 : 0, b->nonce + 32 * first);
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, hipEventRecord(b->dec_ev, c->cstream));
+  return PRAOS_OK;
+}
+
 extern "C" {
 
 // Stored-bytes verification with the upload in K chunks (contiguous runs of headers) and
@@ -3688,22 +3749,28 @@ static int fold_impl(praos_ctx* c, const praos_headers* h, const uint8_t* prev_h
                      praos_chain_state* st, uint8_t* verdict, size_t* chain_stop, size_t* processed,
                      const praos_nonce* etas = nullptr, uint32_t netas = 0, const uint8_t* eta_idx = nullptr,
                      bool tpraos = false, const praos_nonce* extra_entropy = nullptr, uint16_t* failures = nullptr,
-                     const praos_nonce* evol_after = nullptr, const rp_view* view = nullptr) {
+                     const praos_nonce* evol_after = nullptr, const rp_view* view = nullptr,
+                     const uint32_t* map = nullptr, bool client = false, std::string* err_out = nullptr) {
+  // map (praos_validate_candidates): item i of the fold reads row map[i] of every per-header input
+  // (h, prev_hash, crypto, env's arrays, eta_idx) and writes verdict[i] / failures[i] / reads
+  // evol_after[i]; PRAOS_NO_ROW = an item without a header (PRAOS_V_INPUT).  NULL: row i.  client:
+  // the ChainSync client's fold -- DoesntFit before validateHeader, and the fold ends at the first
+  // failure.  err_out: the error text goes there instead of the context (concurrent folds).
   if (!c) return PRAOS_E_ARG;
-  if (!h || !crypto || !crypto->bits || !crypto->nonce || !verdict || !ei || !st || !prev_hash) {
-    c->err = "fold: a required pointer is NULL (headers, crypto bits / nonce, verdict, epoch info, state, prev_hash)";
-    return PRAOS_E_ARG;
-  }
-  if (ei->epoch_length == 0 || st->m > st->cap || (st->cap && (!st->counter_hash28 || !st->counter))) {
-    c->err = "fold: epoch_length 0 or a counter map without room";
-    return PRAOS_E_ARG;
-  }
-  if (env && h->n && (!env->block_no || !env->header_hash || !env->header_size || !env->body_size)) {
-    c->err = "fold: the envelope needs block_no, header_hash, header_size and body_size";
-    return PRAOS_E_ARG;
-  }
-  if (!c->have_epoch) { c->err = "fold: no epoch installed (praos_set_epoch)"; return PRAOS_E_STATE; }
-  if (eta_idx && (!etas || netas == 0)) { c->err = "fold: eta_idx without etas"; return PRAOS_E_ARG; }
+  auto fail = [&](const char* m, int rc) {
+    if (err_out) *err_out = m;
+    else c->err = m;
+    return rc;
+  };
+  if (!h || !crypto || !crypto->bits || !crypto->nonce || !verdict || !ei || !st || !prev_hash)
+    return fail("fold: a required pointer is NULL (headers, crypto bits / nonce, verdict, epoch info, state, prev_hash)",
+                PRAOS_E_ARG);
+  if (ei->epoch_length == 0 || st->m > st->cap || (st->cap && (!st->counter_hash28 || !st->counter)))
+    return fail("fold: epoch_length 0 or a counter map without room", PRAOS_E_ARG);
+  if (env && h->n && (!env->block_no || !env->header_hash || !env->header_size || !env->body_size))
+    return fail("fold: the envelope needs block_no, header_hash, header_size and body_size", PRAOS_E_ARG);
+  if (!c->have_epoch) return fail("fold: no epoch installed (praos_set_epoch)", PRAOS_E_STATE);
+  if (eta_idx && (!etas || netas == 0)) return fail("fold: eta_idx without etas", PRAOS_E_ARG);
   praos_nonce eta0{};
   eta0.neutral = c->eta0_neutral;
   if (!c->eta0_neutral) std::memcpy(eta0.hash, c->eta0, 32);
@@ -3749,11 +3816,28 @@ static int fold_impl(praos_ctx* c, const praos_headers* h, const uint8_t* prev_h
   std::vector<uint64_t> Fctr;                        // and its counters (T is W's)
   std::vector<uint8_t> Fhas;
   size_t stop = h->n, i = 0;
+  auto freeze = [&] {
+    if (frozen) return;
+    F = W;
+    Fctr = T.ctr;
+    Fhas = T.has;
+    frozen = true;
+    stop = i;
+  };
   for (; i < h->n; i++) {
-    const uint64_t slot = h->slot[i];
+    const size_t r = map ? map[i] : i;
+    if (map && (map[i] == PRAOS_NO_ROW || (crypto->bits[r] & PRAOS_BIT_INPUT))) {
+      // no header to read (it did not unwrap or decode): the chain ends here
+      verdict[i] = PRAOS_V_INPUT;
+      if (failures) failures[i] = 0;
+      freeze();
+      if (client) { i++; break; }
+      continue;
+    }
+    const uint64_t slot = h->slot[r];
     bool ok = true;
     const uint64_t e_new = epoch_of(slot, &ok);
-    if (!ok) { c->err = "slot before the epoch base"; return PRAOS_E_ARG; }
+    if (!ok) return fail("slot before the epoch base", PRAOS_E_ARG);
     // tickChainDepState (Praos.hs:407-431) with isNewEpoch (Ledger/Util.hs:27-40)
     const uint64_t e_old = W.origin ? 0 : epoch_of(W.last_slot, &ok);
     praos_nonce tick_epoch = W.epoch_nonce, tick_leb = W.leb;
@@ -3764,48 +3848,49 @@ static int fold_impl(praos_ctx* c, const praos_headers* h, const uint8_t* prev_h
     }
     // the crypto outputs of header i were computed for this nonce: a tick to another one
     // ends the fold (the caller re-verifies from here under the right nonce)
-    if (eta_idx && eta_idx[i] >= netas) { c->err = "eta_idx out of range"; return PRAOS_E_ARG; }
-    if (!nonce_eq(tick_epoch, eta_idx ? etas[eta_idx[i]] : eta0)) break;
+    if (eta_idx && eta_idx[r] >= netas) return fail("eta_idx out of range", PRAOS_E_ARG);
+    if (!nonce_eq(tick_epoch, eta_idx ? etas[eta_idx[r]] : eta0)) break;
     // the issuer's counter slot (hashKey of the cold key, Praos.hs:595-606)
-    const int32_t pidx = crypto->pool_idx ? crypto->pool_idx[i] : -1;
+    const int32_t pidx = crypto->pool_idx ? crypto->pool_idx[r] : -1;
     uint32_t k;
     if (pidx >= 0 && (uint32_t)pidx < np) {
       k = (uint32_t)pidx;
     } else {
       uint8_t hh[28];
-      praos_host::blake2b(hh, 28, h->cold_vk + 32 * i, 32);
+      praos_host::blake2b(hh, 28, h->cold_vk + 32 * r, 32);
       k = counter_slot(by_hash, T, hh);
     }
-    const uint64_t n = h->ocert_n[i];
+    const uint64_t n = h->ocert_n[r];
     const bool has = T.has[k];
     uint8_t v;
     if (tpraos) {
       // currentIssueNo: the counter map, else 0 for a pool or a genesis delegate
       const bool known = has || k < np || c->gen_delegate_hashes.count(T.extra_keys[k - np]) > 0;
-      const uint16_t f = (crypto->bits[i] & PRAOS_BIT_INPUT) ? 0 : tpraos_failures(crypto->bits[i], known,
+      const uint16_t f = (crypto->bits[r] & PRAOS_BIT_INPUT) ? 0 : tpraos_failures(crypto->bits[r], known,
                                                                                     has ? T.ctr[k] : 0, n);
       if (failures) failures[i] = f;
-      v = (crypto->bits[i] & PRAOS_BIT_INPUT) ? PRAOS_V_INPUT : (f ? PRAOS_V_TPRAOS : PRAOS_V_OK);
+      v = (crypto->bits[r] & PRAOS_BIT_INPUT) ? PRAOS_V_INPUT : (f ? PRAOS_V_TPRAOS : PRAOS_V_OK);
     } else {
-      v = header_verdict(crypto->bits[i], has || k < np, has ? T.ctr[k] : 0, n);
+      v = header_verdict(crypto->bits[r], has || k < np, has ? T.ctr[k] : 0, n);
     }
     // validateHeader (HeaderValidation.hs:419-428): the envelope before the protocol checks
     if (env && v != PRAOS_V_INPUT) {
-      const uint8_t ve = envelope_verdict(env, W.tip, h, prev_hash, prev_is_genesis, i);
+      const uint8_t ve = envelope_verdict(env, W.tip, h, prev_hash, prev_is_genesis, r);
       if (ve != PRAOS_V_OK) {
         v = ve;
         if (failures) failures[i] = 0;               // validateEnvelope failed: PRTCL does not run
       }
     }
+    if (client && env && v != PRAOS_V_INPUT) {
+      // Client.hs:794-810: the header must fit onto the candidate's head before validateHeader
+      const bool genesis = prev_is_genesis && prev_is_genesis[r];
+      const bool fits = W.tip.origin ? genesis : (!genesis && std::memcmp(prev_hash + 32 * r, W.tip.hash, 32) == 0);
+      if (!fits) v = PRAOS_V_DOESNT_FIT;
+    }
     verdict[i] = v;
     if (v != PRAOS_V_OK) {
-      if (!frozen) {
-        F = W;
-        Fctr = T.ctr;
-        Fhas = T.has;
-        frozen = true;
-        stop = i;
-      }
+      freeze();
+      if (client) { i++; break; }
       continue;
     }
     // reupdateChainDepState (Praos.hs:468-502)
@@ -3813,11 +3898,11 @@ static int fold_impl(praos_ctx* c, const praos_headers* h, const uint8_t* prev_h
     W.leb = tick_leb;
     W.origin = 0;
     W.last_slot = slot;
-    W.lab.neutral = prev_is_genesis && prev_is_genesis[i];
+    W.lab.neutral = prev_is_genesis && prev_is_genesis[r];
     std::memset(W.lab.hash, 0, 32);
-    if (!W.lab.neutral) std::memcpy(W.lab.hash, prev_hash + 32 * i, 32);
+    if (!W.lab.neutral) std::memcpy(W.lab.hash, prev_hash + 32 * r, 32);
     praos_nonce eta{};
-    std::memcpy(eta.hash, crypto->nonce + 32 * i, 32);
+    std::memcpy(eta.hash, crypto->nonce + 32 * r, 32);
     eta.neutral = 0;
     // evol_after (the replay's nonce chain, run ahead as if every header were valid) equals
     // this chain up to the first invalid header; from there W skips the failed headers
@@ -3829,8 +3914,8 @@ static int fold_impl(praos_ctx* c, const praos_headers* h, const uint8_t* prev_h
     if (env) {                                       // HeaderState tip := getAnnTip hdr
       W.tip.origin = 0;
       W.tip.slot = slot;
-      W.tip.block_no = env->block_no[i];
-      std::memcpy(W.tip.hash, env->header_hash + 32 * i, 32);
+      W.tip.block_no = env->block_no[r];
+      std::memcpy(W.tip.hash, env->header_hash + 32 * r, 32);
     }
   }
   const Work& R = frozen ? F : W;
@@ -3838,7 +3923,7 @@ static int fold_impl(praos_ctx* c, const praos_headers* h, const uint8_t* prev_h
   const std::vector<uint8_t>& Rhas = frozen ? Fhas : T.has;
   size_t m = 0;
   for (size_t k = 0; k < Rhas.size(); k++) m += Rhas[k];
-  if (m > st->cap) { c->err = "counter map capacity exceeded"; return PRAOS_E_ARG; }
+  if (m > st->cap) return fail("counter map capacity exceeded", PRAOS_E_ARG);
   size_t j = 0;
   for (size_t k = 0; k < Rhas.size(); k++) {
     if (!Rhas[k]) continue;
@@ -3866,10 +3951,10 @@ int rp_fold(praos_ctx* c, const praos_headers* h, const uint8_t* prev_hash, cons
             const praos_out* crypto, praos_envelope* env, const praos_epoch_info* ei, praos_chain_state* st,
             const praos_nonce* etas, uint32_t k, const uint8_t* eta_idx, const praos_nonce* evolving_after,
             bool tpraos, const praos_nonce* extra_entropy, uint8_t* verdict, uint16_t* failures, size_t* chain_stop,
-            size_t* processed, const rp_view* view) {
+            size_t* processed, const rp_view* view, const uint32_t* map, bool client, std::string* err_out) {
   if (!etas || !eta_idx || k == 0) return PRAOS_E_ARG;
   return fold_impl(c, h, prev_hash, prev_is_genesis, crypto, env, ei, st, verdict, chain_stop, processed, etas, k,
-                   eta_idx, tpraos, extra_entropy, failures, evolving_after, view);
+                   eta_idx, tpraos, extra_entropy, failures, evolving_after, view, map, client, err_out);
 }
 
 extern "C" {

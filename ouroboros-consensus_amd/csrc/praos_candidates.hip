@@ -1,0 +1,516 @@
+// praos_candidates.hip -- headers as the ChainSync client receives them (call
+// stack 3): host C++ on top of the wire kernels (k_wire.hip) and the internal from-bytes batch of
+// replay_internal.hpp.
+//
+//   praos_unwrap_wire_headers   every era: the inner header span and the header hash of each
+//                               wire item (k_wire_split).
+//   praos_validate_candidates   K candidate fragments of Praos wire headers, each from its own
+//                               HeaderState (MiniProtocol/ChainSync/Client.hs:794-812):
+//     device   k_wire_split, k_hdr_dedup (+ the scan that numbers the distinct headers in order of
+//              first appearance and writes their spans into the batch's span arrays),
+//              k_decode_praos and k_vrf_nonce over those rows only;
+//     host     the speculative nonce chain of each fragment from its own state (the replay's
+//              chain thread: tick, candidate freeze, epoch nonce per header), which gives every
+//              item an epoch nonce out of one table of at most 256; the first nonce seen for a
+//              header takes its row, each further (header, nonce) pair an extra row decoded
+//              from the same span by a second k_decode_praos launch;
+//     device   the crypto run (rp_run) under the per-row nonces;
+//     host     rp_fold per fragment in the client's mode, reading rows through the item-to-row
+//              map, on at most min(K, 16) threads.
+#include <hip/hip_runtime.h>
+
+#include "praos_hip.h"
+#include "launch.hpp"
+#include "host_util.hpp"
+#include "replay_internal.hpp"
+
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <functional>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <unordered_map>
+#include <vector>
+
+void praos_set_error_(praos_ctx* c, const std::string& m);   // praos_api.hip
+
+namespace {
+
+constexpr size_t NT_ITEMS = 256;               // items per block of the k_hdr_* kernels (kcommon.hpp NT)
+constexpr uint32_t NONE = PRAOS_NO_ROW;
+constexpr unsigned MAX_FOLD_THREADS = 16;
+
+#define CHIP(c, x)                                                              \
+  do {                                                                          \
+    hipError_t e_ = (x);                                                        \
+    if (e_ != hipSuccess) {                                                     \
+      praos_set_error_((c), std::string(#x) + ": " + hipGetErrorString(e_));    \
+      return PRAOS_E_HIP;                                                       \
+    }                                                                           \
+  } while (0)
+
+// one device allocation carved into 256-byte aligned pieces (own: freed with the Carve)
+struct Carve {
+  uint8_t* base = nullptr;
+  size_t size = 0, used = 0;
+  bool own = false;
+  ~Carve() {
+    if (base && own) (void)hipFree(base);
+  }
+  static size_t up(size_t b) { return (b + 255) & ~(size_t)255; }
+  template <typename T>
+  T* take(size_t bytes) {
+    T* p = (T*)(base + used);
+    used += up(bytes);
+    return p;
+  }
+};
+
+// the item-side buffers of both entry points
+struct ItemBufs {
+  uint64_t *off, *ioff;
+  uint32_t *len, *hint, *ilen;
+  uint8_t *status, *era, *kind, *hash;
+  static size_t bytes(size_t n) {
+    return 2 * Carve::up(8 * n) + 3 * Carve::up(4 * n) + 3 * Carve::up(n) + Carve::up(32 * n);
+  }
+  void carve(Carve& m, size_t n) {
+    off = m.take<uint64_t>(8 * n); ioff = m.take<uint64_t>(8 * n);
+    len = m.take<uint32_t>(4 * n); hint = m.take<uint32_t>(4 * n); ilen = m.take<uint32_t>(4 * n);
+    status = m.take<uint8_t>(n); era = m.take<uint8_t>(n); kind = m.take<uint8_t>(n);
+    hash = m.take<uint8_t>(32 * n);
+  }
+};
+
+bool items_ok(const praos_header_bytes* s) {
+  return s && (s->n == 0 || (s->off && s->len)) && (s->bytes_len == 0 || s->bytes) && s->n < (1ull << 30);
+}
+
+// runs f(j) for j in [0, k) on at most min(k, 16) threads (never sized by the machine's cores)
+void par_for(size_t k, const std::function<void(size_t)>& f) {
+  const unsigned nt = (unsigned)std::min<size_t>(k, MAX_FOLD_THREADS);
+  if (nt <= 1) {
+    for (size_t j = 0; j < k; j++) f(j);
+    return;
+  }
+  std::atomic<size_t> next{0};
+  std::vector<std::thread> th;
+  for (unsigned t = 0; t < nt; t++)
+    th.emplace_back([&] {
+      for (size_t j; (j = next.fetch_add(1)) < k;) f(j);
+    });
+  for (auto& t : th) t.join();
+}
+
+}  // namespace
+
+extern "C" int praos_unwrap_wire_headers(praos_ctx* c, const praos_header_bytes* items, uint32_t n_eras,
+                                         praos_wire_out* out) {
+  if (!c || !items_ok(items) || !out) return PRAOS_E_ARG;
+  const size_t n = items->n, bytes = items->bytes_len;
+  if (n && (!out->status || !out->era || !out->byron_kind || !out->size_hint || !out->off || !out->len)) {
+    praos_set_error_(c, "unwrap: status, era, byron_kind, size_hint, off and len are required");
+    return PRAOS_E_ARG;
+  }
+  if (rp_device(c) < 0) { praos_set_error_(c, "host-only context: no HIP device"); return PRAOS_E_STATE; }
+  if (n == 0) return PRAOS_OK;
+  CHIP(c, hipSetDevice(rp_device(c)));
+  hipStream_t st = rp_copy_stream(c);
+  Carve m;
+  const size_t arena_sz = ((bytes + 7) & ~(size_t)7) + 16;     // ld64u's pad (arena.hpp)
+  m.size = Carve::up(arena_sz) + ItemBufs::bytes(n);
+  CHIP(c, hipMalloc((void**)&m.base, m.size));
+  m.own = true;
+  uint8_t* arena = m.take<uint8_t>(arena_sz);
+  ItemBufs d;
+  d.carve(m, n);
+  CHIP(c, hipMemsetAsync(arena + bytes, 0, arena_sz - bytes, st));
+  if (bytes) CHIP(c, hipMemcpyAsync(arena, items->bytes, bytes, hipMemcpyHostToDevice, st));
+  CHIP(c, hipMemcpyAsync(d.off, items->off, 8 * n, hipMemcpyHostToDevice, st));
+  CHIP(c, hipMemcpyAsync(d.len, items->len, 4 * n, hipMemcpyHostToDevice, st));
+  launch_wire_split(st, n, arena, bytes, d.off, d.len, n_eras, d.status, d.era, d.kind, d.hint, d.ioff, d.ilen,
+                    out->header_hash ? d.hash : nullptr);
+  CHIP(c, hipGetLastError());
+  CHIP(c, hipMemcpyAsync(out->status, d.status, n, hipMemcpyDeviceToHost, st));
+  CHIP(c, hipMemcpyAsync(out->era, d.era, n, hipMemcpyDeviceToHost, st));
+  CHIP(c, hipMemcpyAsync(out->byron_kind, d.kind, n, hipMemcpyDeviceToHost, st));
+  CHIP(c, hipMemcpyAsync(out->size_hint, d.hint, 4 * n, hipMemcpyDeviceToHost, st));
+  CHIP(c, hipMemcpyAsync(out->off, d.ioff, 8 * n, hipMemcpyDeviceToHost, st));
+  CHIP(c, hipMemcpyAsync(out->len, d.ilen, 4 * n, hipMemcpyDeviceToHost, st));
+  if (out->header_hash) CHIP(c, hipMemcpyAsync(out->header_hash, d.hash, 32 * n, hipMemcpyDeviceToHost, st));
+  CHIP(c, hipStreamSynchronize(st));
+  return PRAOS_OK;
+}
+
+namespace {
+
+// the speculative nonce chain of one fragment (praos_replay.hip's chain thread, Praos rules): the
+// epoch nonce tickChainDepState reaches at each item as if every header before it were valid, as
+// runs (first item, nonce), and the evolving nonce after each item.  Dead after an item without
+// a decoded header: the fold stops there whatever comes after.
+struct Run {
+  size_t first;
+  praos_nonce eta;
+};
+void spec_chain(const praos_chain_state& st, const praos_epoch_info& ei, size_t n, const uint32_t* base_row,
+                const praos_decoded& d, const uint8_t* nonce, std::vector<Run>& runs, praos_nonce* evol) {
+  auto epoch_of = [&](uint64_t s) {
+    return s < ei.epoch_base_slot ? ei.epoch_base_no : ei.epoch_base_no + (s - ei.epoch_base_slot) / ei.epoch_length;
+  };
+  int32_t origin = st.last_slot_origin;
+  uint64_t sp_epoch = origin ? 0 : epoch_of(st.last_slot);
+  praos_nonce evolving = st.evolving, candidate = st.candidate, epoch_nonce = st.epoch_nonce, lab = st.lab,
+              leb = st.last_epoch_block;
+  bool dead = false;
+  runs.clear();
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t r = base_row[i];
+    if (dead || r == NONE || (d.status[r] & PRAOS_DEC_FAILED)) {
+      dead = true;
+      if (runs.empty()) runs.push_back({i, epoch_nonce});
+      evol[i] = evolving;
+      continue;
+    }
+    const uint64_t slot = d.slot[r];
+    const uint64_t e_new = epoch_of(slot);
+    if (e_new > (origin ? 0 : sp_epoch)) {
+      epoch_nonce = praos_host::nonce_combine(candidate, leb);
+      leb = lab;
+    }
+    if (runs.empty() || !praos_host::nonce_eq(runs.back().eta, epoch_nonce)) runs.push_back({i, epoch_nonce});
+    origin = 0;
+    sp_epoch = e_new;
+    lab.neutral = d.prev_is_genesis[r] ? 1 : 0;
+    std::memset(lab.hash, 0, 32);
+    if (!lab.neutral) std::memcpy(lab.hash, d.prev_hash + 32 * (size_t)r, 32);
+    praos_nonce eta;
+    std::memcpy(eta.hash, nonce + 32 * (size_t)r, 32);
+    eta.neutral = 0;
+    evolving = praos_host::nonce_combine(evolving, eta);
+    evol[i] = evolving;
+    const uint64_t first_next =
+        slot < ei.epoch_base_slot ? ei.epoch_base_slot
+                                  : ei.epoch_base_slot + (e_new - ei.epoch_base_no + 1) * ei.epoch_length;
+    if (slot + ei.stability_window < first_next) candidate = evolving;
+  }
+}
+
+}  // namespace
+
+extern "C" int praos_validate_candidates(praos_ctx* c, const praos_candidates_in* in, praos_fragments* frags,
+                                         praos_candidates_out* out) {
+  if (!c || !in || !frags || !out || !items_ok(&in->items)) return PRAOS_E_ARG;
+  const size_t N = in->items.n, K = frags->k, bytes = in->items.bytes_len;
+  if (!frags->frag_first || (K && !frags->frag) || frags->frag_first[0] != 0 || frags->frag_first[K] != N ||
+      in->ei.epoch_length == 0 || (N && (!out->wire_status || !out->row || !out->verdict))) {
+    praos_set_error_(c, "candidates: frag_first must run from 0 to the item count; epoch_length > 0; "
+                        "wire_status, row and verdict are required");
+    return PRAOS_E_ARG;
+  }
+  for (size_t j = 0; j < K; j++) {
+    const praos_chain_state& s = frags->frag[j].state;
+    if (frags->frag_first[j] > frags->frag_first[j + 1] || s.m > s.cap || (s.cap && (!s.counter_hash28 || !s.counter))) {
+      praos_set_error_(c, "candidates: fragment " + std::to_string(j) + ": bounds out of order or a counter map without room");
+      return PRAOS_E_ARG;
+    }
+  }
+  if (rp_device(c) < 0) { praos_set_error_(c, "host-only context: no HIP device"); return PRAOS_E_STATE; }
+  if (!rp_have_epoch(c)) { praos_set_error_(c, "candidates: no epoch installed (praos_set_epoch)"); return PRAOS_E_STATE; }
+  {
+    const int rd = praos_verify_drain(c);      // submitted stored-bytes calls share the context's streams
+    if (rd != PRAOS_OK) return rd;
+  }
+  out->n_rows = 0;
+  out->n_etas = 0;
+  std::memset(out->stats, 0, sizeof out->stats);
+  out->stats[0] = N;
+  for (size_t j = 0; j < K; j++) frags->frag[j].chain_stop = frags->frag[j].processed = 0;
+  if (N == 0) return PRAOS_OK;
+  const uint32_t era_mask = in->praos_eras ? in->praos_eras : ((1u << 5) | (1u << 6));
+  CHIP(c, hipSetDevice(rp_device(c)));
+  hipStream_t st = rp_copy_stream(c);
+  // the hash set: a power of two, at least 2N slots
+  uint32_t tab = 2;
+  while (tab < 2 * N) tab <<= 1;
+  const size_t nb = (N + NT_ITEMS - 1) / NT_ITEMS;
+  // one device buffer, kept with the context between calls: the wire arena (with ld64u's pad), the
+  // item buffers, the dedup's arrays and the rows' spans (at most N rows)
+  const size_t arena_sz = ((bytes + 7) & ~(size_t)7) + 16;
+  Carve m;
+  m.size = Carve::up(arena_sz) + ItemBufs::bytes(N) + 4 * Carve::up(4 * N) + Carve::up(4 * nb) + Carve::up(4) +
+           2 * Carve::up(4 * (size_t)tab) + Carve::up(8 * N) + Carve::up(4 * N);
+  m.base = rp_scratch(c, m.size);
+  if (!m.base) { praos_set_error_(c, "candidates: device allocation failed"); return PRAOS_E_OOM; }
+  uint8_t* arena = m.take<uint8_t>(arena_sz);
+  ItemBufs d;
+  d.carve(m, N);
+  uint32_t* item_slot = m.take<uint32_t>(4 * N);
+  uint32_t* item_rep = m.take<uint32_t>(4 * N);
+  uint32_t* rep_row = m.take<uint32_t>(4 * N);
+  uint32_t* item_row = m.take<uint32_t>(4 * N);
+  uint32_t* blk = m.take<uint32_t>(4 * nb);
+  uint32_t* total = m.take<uint32_t>(4);
+  uint32_t* slot_item = m.take<uint32_t>(4 * (size_t)tab);
+  uint32_t* slot_min = m.take<uint32_t>(4 * (size_t)tab);
+  uint64_t* d_row_off = m.take<uint64_t>(8 * N);
+  uint32_t* d_row_len = m.take<uint32_t>(4 * N);
+
+  // ---- device: unwrap + hash, dedup, decode of the distinct headers
+  const praos_span whole{in->items.bytes, bytes};
+  uint32_t R = 0;
+  std::vector<uint32_t> base_row(N);
+  {
+    const int rc = rp_upload_bytes(c, arena, &whole, bytes ? 1 : 0);
+    if (rc != PRAOS_OK) return rc;
+  }
+  CHIP(c, hipMemcpyAsync(d.off, in->items.off, 8 * N, hipMemcpyHostToDevice, st));
+  CHIP(c, hipMemcpyAsync(d.len, in->items.len, 4 * N, hipMemcpyHostToDevice, st));
+  CHIP(c, hipMemsetAsync(slot_item, 0, 4 * (size_t)tab, st));
+  CHIP(c, hipMemsetAsync(slot_min, 0xff, 4 * (size_t)tab, st));
+  launch_wire_split(st, N, arena, bytes, d.off, d.len, in->n_eras, d.status, d.era, d.kind, d.hint, d.ioff, d.ilen, d.hash);
+  launch_hdr_dedup(st, N, d.status, d.era, d.hash, era_mask, tab - 1, slot_item, slot_min, item_slot, item_rep, blk, total,
+                   d.ioff, d.ilen, (uint32_t)N, d_row_off, d_row_len, rep_row, item_row);
+  CHIP(c, hipGetLastError());
+  CHIP(c, hipMemcpyAsync(&R, total, 4, hipMemcpyDeviceToHost, st));
+  CHIP(c, hipMemcpyAsync(out->wire_status, d.status, N, hipMemcpyDeviceToHost, st));
+  CHIP(c, hipMemcpyAsync(base_row.data(), item_row, 4 * N, hipMemcpyDeviceToHost, st));
+  CHIP(c, hipStreamSynchronize(st));
+  // a replay batch with room for the distinct headers, whatever rows_cap says: the count the
+  // caller needs comes out of the nonce chains over their decoded columns
+  praos_batch* b = nullptr;
+  struct Keep {                                  // the batch goes back to the context on every path
+    praos_ctx* c;
+    praos_batch*& b;
+    ~Keep() {
+      if (b) { rp_batch_quiesce(b); rp_batch_keep(c, 0, b); }
+    }
+  } keep{c, b};
+  b = rp_batch_take(c, 0, std::max<size_t>(R, 1), 8, false);
+  if (!b) { praos_set_error_(c, "candidates: device allocation failed"); return PRAOS_E_OOM; }
+  std::vector<uint64_t> row_off(R);
+  std::vector<uint32_t> row_len(R);
+  praos_decoded dec{};
+  uint8_t* nonce_h = nullptr;
+  {
+    int rc = rp_decode_rows(c, b, arena, bytes, d_row_off, d_row_len, 0, R);
+    if (rc != PRAOS_OK) return rc;
+    if (R) {
+      CHIP(c, hipMemcpyAsync(row_off.data(), d_row_off, 8 * (size_t)R, hipMemcpyDeviceToHost, st));
+      CHIP(c, hipMemcpyAsync(row_len.data(), d_row_len, 4 * (size_t)R, hipMemcpyDeviceToHost, st));
+    }
+    rc = rp_download_decoded(c, b, &dec, &nonce_h);            // (synchronises the copy stream)
+    if (rc != PRAOS_OK) return rc;
+  }
+  size_t unwrapped = 0;
+  for (size_t i = 0; i < N; i++) unwrapped += base_row[i] != NONE;
+  out->stats[1] = unwrapped;
+  out->stats[2] = R;
+
+  // ---- host: each fragment's nonce chain, then one table of nonces and the rows
+  const size_t* F = frags->frag_first;
+  std::vector<std::vector<Run>> runs(K);
+  std::vector<praos_nonce> evol(N);
+  par_for(K, [&](size_t j) {
+    spec_chain(frags->frag[j].state, in->ei, F[j + 1] - F[j], base_row.data() + F[j], dec, nonce_h, runs[j],
+               evol.data() + F[j]);
+  });
+  std::vector<praos_nonce> etas;
+  std::vector<uint8_t> row_eta(R, 0);
+  std::vector<uint8_t> row_set(R, 0);
+  std::vector<uint32_t> extra_base;
+  std::unordered_map<uint64_t, uint32_t> extra;               // (base row, nonce) -> extra row
+  bool too_many = false;
+  for (size_t j = 0; j < K; j++) {
+    for (size_t q = 0; q < runs[j].size(); q++) {
+      size_t e = 0;
+      while (e < etas.size() && !praos_host::nonce_eq(etas[e], runs[j][q].eta)) e++;
+      if (e == etas.size()) etas.push_back(runs[j][q].eta);
+      if (etas.size() > 256) { too_many = true; continue; }
+      const size_t lo = F[j] + runs[j][q].first, hi = q + 1 < runs[j].size() ? F[j] + runs[j][q + 1].first : F[j + 1];
+      for (size_t i = lo; i < hi; i++) {
+        const uint32_t r = base_row[i];
+        uint32_t row = r;
+        if (r != NONE) {
+          if (!row_set[r]) {
+            row_set[r] = 1;
+            row_eta[r] = (uint8_t)e;
+          } else if (row_eta[r] != e) {
+            const uint64_t key = ((uint64_t)r << 8) | e;
+            auto it = extra.find(key);
+            if (it == extra.end()) {
+              it = extra.emplace(key, (uint32_t)(R + extra_base.size())).first;
+              extra_base.push_back(r);
+              row_eta.push_back((uint8_t)e);
+            }
+            row = it->second;
+          }
+        }
+        out->row[i] = row;
+      }
+    }
+  }
+  out->n_etas = (uint32_t)etas.size();
+  if (too_many) {
+    praos_set_error_(c, "candidates: " + std::to_string(etas.size()) + " distinct epoch nonces in one call (at most 256)");
+    return PRAOS_E_ARG;
+  }
+  const size_t R2 = (size_t)R + extra_base.size();
+  out->n_rows = R2;
+  out->stats[3] = R2;
+  out->stats[4] = extra_base.size();
+  if (R2 > out->rows_cap) {
+    praos_set_error_(c, "candidates: rows_cap " + std::to_string(out->rows_cap) + " < " + std::to_string(R2) + " rows");
+    return PRAOS_E_ARG;
+  }
+  if (etas.empty()) {                                          // (only empty fragments)
+    praos_nonce z{};
+    z.neutral = 1;
+    etas.push_back(z);
+  }
+  for (size_t e = 0; e < etas.size() && out->etas; e++) out->etas[e] = etas[e];
+
+  // ---- device: the extra rows' decode, the crypto run under the per-row nonces
+  std::vector<uint64_t> xoff(extra_base.size());
+  std::vector<uint32_t> xlen(extra_base.size());
+  uint16_t* bits_h = nullptr;
+  int32_t* pidx_h = nullptr;
+  bool have_all = false;                         // dec / nonce_h hold the extra rows too
+  {
+    for (size_t x = 0; x < extra_base.size(); x++) { xoff[x] = row_off[extra_base[x]]; xlen[x] = row_len[extra_base[x]]; }
+    if (!xoff.empty()) {                         // (R2 <= N: the span arrays have room)
+      CHIP(c, hipMemcpyAsync(d_row_off + R, xoff.data(), 8 * xoff.size(), hipMemcpyHostToDevice, st));
+      CHIP(c, hipMemcpyAsync(d_row_len + R, xlen.data(), 4 * xlen.size(), hipMemcpyHostToDevice, st));
+    }
+    int rc;
+    if (rp_batch_fits(b, R2, 0)) {
+      rc = rp_decode_rows(c, b, arena, bytes, d_row_off, d_row_len, R, R2);
+    } else {
+      // more extra rows than the batch's headroom: a batch with room for every row, all of them
+      // decoded again from the spans already on the device
+      rp_batch_quiesce(b);
+      rp_batch_destroy(c, b);
+      b = rp_batch_take(c, 0, R2, 8, false);
+      if (!b) { praos_set_error_(c, "candidates: device allocation failed"); return PRAOS_E_OOM; }
+      rc = rp_decode_rows(c, b, arena, bytes, d_row_off, d_row_len, 0, R2);
+      if (rc == PRAOS_OK) rc = rp_download_decoded(c, b, &dec, &nonce_h);
+      have_all = true;
+    }
+    if (rc != PRAOS_OK) return rc;
+    if (R2) {
+      rc = rp_run(c, b, etas.data(), (uint32_t)etas.size(), row_eta.data());
+      if (rc != PRAOS_OK) return rc;
+    }
+    rp_batch_results(b, &bits_h, &pidx_h);
+    rc = rp_download_results(c, b, bits_h, pidx_h);
+    if (rc != PRAOS_OK) return rc;
+  }
+
+  // ---- host: the fold's per-row inputs (the pinned decode download; with extra rows, copies
+  // long enough for them: an extra row has its base row's fields), then each fragment's fold
+  std::vector<uint64_t> x_slot, x_bno, x_ocn;
+  std::vector<uint32_t> x_bsize;
+  std::vector<uint8_t> x_prev, x_gen, x_cold, x_hh, x_nonce;
+  const uint64_t *f_slot = dec.slot, *f_bno = dec.block_no, *f_ocn = dec.ocert_n;
+  const uint32_t* f_bsize = dec.body_size;
+  const uint8_t *f_prev = dec.prev_hash, *f_gen = dec.prev_is_genesis, *f_cold = dec.cold_vk, *f_hh = dec.header_hash,
+                *f_nonce = nonce_h;
+  if (!extra_base.empty()) {
+    row_len.resize(R2);
+    for (size_t x = 0; x < extra_base.size(); x++) row_len[R + x] = xlen[x];
+  }
+  if (!extra_base.empty() && !have_all) {
+    auto grow = [&](auto& v, const auto* src, size_t rec) {
+      v.resize(rec * R2);
+      std::memcpy(v.data(), src, sizeof(*src) * rec * R);
+      for (size_t x = 0; x < extra_base.size(); x++)
+        std::memcpy(v.data() + rec * (R + x), src + rec * extra_base[x], sizeof(*src) * rec);
+    };
+    grow(x_slot, dec.slot, 1); grow(x_bno, dec.block_no, 1); grow(x_ocn, dec.ocert_n, 1);
+    grow(x_bsize, dec.body_size, 1);
+    grow(x_prev, dec.prev_hash, 32); grow(x_gen, dec.prev_is_genesis, 1); grow(x_cold, dec.cold_vk, 32);
+    grow(x_hh, dec.header_hash, 32); grow(x_nonce, nonce_h, 32);
+    f_slot = x_slot.data(); f_bno = x_bno.data(); f_ocn = x_ocn.data(); f_bsize = x_bsize.data();
+    f_prev = x_prev.data(); f_gen = x_gen.data(); f_cold = x_cold.data(); f_hh = x_hh.data(); f_nonce = x_nonce.data();
+  }
+  if (R2 == 0) {                                 // no row at all: the fold still wants arrays to point at
+    row_eta.assign(1, 0);
+    row_len.assign(1, 0);
+  }
+  std::mutex err_mu;
+  int first_rc = PRAOS_OK;
+  size_t first_j = 0;
+  std::string first_err;
+  par_for(K, [&](size_t j) {
+    praos_fragment& fr = frags->frag[j];
+    const size_t n = F[j + 1] - F[j];
+    const uint32_t* map = out->row + F[j];
+    // the forecast horizon: the client waits at the first header the ledger view does not reach
+    size_t cut = n;
+    for (size_t i = 0; i < n; i++) {
+      const uint32_t r = map[i];
+      if (r == NONE || (bits_h[r] & PRAOS_BIT_INPUT)) break;   // (the fold stops here at the latest)
+      if (f_slot[r] >= in->view_end_slot) { cut = i; break; }
+    }
+    praos_headers h{};
+    h.n = cut;
+    h.slot = f_slot;
+    h.cold_vk = f_cold;
+    h.ocert_n = f_ocn;
+    praos_out crypto{bits_h, pidx_h, nullptr, nullptr, const_cast<uint8_t*>(f_nonce)};
+    praos_envelope env{};
+    env.block_no = f_bno;
+    env.header_hash = f_hh;
+    env.header_size = row_len.data();
+    env.body_size = f_bsize;
+    env.tip_is_origin = fr.tip_is_origin;
+    env.tip_slot = fr.tip_slot;
+    env.tip_block_no = fr.tip_block_no;
+    std::memcpy(env.tip_hash, fr.tip_hash, 32);
+    env.max_major_pv = in->max_major_pv;
+    env.lv_prot_major = in->lv_prot_major;
+    env.max_header_size = in->max_header_size;
+    env.max_body_size = in->max_body_size;
+    size_t stop = 0, done = 0;
+    std::string err;
+    uint8_t* v = out->verdict + F[j];
+    const int rc = rp_fold(c, &h, f_prev, f_gen, &crypto, &env, &in->ei, &fr.state, etas.data(), (uint32_t)etas.size(),
+                           row_eta.data(), evol.data() + F[j], false, nullptr, v, nullptr, &stop, &done, nullptr, map,
+                           true, &err);
+    if (rc != PRAOS_OK) {
+      std::lock_guard<std::mutex> g(err_mu);
+      if (first_rc == PRAOS_OK || j < first_j) { first_rc = rc; first_j = j; first_err = err; }
+      return;
+    }
+    // (a fold that ended on a nonce it did not tick to -- only after a failure -- judged up to done)
+    fr.chain_stop = stop;
+    fr.processed = done;
+    for (size_t i = done; i < n; i++) v[i] = PRAOS_V_NOT_REACHED;
+    fr.tip_is_origin = env.tip_is_origin;
+    fr.tip_slot = env.tip_slot;
+    fr.tip_block_no = env.tip_block_no;
+    std::memcpy(fr.tip_hash, env.tip_hash, 32);
+  });
+  if (first_rc != PRAOS_OK) {
+    praos_set_error_(c, "candidates: fragment " + std::to_string(first_j) + ": " + first_err);
+    return first_rc;
+  }
+
+  // ---- the rows' outputs
+  if (R2) {
+    if (out->rows.bits) std::memcpy(out->rows.bits, bits_h, 2 * R2);
+    if (out->rows.pool_idx) std::memcpy(out->rows.pool_idx, pidx_h, 4 * R2);
+    if (out->rows.beta || out->rows.leader || out->rows.nonce) {
+      praos_out o = out->rows;
+      o.bits = bits_h;                                         // (required there; the same values again)
+      o.pool_idx = nullptr;
+      const int rc = praos_batch_download(c, b, &o);
+      if (rc != PRAOS_OK) return rc;
+    }
+    const int rc = praos_batch_download_decoded(c, b, &out->dec);
+    if (rc != PRAOS_OK) return rc;
+    if (out->eta_idx) std::memcpy(out->eta_idx, row_eta.data(), R2);
+  }
+  return PRAOS_OK;
+}

@@ -2,8 +2,10 @@
 // replay_internal.hpp -- entry points of libpraos_hip used by the replay driver
 // (praos_replay.hip) for its threaded pipeline; C++ linkage, not part of the C ABI.
 #include "praos_hip.h"
+#include <hip/hip_runtime_api.h>
 #include <cstddef>
 #include <cstdint>
+#include <string>
 
 struct praos_span {           // a run of stored bytes in host memory (e.g. an mmapped chunk file)
   const uint8_t* p;
@@ -64,7 +66,25 @@ int rp_fold(praos_ctx* c, const praos_headers* h, const uint8_t* prev_hash, cons
             const praos_out* crypto, praos_envelope* env, const praos_epoch_info* ei, praos_chain_state* st,
             const praos_nonce* etas, uint32_t k, const uint8_t* eta_idx, const praos_nonce* evolving_after,
             bool tpraos, const praos_nonce* extra_entropy, uint8_t* verdict, uint16_t* failures, size_t* chain_stop,
-            size_t* processed, const rp_view* view);
+            size_t* processed, const rp_view* view, const uint32_t* map = nullptr, bool client = false,
+            std::string* err_out = nullptr);
+// map: item i reads row map[i] of every per-header input (PRAOS_NO_ROW: an item without a header,
+// PRAOS_V_INPUT) and keeps index i for verdict / failures / evolving_after; NULL: row i.  client:
+// the ChainSync client's fold (PRAOS_V_DOESNT_FIT before validateHeader; ends at the first
+// failure).  err_out: the error text, instead of the context's (folds running side by side).
+//
+// The candidates call (praos_candidates.hip): a device buffer of at least `bytes` the context keeps
+// between calls (NULL: allocation failed; its earlier contents are gone when it grows), an upload
+// of the spans' concatenation into it (copy stream, pinned staging; dst has room for the bytes
+// rounded up to 8 plus 16, the pad is zeroed), and the decode of rows [first, n) of a replay
+// batch from device span arrays into that arena.
+int rp_device(const praos_ctx* c);
+hipStream_t rp_copy_stream(praos_ctx* c);
+bool rp_have_epoch(const praos_ctx* c);
+uint8_t* rp_scratch(praos_ctx* c, size_t bytes);
+int rp_upload_bytes(praos_ctx* c, uint8_t* dst, const praos_span* spans, size_t nspans);
+int rp_decode_rows(praos_ctx* c, praos_batch* b, const uint8_t* arena, size_t arena_len, const uint64_t* hoff,
+                   const uint32_t* hlen, size_t first, size_t n);
 // The replay of praos_replay_immutable[_tpraos|_views] over m contexts (praos_replay.hip): batch k
 // is uploaded, decoded and verified on mem[k % m]; the nonce chain and the fold run once, in chain
 // order, the fold and the error text on mem[0].  m = 1 is the single-context replay.  views

@@ -51,6 +51,7 @@ V_OK, V_KES_BEFORE_START, V_KES_AFTER_END, V_OCERT_SIG, V_KES_SIG, V_COUNTER_MIS
     V_LEADER_TOO_BIG, V_INPUT, V_ENV_BLOCK_NO, V_ENV_SLOT_NO, V_ENV_PREV_HASH, V_ENV_OBSOLETE_NODE, \
     V_ENV_HEADER_SIZE, V_ENV_BLOCK_SIZE = range(19)
 V_TPRAOS = 19
+V_DOESNT_FIT, V_NOT_REACHED = 25, 255      # praos_validate_candidates (praos_hip.wire)
 # TPraos PRTCL predicate failures (PRAOS_TPF_*)
 TPF_KES_BEFORE_START, TPF_KES_AFTER_END, TPF_OCERT_SIG, TPF_KES_SIG, TPF_COUNTER_MISSING, \
     TPF_COUNTER_TOO_SMALL, TPF_COUNTER_OVER_INC = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40
@@ -425,6 +426,9 @@ SIGNATURES = {
                                        u8p, u8p, u8p]),
     "praos_debug_hash_bytes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, u8p, ctypes.c_size_t,
                                               u64p, u32p, u8p, u64p, ctypes.c_size_t, u8p]),
+    # wire headers (the structs are praos_hip.wire's)
+    "praos_unwrap_wire_headers": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    "praos_validate_candidates": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 _lib = None
