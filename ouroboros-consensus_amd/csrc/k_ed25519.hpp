@@ -126,13 +126,16 @@ __device__ __forceinline__ void kes_leaf_select(uint32_t leaf[8], uint64_t t, co
 }
 
 // kes_prepare with the path dedup: rep / rep_ok = the item's cache entry's representative and
-// its walk verdict (rep_ok null: every item walks)
+// its walk verdict (rep_ok null in every lane: every item walks).  The branch is on the wave:
+// the hit list is grouped by key, so nearly every wave holds equal paths only and skips the six
+// Blake2b compressions altogether; one lane with a path of its own sends its whole wave through
+// the walk (a per-lane branch would run both sides for every wave).
 __device__ __forceinline__ void kes_prepare_dd(const KesIn& a, size_t i, size_t rep, const uint8_t* rep_ok,
                                                uint32_t sg[16], uint32_t leaf[8], uint32_t hram[16],
                                                bool& merkle_ok, bool& in_range) {
   const uint8_t* sig = a.kes_sig + 448 * i;
   const uint64_t t = kes_t(a, i);
-  if (rep_ok && kes_path_same(a, i, rep, t)) {
+  if (rep_ok && __ballot(!kes_path_same(a, i, rep, t)) == 0) {
     merkle_ok = *rep_ok != 0;
     kes_leaf_select(leaf, t, sig);
   } else {

@@ -34,6 +34,8 @@ struct VrfIn {
   int tp_seed;                           // stage V alpha: 0 Praos mkInputVRF; 1 + k TPraos mkSeed
                                          // with ucNonce k (0 seedEta, 1 seedL)
   int pre;                               // join: the pool part ran ahead (k_vrf_pool wrote bits[i])
+  const int32_t* __restrict__ rec_entry; // join / k_vrf_pool: header i's VRF key-cache entry or -1 ...
+  const uint32_t* __restrict__ rec;      // ... and the per-entry pool records (k_vrf_keyrec), or null
 };
 
 // issuer pool: hashKey (Blake2b-224 of the cold vk, Praos.hs:552) -> sorted index or -1
@@ -52,6 +54,52 @@ __device__ __forceinline__ int32_t pool_search(const uint32_t hk[8], const uint3
     if (c < 0) lo = mid + 1; else hi = mid - 1;
   }
   return -1;
+}
+
+// the pool part of a header (Praos.hs:533-541): issuer hash -> pool, the VRF key's hash against
+// the pool's registered one; returns the key bits
+__device__ __forceinline__ uint16_t vrf_pool_part(const VrfIn& a, const uint32_t cv[8], const uint32_t pk[8],
+                                                  int32_t& sidx) {
+  uint32_t hk[8];
+  blake2b_32(hk, cv, 28);
+  sidx = pool_search(hk, a.pool_hash, a.npools);
+  if (sidx < 0) return PRAOS_BIT_VRF_KEY_UNKNOWN;
+  uint32_t vh[8];
+  blake2b_32(vh, pk, 32);
+  bool same = true;
+#pragma unroll
+  for (int k = 0; k < 8; k++) same &= vh[k] == a.pool_vrf[8 * sidx + k];
+  return same ? 0 : PRAOS_BIT_VRF_KEY_WRONG;
+}
+
+// Per-key pool record of the VRF key cache (k_vrf_keyrec, one per entry): the pool part is a
+// function of (cold_vk, vrf_vk), and a cached key's headers nearly always carry one cold key.
+// Words 0..7 the representative's cold key, 8 its sorted pool index, 9 its key bits, 10 its
+// pool index (pool_map), 11 unused (VREC_WORDS, launch.hpp).
+
+// The pool part through the record: rec = the record of the lane's entry (has: the lane has
+// one).  The branch is on the wave: only when every lane's cold key equals its record's are the
+// hashes and the search skipped; one deviant lane sends the whole wave through vrf_pool_part.
+__device__ __forceinline__ uint16_t vrf_pool_part_rec(const VrfIn& a, const uint32_t* __restrict__ rec, bool has,
+                                                      const uint32_t cv[8], const uint32_t pk[8], int32_t& sidx,
+                                                      int32_t& pidx) {
+  uint32_t r[VREC_WORDS];
+#pragma unroll
+  for (int k = 0; k < VREC_WORDS / 4; k++) {
+    const uint4 q = ((const uint4*)rec)[k];
+    r[4 * k] = q.x; r[4 * k + 1] = q.y; r[4 * k + 2] = q.z; r[4 * k + 3] = q.w;
+  }
+  bool same = has;
+#pragma unroll
+  for (int k = 0; k < 8; k++) same &= r[k] == cv[k];
+  if (__ballot(!same) == 0) {
+    sidx = (int32_t)r[8];
+    pidx = (int32_t)r[10];
+    return (uint16_t)r[9];
+  }
+  const uint16_t b = vrf_pool_part(a, cv, pk, sidx);
+  pidx = sidx < 0 ? -1 : a.pool_map[sidx];
+  return b;
 }
 
 // alpha = mkInputVRF(slot, eta) of header i (Praos/VRF.hs:55-69), or for a TPraos

@@ -35,26 +35,21 @@ __global__ void __launch_bounds__(NT, LB_VRF_V) k_vrf_v(size_t n, size_t i0, siz
 template <int CACHED>
 __device__ __forceinline__ void vrf_fin_item(const VrfIn& a, size_t i, size_t stride, const uint4* __restrict__ mid,
                                              const ge_niels* __restrict__ btab, const ge_cached* __restrict__ ktab,
-                                             const uint32_t* __restrict__ kinfo) {
+                                             const uint32_t* __restrict__ kinfo,
+                                             const uint32_t* __restrict__ rec = nullptr) {
   uint32_t pk[8], pr[20];
   load_words(pk, a.vrf_vk + 32 * i, 8);
   load_words(pr, a.vrf_proof + 80 * i, 20);
-  uint16_t b = 0;
-  int32_t sidx;
+  uint16_t b;
+  int32_t sidx, pidx;
   {
-    uint32_t cv[8], hk[8];
+    uint32_t cv[8];
     load_words(cv, a.cold_vk + 32 * i, 8);
-    blake2b_32(hk, cv, 28);
-    sidx = pool_search(hk, a.pool_hash, a.npools);
-    if (sidx < 0) {
-      b |= PRAOS_BIT_VRF_KEY_UNKNOWN;
+    if (CACHED && a.rec) {                     // (rec: the entry's record; a.rec null: no records this run)
+      b = vrf_pool_part_rec(a, rec, true, cv, pk, sidx, pidx);
     } else {
-      uint32_t vh[8];
-      blake2b_32(vh, pk, 32);
-      bool same = true;
-#pragma unroll
-      for (int k = 0; k < 8; k++) same &= vh[k] == a.pool_vrf[8 * sidx + k];
-      if (!same) b |= PRAOS_BIT_VRF_KEY_WRONG;
+      b = vrf_pool_part(a, cv, pk, sidx);
+      pidx = sidx < 0 ? -1 : a.pool_map[sidx];
     }
   }
   uint32_t beta[16];
@@ -79,7 +74,7 @@ __device__ __forceinline__ void vrf_fin_item(const VrfIn& a, size_t i, size_t st
   store_words(a.leader_out + 32 * i, lv, 8);
   store_words(a.nonce_out + 32 * i, nn, 8);
   store_words(a.beta_out + 64 * i, beta, 16);
-  a.pool_idx[i] = sidx < 0 ? -1 : a.pool_map[sidx];
+  a.pool_idx[i] = pidx;
   a.pool_sorted_idx[i] = sidx;
   a.bits[i] = b;
 }
@@ -97,7 +92,8 @@ __global__ void __launch_bounds__(NT, LB_VRF_J) k_vrf_fin(size_t stride, const u
   if (t >= items) return;
   const size_t i = list[t];
   const size_t e = (size_t)item_entry[i];
-  vrf_fin_item<true>(a, i, stride, mid, comb, ktab + e * KT_STRIDE, kinfo + 9 * e);
+  vrf_fin_item<true>(a, i, stride, mid, comb, ktab + e * KT_STRIDE, kinfo + 9 * e,
+                     a.rec ? a.rec + VREC_WORDS * e : nullptr);
 }
 
 // keys of the wide tier (their own hit list): U from the key's positional tables, no doublings
@@ -114,7 +110,8 @@ __global__ void __launch_bounds__(NT, LB_VRF_J) k_vrf_fin_w(size_t stride, const
   if (t >= items) return;
   const size_t i = list[t];
   const size_t e = (size_t)item_entry[i];
-  vrf_fin_item<2>(a, i, stride, mid, comb, wtab + (size_t)entry_wide[e] * WT_STRIDE, kinfo + 9 * e);
+  vrf_fin_item<2>(a, i, stride, mid, comb, wtab + (size_t)entry_wide[e] * WT_STRIDE, kinfo + 9 * e,
+                  a.rec ? a.rec + VREC_WORDS * e : nullptr);
 }
 
 // uncached keys (the miss list, or every header): U on a per-lane chain
@@ -197,23 +194,18 @@ __global__ void __launch_bounds__(NT, LB_VRF_F) k_vrf_u_nc(size_t n, const uint3
 // indices and the leader / nonce values of the stated output (Praos.hs:468-502); returns the
 // key bits
 __device__ __forceinline__ uint16_t vrf_pool_item(const VrfIn& a, size_t i) {
-  uint16_t b = 0;
-  int32_t sidx;
+  uint16_t b;
+  int32_t sidx, pidx;
   {
-    uint32_t pk[8], cv[8], hk[8];
+    uint32_t pk[8], cv[8];
     load_words(cv, a.cold_vk + 32 * i, 8);
-    blake2b_32(hk, cv, 28);
-    sidx = pool_search(hk, a.pool_hash, a.npools);
-    if (sidx < 0) {
-      b |= PRAOS_BIT_VRF_KEY_UNKNOWN;
+    load_words(pk, a.vrf_vk + 32 * i, 8);
+    if (a.rec) {                               // cached VRF keys: the pool part from the key's record
+      const int32_t e = a.rec_entry[i];
+      b = vrf_pool_part_rec(a, a.rec + VREC_WORDS * (size_t)(e < 0 ? 0 : e), e >= 0, cv, pk, sidx, pidx);
     } else {
-      load_words(pk, a.vrf_vk + 32 * i, 8);
-      uint32_t vh[8];
-      blake2b_32(vh, pk, 32);
-      bool same = true;
-#pragma unroll
-      for (int k = 0; k < 8; k++) same &= vh[k] == a.pool_vrf[8 * sidx + k];
-      if (!same) b |= PRAOS_BIT_VRF_KEY_WRONG;
+      b = vrf_pool_part(a, cv, pk, sidx);
+      pidx = sidx < 0 ? -1 : a.pool_map[sidx];
     }
   }
   uint32_t out[16], lv[8], nv[8], nn[8];
@@ -223,9 +215,28 @@ __device__ __forceinline__ uint16_t vrf_pool_item(const VrfIn& a, size_t i) {
   blake2b_32(nn, nv, 32);
   store_words(a.leader_out + 32 * i, lv, 8);
   store_words(a.nonce_out + 32 * i, nn, 8);
-  a.pool_idx[i] = sidx < 0 ? -1 : a.pool_map[sidx];
+  a.pool_idx[i] = pidx;
   a.pool_sorted_idx[i] = sidx;
   return b;
+}
+
+// The pool record of each VRF key-cache entry (VREC_WORDS words, k_vrf.hpp): the pool part of
+// the entry's representative header, one lane per entry.
+__global__ void __launch_bounds__(NT) k_vrf_keyrec(const uint32_t* __restrict__ counters, uint32_t max_entries,
+                                                   const uint32_t* __restrict__ entry_rep, VrfIn a,
+                                                   uint32_t* __restrict__ rec) {
+  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= min(counters[0], max_entries)) return;
+  const size_t i = entry_rep[e];
+  uint32_t cv[8], pk[8];
+  load_words(cv, a.cold_vk + 32 * i, 8);
+  load_words(pk, a.vrf_vk + 32 * i, 8);
+  int32_t sidx;
+  const uint16_t b = vrf_pool_part(a, cv, pk, sidx);
+  uint4* o = (uint4*)(rec + VREC_WORDS * (size_t)e);
+  o[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
+  o[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
+  o[2] = make_uint4((uint32_t)sidx, b, (uint32_t)(sidx < 0 ? -1 : a.pool_map[sidx]), 0u);
 }
 
 // ... ahead of the join (small batches, on a stream with slack): the join's lanes then end
@@ -370,10 +381,11 @@ void launch_vrf_fin(hipStream_t stream, size_t n, const uint32_t* list, const ui
                     const uint8_t* vrf_proof, const uint32_t* pool_hash, const uint32_t* pool_vrf,
                     const int32_t* pool_map, uint32_t npools, int check_output, uint16_t* bits, int32_t* pool_idx,
                     int32_t* pool_sorted_idx, uint8_t* beta_out, uint8_t* leader_out, uint8_t* nonce_out,
-                    ge_cached* tabs, const void* mid, const int32_t* entry_wide) {
-  const VrfIn a = vrf_in(cold_vk, vrf_vk, vrf_out, vrf_proof, nullptr, nullptr, 0, nullptr, pool_hash, pool_vrf,
-                         pool_map, npools, check_output, bits, pool_idx, pool_sorted_idx, beta_out, leader_out,
-                         nonce_out, tabs);
+                    ge_cached* tabs, const void* mid, const int32_t* entry_wide, const uint32_t* rec) {
+  VrfIn a = vrf_in(cold_vk, vrf_vk, vrf_out, vrf_proof, nullptr, nullptr, 0, nullptr, pool_hash, pool_vrf,
+                   pool_map, npools, check_output, bits, pool_idx, pool_sorted_idx, beta_out, leader_out,
+                   nonce_out, tabs);
+  a.rec = ktab ? rec : nullptr;
   const dim3 g((unsigned)((n + NT - 1) / NT));
   if (entry_wide)
     hipLaunchKernelGGL(k_vrf_fin_w, g, dim3(NT), 0, stream, n, list, count, item_entry, entry_wide, ktab, kinfo, comb,
@@ -406,23 +418,37 @@ void launch_vrf_join(hipStream_t stream, size_t n, const uint8_t* cold_vk, const
                      const uint8_t* vrf_out, const uint8_t* vrf_proof, const uint32_t* pool_hash,
                      const uint32_t* pool_vrf, const int32_t* pool_map, uint32_t npools, int check_output,
                      uint16_t* bits, int32_t* pool_idx, int32_t* pool_sorted_idx, uint8_t* beta_out,
-                     uint8_t* leader_out, uint8_t* nonce_out, const void* mid, int wave_prio, int pre) {
+                     uint8_t* leader_out, uint8_t* nonce_out, const void* mid, int wave_prio, int pre,
+                     const int32_t* rec_entry, const uint32_t* rec) {
   VrfIn a = vrf_in(cold_vk, vrf_vk, vrf_out, vrf_proof, nullptr, nullptr, 0, nullptr, pool_hash, pool_vrf,
                    pool_map, npools, check_output, bits, pool_idx, pool_sorted_idx, beta_out, leader_out,
                    nonce_out, nullptr);
   a.wave_prio = wave_prio;
   a.pre = pre;
+  a.rec_entry = rec_entry;
+  a.rec = rec_entry ? rec : nullptr;
   const unsigned bs = lat_block(n);
   hipLaunchKernelGGL(k_vrf_join, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, stream, n, a, (const uint4*)mid);
 }
 void launch_vrf_pool(hipStream_t stream, size_t n, const uint8_t* cold_vk, const uint8_t* vrf_vk,
                      const uint8_t* vrf_out, const uint32_t* pool_hash, const uint32_t* pool_vrf,
                      const int32_t* pool_map, uint32_t npools, uint16_t* bits, int32_t* pool_idx,
-                     int32_t* pool_sorted_idx, uint8_t* leader_out, uint8_t* nonce_out) {
-  const VrfIn a = vrf_in(cold_vk, vrf_vk, vrf_out, nullptr, nullptr, nullptr, 0, nullptr, pool_hash, pool_vrf,
-                         pool_map, npools, 0, bits, pool_idx, pool_sorted_idx, nullptr, leader_out, nonce_out,
-                         nullptr);
+                     int32_t* pool_sorted_idx, uint8_t* leader_out, uint8_t* nonce_out, const int32_t* rec_entry,
+                     const uint32_t* rec) {
+  VrfIn a = vrf_in(cold_vk, vrf_vk, vrf_out, nullptr, nullptr, nullptr, 0, nullptr, pool_hash, pool_vrf,
+                   pool_map, npools, 0, bits, pool_idx, pool_sorted_idx, nullptr, leader_out, nonce_out,
+                   nullptr);
+  a.rec_entry = rec_entry;
+  a.rec = rec_entry ? rec : nullptr;
   hipLaunchKernelGGL(k_vrf_pool, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, stream, n, a);
+}
+void launch_vrf_keyrec(hipStream_t stream, const uint32_t* counters, uint32_t max_entries, const uint32_t* entry_rep,
+                       const uint8_t* cold_vk, const uint8_t* vrf_vk, const uint32_t* pool_hash,
+                       const uint32_t* pool_vrf, const int32_t* pool_map, uint32_t npools, uint32_t* rec) {
+  const VrfIn a = vrf_in(cold_vk, vrf_vk, nullptr, nullptr, nullptr, nullptr, 0, nullptr, pool_hash, pool_vrf,
+                         pool_map, npools, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  hipLaunchKernelGGL(k_vrf_keyrec, dim3((max_entries + NT - 1) / NT), dim3(NT), 0, stream, counters, max_entries,
+                     entry_rep, a, rec);
 }
 void launch_vrf_join_tp(hipStream_t stream, size_t n, int cert, const uint8_t* cold_vk, const uint8_t* vrf_vk,
                         const uint8_t* cert_out, const uint8_t* cert_proof, const uint32_t* pool_hash,

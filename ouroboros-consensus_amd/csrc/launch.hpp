@@ -165,7 +165,8 @@ void launch_vrf_fin(hipStream_t stream, size_t n, const uint32_t* list, const ui
                     const int32_t* pool_map, uint32_t npools, int check_output, uint16_t* bits, int32_t* pool_idx,
                     int32_t* pool_sorted_idx, uint8_t* beta_out, uint8_t* leader_out, uint8_t* nonce_out,
                     ge_cached* tabs, const void* mid,
-                    const int32_t* entry_wide = nullptr);   // list = a wide hit list, ktab = the wide tables
+                    const int32_t* entry_wide = nullptr,    // list = a wide hit list, ktab = the wide tables
+                    const uint32_t* rec = nullptr);         // cached keys: the entries' pool records (launch_vrf_keyrec)
 // three-kernel VRF: stage U (cached: ktab != null, k_vrf_u over the hit list; uncached: k_vrf_u_nc
 // over list[0 .. *count) or all n, 8-entry lane tables utabs) and the join over all n
 void launch_vrf_u(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count, const int32_t* item_entry,
@@ -182,12 +183,22 @@ void launch_vrf_join(hipStream_t stream, size_t n, const uint8_t* cold_vk, const
                      const uint32_t* pool_vrf, const int32_t* pool_map, uint32_t npools, int check_output,
                      uint16_t* bits, int32_t* pool_idx, int32_t* pool_sorted_idx, uint8_t* beta_out,
                      uint8_t* leader_out, uint8_t* nonce_out, const void* mid, int wave_prio = 0,
-                     int pre = 0);                         // pre: launch_vrf_pool ran before (bits, pool, leader, nonce)
+                     int pre = 0,                          // pre: launch_vrf_pool ran before (bits, pool, leader, nonce)
+                     const int32_t* rec_entry = nullptr,   // the VRF key cache's item_entry and pool records
+                     const uint32_t* rec = nullptr);       // (launch_vrf_keyrec), or null
 // the join's pool part ahead of it (k_vrf_stage.hip k_vrf_pool): key bits, pool indices, leader / nonce
 void launch_vrf_pool(hipStream_t stream, size_t n, const uint8_t* cold_vk, const uint8_t* vrf_vk,
                      const uint8_t* vrf_out, const uint32_t* pool_hash, const uint32_t* pool_vrf,
                      const int32_t* pool_map, uint32_t npools, uint16_t* bits, int32_t* pool_idx,
-                     int32_t* pool_sorted_idx, uint8_t* leader_out, uint8_t* nonce_out);
+                     int32_t* pool_sorted_idx, uint8_t* leader_out, uint8_t* nonce_out,
+                     const int32_t* rec_entry = nullptr, const uint32_t* rec = nullptr);   // as launch_vrf_join
+// the pool record of each VRF key-cache entry (k_vrf_stage.hip k_vrf_keyrec; VREC_WORDS words per
+// entry): the pool part of the entry's representative, which the entry's headers with the same
+// cold key take instead of hashing and searching themselves
+#define VREC_WORDS 12
+void launch_vrf_keyrec(hipStream_t stream, const uint32_t* counters, uint32_t max_entries, const uint32_t* entry_rep,
+                       const uint8_t* cold_vk, const uint8_t* vrf_vk, const uint32_t* pool_hash,
+                       const uint32_t* pool_vrf, const int32_t* pool_map, uint32_t npools, uint32_t* rec);
 // TPraos join of certificate cert (0: eta, 1: leader; k_vrf_stage.hip k_vrf_join_tp), after
 // stage V (tp_seed 1 + cert) and U of that certificate into `mid`
 void launch_vrf_join_tp(hipStream_t stream, size_t n, int cert, const uint8_t* cold_vk, const uint8_t* vrf_vk,

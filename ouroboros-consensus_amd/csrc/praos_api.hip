@@ -124,6 +124,13 @@ static constexpr size_t KEY_PRIO_BATCH = 400000;
 // (profiles/r04/y: 96k 4.06 -> 3.64 ms, 108k 4.25 -> 4.10, 112k 4.39 -> 4.15; equal at 120k,
 // slower at 128k)
 static constexpr size_t ILP4_BATCH = 120000;
+// from this many headers on the KES Merkle walk runs once per leaf-key entry (PRAOS_KES_DEDUP -1).
+// Medians of alternating runs, ms per step without / with it, beside the other cuts of DESIGN
+// section 24: 432k 9.907 -> 9.847 (eight runs each, every run with it below every run without);
+// 300k 7.170 -> 7.231 and 160k 4.058 -> 4.117 (four each): slower, the step there is not bound
+// by the instruction count; the KES-only configs[3] 9.355 -> 9.413, inside its spread
+// (profiles/r08_perkey_ab.json)
+static constexpr size_t KES_DEDUP_BATCH = 400000;
 // Byron header batches (praos_verify_pbft_headers) below this many headers verify uncached: the
 // delegate keys' precompute chain (250 doublings, then the table pass) is pure latency there.
 // Measured on an MI355X (tools/pbft_bench.py: 7 delegates in turn, a freshly opened context per
@@ -216,15 +223,24 @@ struct praos_ctx {
   long kes_pair = -1;                                  // k_kes_ck two headers per lane from this many hits on
                                                        // (PRAOS_KES_PAIR, 0 = never; -1: from 196,608 when the
                                                        // KES pass runs alone -- beside the OCert / VRF passes
-                                                       // the longer paired waves cost the C5 step 2 %,
-                                                       // profiles/r04/i: 12.15 -> 12.40 ms, C4 6.43 -> 6.10 ms)
+                                                       // the paired kernel has 4 % fewer VALU instructions
+                                                       // (0.983 G -> 0.941 G per 432k step) and the step is
+                                                       // longer, 9.847 -> 10.113 ms, medians of eight
+                                                       // alternating runs, profiles/r08_perkey_ab.json; its
+                                                       // waves are twice as long and spill 176 bytes per lane)
   uint32_t kes_pair_min() const {
     return kes_pair >= 0 ? (uint32_t)kes_pair : ((kernels & 5) ? 0u : 196608u);
   }
-  int kes_dedup = 0;                                   // KES Merkle path dedup per leaf-key entry (PRAOS_KES_DEDUP):
-                                                       // off, measured slower (C4 10.7 -> 11.2 ms: the
-                                                       // representatives' walks lengthen the KES chain more than
-                                                       // the skipped walks save; C5 unchanged, profiles/r04/r)
+  int kes_dedup = -1;                                  // KES Merkle path dedup per leaf-key entry (PRAOS_KES_DEDUP
+                                                       // 1 / 0): the representatives walk once, a wave of
+                                                       // k_kes_ck whose paths all equal theirs skips the walk;
+                                                       // -1: from KES_DEDUP_BATCH headers on
+  bool use_kes_dedup(size_t n) const { return kes_dedup > 0 || (kes_dedup < 0 && n >= KES_DEDUP_BATCH); }
+  int vrf_perkey = 1;                                  // pool record per VRF key-cache entry (k_vrf_keyrec): a
+                                                       // wave of the cached stage F / the join whose cold keys
+                                                       // all equal their records' skips the two Blake2b and the
+                                                       // pool search (PRAOS_VRF_PERKEY 1 / 0)
+  hipEvent_t vrec_ev = nullptr;                        // the VRF key records are written (k_vrf_keyrec)
   int v_main = -1;                                     // stage V on the main stream (PRAOS_V_MAIN; 0 off): no
                                                        // cross-stream wait between the previous run's end and V;
                                                        // the join after U and V on the VRF stream (3), or on the
@@ -563,6 +579,7 @@ struct praos_batch {
     uint32_t *counters = nullptr, *hit = nullptr, *miss = nullptr;   // counters: entries, hits, misses
     ge_cached* ktab = nullptr;
     uint8_t* rep_ok = nullptr;   // KES leaf keys: the Merkle walk verdict of each entry's representative
+    uint32_t* vrec = nullptr;    // VRF keys: the pool record of each entry (k_vrf_keyrec, VREC_WORDS words)
     // this run's entry space: the arrays above, or the context's pool-key store
     ge_cached* kt = nullptr;
     uint32_t *ki = nullptr, *erep = nullptr, *epos = nullptr;
@@ -719,6 +736,8 @@ static bool open_streams(praos_ctx* c) {
   if (const char* e = std::getenv("PRAOS_U4")) c->u4 = std::atoi(e);
   if (const char* e = std::getenv("PRAOS_CK4")) c->ck4 = std::atoi(e);
   if (const char* e = std::getenv("PRAOS_KES_DEDUP")) c->kes_dedup = std::atoi(e);
+  if (const char* e = std::getenv("PRAOS_VRF_PERKEY")) c->vrf_perkey = std::atoi(e);
+  (void)hipEventCreateWithFlags(&c->vrec_ev, hipEventDisableTiming);
   if (const char* e = std::getenv("PRAOS_POOL_KEYS")) (void)praos_set_option(c, PRAOS_OPT_POOL_KEYS, std::atoi(e));
   if (const char* e = std::getenv("PRAOS_VRF_KEYS_FIRST")) c->vrf_keys_first = std::atoi(e);
   if (const char* e = std::getenv("PRAOS_VRF_WIDE")) (void)praos_set_vrf_wide(c, std::atoi(e), c->vrf_wide_cap);
@@ -800,6 +819,9 @@ praos_ctx* praos_open(int device) {
     praos_close(c);
     return nullptr;
   }
+  // (the check below reads the thread's last error: drop one that an earlier call of this thread
+  // left, such as an argument check on a host-only context)
+  (void)hipGetLastError();
   launch_init_btab(dim3(BCOMB_TABLES * BTAB_N / 256), dim3(256), c->stream, c->btab);
   if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
     fprintf(stderr, "praos_open: init kernel failed\n");
@@ -870,6 +892,7 @@ void praos_close(praos_ctx* c) {
   if (c->v_ev) (void)hipEventDestroy(c->v_ev);
   if (c->v0_ev) (void)hipEventDestroy(c->v0_ev);
   if (c->u_ev) (void)hipEventDestroy(c->u_ev);
+  if (c->vrec_ev) (void)hipEventDestroy(c->vrec_ev);
   if (c->v1_ev) (void)hipEventDestroy(c->v1_ev);
   if (c->kc0_ev) (void)hipEventDestroy(c->kc0_ev);
   if (c->kc1_ev) (void)hipEventDestroy(c->kc1_ev);
@@ -1089,7 +1112,7 @@ void praos_batch_free(praos_ctx* c, praos_batch* b) {
 }
 
 // one public-key cache (k_keys.hip) for batches of up to n items
-static bool alloc_keycache(praos_batch* b, praos_batch::KeyCache& k, size_t n) {
+static bool alloc_keycache(praos_batch* b, praos_batch::KeyCache& k, size_t n, bool vrf = false) {
   bool ok = true;
   k.cap = 256;
   while (k.cap < 2 * n) k.cap <<= 1;
@@ -1107,6 +1130,7 @@ static bool alloc_keycache(praos_batch* b, praos_batch::KeyCache& k, size_t n) {
   ok &= dalloc(b, &k.kinfo, 36 * (size_t)k.max_entries) == hipSuccess;
   ok &= dalloc(b, (uint8_t**)&k.ktab, KT_BYTES * k.max_entries) == hipSuccess;
   ok &= dalloc(b, &k.rep_ok, (size_t)k.max_entries) == hipSuccess;
+  if (vrf) ok &= dalloc(b, &k.vrec, 4 * (size_t)VREC_WORDS * k.max_entries) == hipSuccess;
   return ok;
 }
 
@@ -1146,7 +1170,7 @@ static bool alloc_soa(praos_batch* b, size_t n, size_t body_arena_bytes) {
   ok &= dalloc(b, &b->dd_reps, 4 * n) == hipSuccess;
   ok &= dalloc(b, &b->dd_counters, 16) == hipSuccess;
   ok &= dalloc(b, &b->dd_ok, n) == hipSuccess;
-  for (auto& k : b->kc) ok &= alloc_keycache(b, k, n);
+  for (auto& k : b->kc) ok &= alloc_keycache(b, k, n, &k == &b->kc[1]);
   return ok;
 }
 
@@ -1614,15 +1638,27 @@ static int batch_run_impl(praos_ctx* c, praos_batch* b) {
   // started 0.33 ms into a 54k-header step, behind the OCert and KES lists)
   const bool vrf3 = do_vrf && !b->tp_only && (c->vrf3 > 0 || (c->vrf3 < 0 && n < 300000));
   bool vrf_keys_queued = false;
+  // pool records of the VRF key cache's entries (k_vrf_keyrec), set once this run's lists are queued;
+  // not for the pool-key store's entries (their representatives are headers of earlier runs)
+  const uint32_t* vrec = nullptr;
+  auto queue_vrec = [&](praos_batch::KeyCache& k) {
+    if (!c->vrf_perkey || k.store >= 0 || !k.vrec) return;
+    launch_vrf_keyrec(sm_[2], k.counters, k.max_entries, k.entry_rep, b->cold_vk, b->vrf_vk, c->d_pool_hash,
+                      c->d_pool_vrf, c->d_pool_map, c->npools, k.vrec);
+    vrec = k.vrec;
+  };
   const bool pre_join = vrf3 && kc && (c->pre_join > 0 || (c->pre_join < 0 && n < SMALL_BATCH));
   auto vrf_keys = [&]() -> int {
     praos_batch::KeyCache& k = b->kc[1];
     int r = keycache_lists(k, b->vrf_vk, sv);
     if (r == PRAOS_OK) r = to_main(2, sv);
     if (r != PRAOS_OK) return r;
+    // (the records head the miss stream: the join and k_vrf_pool follow them there or wait for u_ev)
+    queue_vrec(k);
     if (pre_join)
       launch_vrf_pool(sm_[2], n, b->cold_vk, b->vrf_vk, b->vrf_out, c->d_pool_hash, c->d_pool_vrf, c->d_pool_map,
-                      c->npools, bv, b->pool_idx, b->pool_sorted, b->leader, b->nonce);
+                      c->npools, bv, b->pool_idx, b->pool_sorted, b->leader, b->nonce, vrec ? k.item_entry : nullptr,
+                      vrec);
     launch_vrf_u(sm_[2], n, k.miss, k.counters + 2, nullptr, nullptr, nullptr, c->bcomb16, c->btab, b->vrf_vk,
                  b->vrf_proof, b->tab_vrfu, b->vrf_mid);
     if (sm_[2] != sv) HIPCHK(c, hipEventRecord(c->u_ev, sm_[2]));
@@ -1734,6 +1770,12 @@ static int batch_run_impl(praos_ctx* c, praos_batch* b) {
       int r = keycache_lists(k, b->kes_leaf, sk);
       if (r == PRAOS_OK) r = to_main(1, sk);
       if (r != PRAOS_OK) return r;
+      // Merkle path dedup: a pool's headers of one KES period carry the same hot key, period and
+      // six vk pairs, so each cache entry's representative walks once and equal paths reuse it.
+      // The walks stay on the KES stream ahead of the key precompute: on the miss stream, on a
+      // stream of their own or behind the misses, with k_kes_ck waiting for their event, the 432k
+      // step was 0.06-0.09 ms longer (profiles/r08_perkey_ab.json, kes_walks_placement)
+      const bool kes_dd = c->use_kes_dedup(n);
       if (c->use_miss4(n))
         launch_kes4(g, blk, sm_[1], k.miss, k.counters + 2, c->btab, b->hot_vk, b->kes_sig, b->body_off, b->body_len,
                     b->body, b->body_bytes_len, b->slot, b->ocert_c0, P.slots_per_kes_period, bk, b->tab_kes,
@@ -1742,22 +1784,20 @@ static int batch_run_impl(praos_ctx* c, praos_batch* b) {
         launch_kes(g, blk, sm_[1], n, k.miss, k.counters + 2, c->btab, b->hot_vk, b->kes_sig, b->body_off,
                    b->body_len, b->body, b->body_bytes_len, b->slot, b->ocert_c0, P.slots_per_kes_period,
                    (const uint32_t*)nullptr, bk, (uint8_t*)nullptr, b->tab_kes);
-      // Merkle path dedup: a pool's headers of one KES period carry the same hot key, period and
-      // six vk pairs, so each cache entry's representative walks once and equal paths reuse it
-      if (c->kes_dedup)
+      if (kes_dd)
         launch_kes_merkle_reps(sk, k.counters, k.max_entries, k.entry_rep, b->hot_vk, b->kes_sig, b->slot,
                                b->ocert_c0, P.slots_per_kes_period, k.rep_ok);
       keycache_precompute(k, b->kes_leaf, 0, sk);
       HIPCHK(c, hipEventRecord(c->kc0_ev, sk));
-      if (c->use_ck4(n) && !c->kes_pair_min() && !c->kes_dedup)
+      if (c->use_ck4(n) && !c->kes_pair_min() && !kes_dd)
         launch_kes_ck4(sk, n, k.hit, k.counters + 1, k.item_entry, k.kt, k.ki, c->bcomb16, b->hot_vk, b->kes_sig,
                        b->body_off, b->body_len, b->body, b->body_bytes_len, b->slot, b->ocert_c0,
                        P.slots_per_kes_period, bk);
       else
         launch_kes_ck(gl, bl, sk, k.hit, k.counters + 1, k.item_entry, k.kt, k.ki, c->bcomb16, b->hot_vk, b->kes_sig,
                       b->body_off, b->body_len, b->body, b->body_bytes_len, b->slot, b->ocert_c0,
-                      P.slots_per_kes_period, bk, c->kes_pair_min(), c->kes_dedup ? k.entry_rep : nullptr,
-                      c->kes_dedup ? k.rep_ok : nullptr, 0);
+                      P.slots_per_kes_period, bk, c->kes_pair_min(), kes_dd ? k.entry_rep : nullptr,
+                      kes_dd ? k.rep_ok : nullptr, 0);
       HIPCHK(c, hipEventRecord(c->kc1_ev, sk));
       c->kes_ck_timed = true;
     } else {
@@ -1841,7 +1881,7 @@ static int batch_run_impl(praos_ctx* c, praos_batch* b) {
                      k ? k->ki : nullptr, c->bcomb16, c->btab, b->cold_vk, b->vrf_vk, b->vrf_out, b->vrf_proof,
                      c->d_pool_hash, c->d_pool_vrf, c->d_pool_map, c->npools, (int)P.vrf_check_output, bv, b->pool_idx,
                      b->pool_sorted, b->beta, b->leader, b->nonce, b->tab_vrf, b->vrf_mid,
-                     wide ? k->wide.entry_wide : nullptr);
+                     wide ? k->wide.entry_wide : nullptr, k ? vrec : nullptr);
     };
     auto stage_u = [&](hipStream_t st, const uint32_t* list, const uint32_t* count, const praos_batch::KeyCache* k) {
       launch_vrf_u(st, n, list, count, k ? k->item_entry : nullptr, k ? k->kt : nullptr, k ? k->ki : nullptr,
@@ -1850,7 +1890,8 @@ static int batch_run_impl(praos_ctx* c, praos_batch* b) {
     auto join = [&](hipStream_t st) {
       launch_vrf_join(st, n, b->cold_vk, b->vrf_vk, b->vrf_out, b->vrf_proof, c->d_pool_hash, c->d_pool_vrf,
                       c->d_pool_map, c->npools, (int)P.vrf_check_output, bv, b->pool_idx, b->pool_sorted, b->beta,
-                      b->leader, b->nonce, b->vrf_mid, wprio, pre_join ? 1 : 0);
+                      b->leader, b->nonce, b->vrf_mid, wprio, pre_join ? 1 : 0,
+                      vrec && kc ? b->kc[1].item_entry : nullptr, vrec);
     };
     if (vrf3) {
       // three kernels: U runs beside V (uncached keys at once on the miss stream, cached keys
@@ -1878,8 +1919,13 @@ static int batch_run_impl(praos_ctx* c, praos_batch* b) {
       praos_batch::KeyCache& k = b->kc[1];
       int r = keycache_lists(k, b->vrf_vk, sv);
       if (r == PRAOS_OK) r = to_main(2, sv);
-      if (r == PRAOS_OK) r = after_v(sm_[2]);
       if (r != PRAOS_OK) return r;
+      // the entries' pool records: on the miss stream ahead of its wait for stage V, off the chain
+      // lists -> precompute -> tables that the cached F waits for; sv joins them after its tables
+      queue_vrec(k);
+      const bool vrec_wait = vrec && sm_[2] != sv;
+      if (vrec_wait) HIPCHK(c, hipEventRecord(c->vrec_ev, sm_[2]));
+      if ((r = after_v(sm_[2])) != PRAOS_OK) return r;
       fin(sm_[2], k.miss, k.counters + 2, nullptr);
       keycache_precompute(k, b->vrf_vk, 1, sv);
       if (k.wide.min_uses && sm_[2] != sv) {
@@ -1891,9 +1937,11 @@ static int batch_run_impl(praos_ctx* c, praos_batch* b) {
         HIPCHK(c, hipStreamWaitEvent(sm_[2], c->u_ev, 0));
         fin(sm_[2], k.hit, k.counters + 1, &k);
         if ((r = after_v(sv)) != PRAOS_OK) return r;
+        if (vrec_wait) HIPCHK(c, hipStreamWaitEvent(sv, c->vrec_ev, 0));
         fin(sv, k.wide.hit, k.wide.wcnt + 1, &k, true);
       } else {
         if ((r = after_v(sv)) != PRAOS_OK) return r;
+        if (vrec_wait) HIPCHK(c, hipStreamWaitEvent(sv, c->vrec_ev, 0));
         if (k.wide.min_uses) fin(sv, k.wide.hit, k.wide.wcnt + 1, &k, true);
         fin(sv, k.hit, k.counters + 1, &k);
       }

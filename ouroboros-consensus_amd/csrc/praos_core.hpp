@@ -521,19 +521,15 @@ FE_INLINE void vrf_v_core(uint4* __restrict__ mid, size_t stride, size_t i, cons
     ge_enc_affine(gs, G);
     mid_put(mid, stride, i, VRF_MID_GS, gs);
     mid[(size_t)VRF_MID_FLAGS * stride + i] = make_uint4(gamma_ok ? 1u : 0u, 0u, 0u, 0u);
-    ge_p3 G2, G4;
-    ge_p3_dbl_to_p3(G2, G);
-    ge_p3_dbl_to_p3(G4, G2);
-    ge_p1p1 t;
-    ge_p2 q;
-    ge_p3_to_p2(q, G4);
-    ge_p2_dbl(t, q);
-    ge_p2 G8;
-    ge_p1p1_to_p2(G8, t);
-    mid_put_xyz(mid, stride, i, VRF_MID_G8, G8.X, G8.Y, G8.Z);
+    // 8 Gamma is the negative of the {1..8}(-Gamma) table's last point: the additions are complete,
+    // so it is the point three doublings of Gamma give, in other projective coordinates (the
+    // encoding the join takes is the same); 24 products fewer per header
     fe_neg(G.X, G.X);
     fe_neg(G.T, G.T);
-    build_cached_table(vt + 8, G);
+    ge_p3 G8;
+    build_cached_table(vt + 8, G, &G8);
+    fe_neg(G8.X, G8.X);
+    mid_put_xyz(mid, stride, i, VRF_MID_G8, G8.X, G8.Y, G8.Z);
   }
   uint32_t sx[16], s[8], c[8], sw[8], cw[8];
 #pragma unroll
