@@ -1263,6 +1263,26 @@ int praos_debug_hash_bytes(praos_ctx* ctx, int kind, size_t n, const uint8_t* ar
                            const uint64_t* off, const uint32_t* len, const uint8_t* aux, const uint64_t* parts,
                            size_t n_parts, uint8_t* out);
 
+/* ---- addition (ABI stays 15): self test of the integer routines under every verdict: scalars
+ * mod L (sc25519.hpp), the signed-digit recoders (scalarmult.hpp) and the Fixed E34 helpers of the
+ * leader check (leader.hpp).  One item per lane runs the product routine unchanged.  a, b, c, out:
+ * n*32 bytes, eight 32-bit words LE per item; arrays an op does not read may be null.
+ *   op 0  sc_reduce256    a mod L                                             out 8 words
+ *   op 1  sc_muladd       (a * b + c) mod L, any 256-bit a, b, c               out 8 words
+ *   op 2  sc_is_canonical a < L                                               out word 0 = 0 / 1
+ *   op 3  sc_recode16     a + 0x88..88, a < 2^253                              out 8 words
+ *   op 4  sc_recode256    a + 0x80..80, a < 2^253                              out 8 words
+ *   op 5  sc_recode65536  a + 0x8000..8000, a < 2^253                          out 8 words
+ *   op 6  sc_recode64     a + sum_k 32 * 64^k (k < 22), a < 2^128              out 5 words
+ *   op 7  fx_div_R        floor(a / 10^34), any 256-bit a                      out 8 words
+ *   op 8  mp_div_small    floor(a / k), k = word 0 of b, 2 <= k < 65536        out 8 words
+ * Words of out an op does not write are 0.  (x mod L for 512-bit x is praos_debug_sc_reduce.)
+ * PRAOS_E_ARG, with nothing launched and praos_last_error naming the function: an unknown op, a
+ * null array the op reads when n > 0, a scalar outside the recoder's range (ops 3 .. 6), a divisor
+ * outside 2 .. 65535 (op 8).  n = 0 is PRAOS_OK.  PRAOS_E_STATE on a host-only context. */
+int praos_debug_int(praos_ctx* ctx, int op, size_t n, const uint8_t* a, const uint8_t* b, const uint8_t* c,
+                    uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

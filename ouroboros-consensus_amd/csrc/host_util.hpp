@@ -113,7 +113,10 @@ inline void ceil_div_256_128(uint8_t q_le[16], const u256& x, unsigned __int128 
 
 // x_raw = -floor(sigma_fp * c_raw / R) = ceil(sigma_fp * |c| / R) for c_raw <= 0.
 // Rejected above X_MAX = 16 R: the device Taylor loop (leader.hpp) keeps err * x in
-// 256 bits, and err_n <= R e^X, so err * x <= R^2 X e^X < 2^226 * 2^28 for X <= 16
+// 256 bits.  err_n does not depend on the leader value, and over the recurrence at
+// x = 16 R the largest err_n * x is 14106527.2 R^2 (n = 14), 250 bits, 1.2 % of 2^256;
+// tests/leader_cases.py runs the device up to n = 13 there (13224869.3 R^2, 250 bits; no
+// case at 16 R runs longer) and through the negative acc' - e of every x >= 2 R
 // (sigma |ln(1-f)| <= 16 covers every f <= 1 - e^-16).
 inline bool leader_x_raw(uint8_t x_le[16], const uint8_t sigma_fp[16], const uint8_t c_raw[16]) {
   unsigned __int128 c;

@@ -1,5 +1,6 @@
 // k_selftest.hpp -- self-test kernels of the field, group and scalar-multiplication layers
-// (praos_debug_fe_multi, praos_debug_fe ops 9.., praos_debug_ge, praos_debug_msm), shared by
+// (praos_debug_fe_multi, praos_debug_fe ops 9.., praos_debug_ge, praos_debug_msm) and of the
+// integer routines under them (praos_debug_int, default build only), shared by
 // the default build (k_selftest.hip) and the ILP-4 build (k_selftest4.hip, PRAOS_ILP4 = 1).
 // They call the routines of fe25519.hpp / ge25519.hpp / scalarmult.hpp with the templates and
 // arguments of the product code and return raw limbs or encodings; no product kernel is touched.
@@ -269,6 +270,47 @@ __global__ void __launch_bounds__(NT) k_selftest_msm(size_t n, const uint8_t* __
   store_words(out + 32 * i, enc, 8);
 }
 
+#if !PRAOS_ILP4
+// praos_debug_int: one integer routine per lane (sc25519.hpp, the recoders of scalarmult.hpp, the
+// Fixed E34 helpers of leader.hpp), 32 bytes per item and array; the host checks the preconditions
+//   op 0 sc_reduce256   1 sc_muladd   2 sc_is_canonical   3, 4, 5 sc_recode16 / 256 / 65536
+//   op 6 sc_recode64 (5 words)   7 fx_div_R   8 mp_div_small by word 0 of b
+template <int BUILD>
+__global__ void __launch_bounds__(64) k_selftest_int(int op, size_t n, const uint8_t* __restrict__ a,
+                                                     const uint8_t* __restrict__ b, const uint8_t* __restrict__ c,
+                                                     uint8_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t x[8], y[8], z[8], r[8];
+  load_words(x, a + 32 * i, 8);
+#pragma unroll
+  for (int k = 0; k < 8; k++) { y[k] = 0; z[k] = 0; r[k] = 0; }
+  if (op == 1) {
+    load_words(y, b + 32 * i, 8);
+    load_words(z, c + 32 * i, 8);
+  }
+  if (op == 8) load_words(y, b + 32 * i, 8);
+  switch (op) {
+    case 0: sc_reduce256(r, x); break;
+    case 1: sc_muladd(r, x, y, z); break;
+    case 2: r[0] = sc_is_canonical(x) ? 1u : 0u; break;
+    case 3: sc_recode16(r, x); break;
+    case 4: sc_recode256(r, x); break;
+    case 5: sc_recode65536(r, x); break;
+    case 6: {
+      uint32_t w[5];
+      sc_recode64(w, x);
+#pragma unroll
+      for (int k = 0; k < 5; k++) r[k] = w[k];
+    } break;
+    case 7: fx_div_R(r, x); break;
+    case 8: mp_div_small(r, x, y[0]); break;
+    default: break;
+  }
+  store_words(out + 32 * i, r, 8);
+}
+#endif
+
 // ---- host launchers
 void ST_LAUNCH(ge)(hipStream_t stream, int op, size_t n, const uint8_t* p, const uint8_t* q, uint8_t* out,
                    const ge_niels* gbtab) {
@@ -302,5 +344,9 @@ void launch_selftest_fe_multi(hipStream_t stream, int op, size_t n, const uint8_
 }
 void launch_selftest_fe(hipStream_t stream, int op, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* r) {
   hipLaunchKernelGGL(k_selftest_fe<0>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, op, n, a, b, r);
+}
+void launch_selftest_int(hipStream_t stream, int op, size_t n, const uint8_t* a, const uint8_t* b, const uint8_t* c,
+                         uint8_t* out) {
+  hipLaunchKernelGGL(k_selftest_int<0>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, op, n, a, b, c, out);
 }
 #endif

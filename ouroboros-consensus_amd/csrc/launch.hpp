@@ -263,6 +263,8 @@ void launch_vrf_nonce(hipStream_t stream, size_t n, const uint8_t* vrf_out, int 
 // launch_selftest4_* forms come from the ILP-4 build, k_selftest4.hip)
 void launch_selftest_fe_multi(hipStream_t stream, int op, size_t n, const uint8_t* in, uint8_t* out);
 void launch_selftest_fe(hipStream_t stream, int op, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* r);
+void launch_selftest_int(hipStream_t stream, int op, size_t n, const uint8_t* a, const uint8_t* b, const uint8_t* c,
+                         uint8_t* out);
 void launch_selftest_ge(hipStream_t stream, int op, size_t n, const uint8_t* p, const uint8_t* q, uint8_t* out,
                         const ge_niels* gbtab);
 void launch_selftest4_ge(hipStream_t stream, int op, size_t n, const uint8_t* p, const uint8_t* q, uint8_t* out,

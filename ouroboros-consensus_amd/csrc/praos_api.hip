@@ -4849,4 +4849,38 @@ int praos_debug_hash_bytes(praos_ctx* c, int kind, size_t n, const uint8_t* aren
   return PRAOS_OK;
 }
 
+int praos_debug_int(praos_ctx* c, int op, size_t n, const uint8_t* a, const uint8_t* b, const uint8_t* cc,
+                    uint8_t* out) {
+  if (!c) return PRAOS_E_ARG;
+  auto bad = [&](const std::string& what) {
+    c->err = "praos_debug_int: " + what;
+    return PRAOS_E_ARG;
+  };
+  if (op < 0 || op > 8) return bad("unknown op " + std::to_string(op));
+  if (n == 0) return PRAOS_OK;
+  if (n > (1u << 24)) return bad("more than 2^24 items");
+  if (!a || !out || (op == 1 && (!b || !cc)) || (op == 8 && !b)) return bad("null array");
+  // the routines' documented ranges (scalarmult.hpp, leader.hpp)
+  if (op >= 3 && op <= 5 && !scalars_below(a, n, 253)) return bad("scalar not below 2^253");
+  if (op == 6 && !scalars_below(a, n, 128)) return bad("scalar not below 2^128");
+  for (size_t i = 0; i < n && op == 8; i++) {
+    uint32_t k;
+    std::memcpy(&k, b + 32 * i, 4);
+    if (k < 2 || k >= 65536) return bad("divisor outside 2..65535, item " + std::to_string(i));
+  }
+  if (c->device < 0) { c->err = "host-only context: no HIP device"; return PRAOS_E_STATE; }
+  HIPCHK(c, hipSetDevice(c->device));
+  Scratch s(c);
+  auto da = s.up(a, 32 * n);
+  auto db = (op == 1 || op == 8) ? s.up(b, 32 * n) : (uint8_t*)nullptr;
+  auto dc = op == 1 ? s.up(cc, 32 * n) : (uint8_t*)nullptr;
+  auto dout = s.zeros<uint8_t>(32 * n);
+  if (!s.ok) return PRAOS_E_OOM;
+  launch_selftest_int(c->stream, op, n, da, db, dc, dout);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, dout, 32 * n, hipMemcpyDeviceToHost));
+  return PRAOS_OK;
+}
+
 }  // extern "C"

@@ -426,6 +426,7 @@ SIGNATURES = {
                                        u8p, u8p, u8p]),
     "praos_debug_hash_bytes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, u8p, ctypes.c_size_t,
                                               u64p, u32p, u8p, u64p, ctypes.c_size_t, u8p]),
+    "praos_debug_int": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, u8p, u8p, u8p, u8p]),
     # wire headers (the structs are praos_hip.wire's)
     "praos_unwrap_wire_headers": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "praos_validate_candidates": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -1425,6 +1426,14 @@ class Context:
         self.check(self.L.praos_debug_hash_bytes(self.h, kind, n, ptr(a) if len(a) else None, len(a), ptr(off, u64p),
                                                  ptr(length, u32p), ptr(aux), ptr(parts, u64p),
                                                  len(parts) if parts is not None else 0, ptr(out)))
+        return out
+
+    def debug_int(self, op, a, b=None, c=None):
+        """One integer routine per item (ops: praos_hip.h).  a, b, c (n, 32) uint8, eight LE words
+        each -> (n, 32)."""
+        a, b, c = [np.ascontiguousarray(x, np.uint8) if x is not None else None for x in (a, b, c)]
+        out = np.zeros((len(a), 32), np.uint8)
+        self.check(self.L.praos_debug_int(self.h, op, len(a), ptr(a), ptr(b), ptr(c), ptr(out)))
         return out
 
 

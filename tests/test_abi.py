@@ -301,3 +301,55 @@ def test_hash_bytes_entry_point_and_argument_checks():
         assert b"praos_debug_hash_bytes" in c.L.praos_last_error(c.h)
     finally:
         c.close()
+
+
+def test_debug_int_entry_point_and_argument_checks():
+    """praos_debug_int is declared after praos_debug_hash_bytes, bound with its 7 arguments and
+    reachable from Context; the ABI version did not move; its argument checks need no device and
+    come before anything is uploaded or launched; the kernel sits beside the other self tests."""
+    import numpy as np
+    from praos_hip import abi
+    assert "praos_debug_int" in _declared() and callable(abi.Context.debug_int)
+    assert len(abi.SIGNATURES["praos_debug_int"][1]) == 7
+    hdr = open(abi.HEADER_PATH).read()
+    assert hdr.index("praos_debug_hash_bytes(") < hdr.index("praos_debug_int(")
+    assert int(re.search(r"#define PRAOS_ABI_VERSION (\d+)", hdr).group(1)) == 15
+    csrc = os.path.join(os.path.dirname(abi.LIB_PATH), "csrc")
+    assert "k_selftest_int" in open(os.path.join(csrc, "k_selftest.hpp")).read()
+    E_STATE = -4
+    c = abi.Context(abi.HOST_ONLY)
+    try:
+        val = lambda *v: np.frombuffer(b"".join(int(x).to_bytes(32, "little") for x in v), np.uint8).copy()
+        out = np.zeros(2 * 32, np.uint8)
+
+        def call(op, n, a=None, b=None, cc=None, h=c.h, o=out):
+            return c.L.praos_debug_int(h, op, n, abi.ptr(a), abi.ptr(b), abi.ptr(cc), abi.ptr(o))
+
+        one = val(1)
+        assert call(0, 1, one, h=None) == abi.E_ARG
+        for op in (-1, 9):
+            assert call(op, 1, one, one, one) == abi.E_ARG
+            assert call(op, 0) == abi.E_ARG
+        assert b"praos_debug_int" in c.L.praos_last_error(c.h)
+        for op in range(9):                                                   # n = 0 needs no array
+            assert call(op, 0) == 0
+        # well-formed calls get as far as the device check
+        for op in (0, 2, 3, 4, 5, 6, 7):
+            assert call(op, 1, one) == E_STATE
+        assert call(1, 1, one, one, one) == E_STATE
+        assert call(8, 2, val(7, 2 ** 256 - 1), val(2, 65535)) == E_STATE
+        assert call(3, 1, val(2 ** 253 - 1)) == E_STATE and call(6, 1, val(2 ** 128 - 1)) == E_STATE
+        # null arrays the op reads
+        assert call(0, 1) == abi.E_ARG and call(0, 1, one, o=None) == abi.E_ARG
+        assert call(1, 1, one, one) == abi.E_ARG and call(1, 1, one, None, one) == abi.E_ARG
+        assert call(8, 1, one) == abi.E_ARG
+        # preconditions: the recoders' ranges, the divisor's
+        for op in (3, 4, 5):
+            assert call(op, 2, val(1, 2 ** 253)) == abi.E_ARG
+            assert call(op, 1, val(2 ** 255)) == abi.E_ARG
+        assert call(6, 2, val(1, 2 ** 128)) == abi.E_ARG and call(6, 1, val(2 ** 255)) == abi.E_ARG
+        for k in (0, 1, 65536, 2 ** 32 - 1):
+            assert call(8, 2, val(9, 9), val(2, k)) == abi.E_ARG
+        assert b"praos_debug_int" in c.L.praos_last_error(c.h)
+    finally:
+        c.close()
