@@ -47,8 +47,13 @@ DEC_OVERFLOW = 0x40
 MAX_PROT_MAJOR = 9
 DEC_FAIL = 0x5F               # every bit but NONCANONICAL
 
-SIGNED_STRIDE = 448           # max canonical body = 447 bytes
-TP_SIGNED_STRIDE = 640        # max canonical TPraos BHBody = 598 bytes
+# Longest canonical body the decoder accepts (every integer at its maximum, bodySize a
+# Word32, protMajor <= MAX_PROT_MAJOR, so one byte): 439 bytes (Praos), 586 (TPraos);
+# tests/test_decode_cases.py builds both.  The 447 and 598 quoted before were upper bounds
+# that ignore limits the decoder enforces: 447 = 439 with a 9-byte protMajor, 598 = 586 with
+# a 9-byte protMajor and a 9-byte bodySize.  Neither length can be a decoded header's.
+SIGNED_STRIDE = 448           # max canonical body = 439 bytes
+TP_SIGNED_STRIDE = 640        # max canonical TPraos BHBody = 586 bytes
 
 
 class _Fail(Exception):
@@ -116,7 +121,10 @@ class _R:
 
 def _head(mt, v, wide=False):
     """Shortest-form CBOR head (cborg's encoders); wide=True gives the 8-byte (or
-    for lengths 2-byte) non-canonical form that cborg's decoders still accept."""
+    for lengths 2-byte) non-canonical form that cborg's decoders still accept, wide =
+    24..27 the 1-, 2-, 4- or 8-byte form."""
+    if wide is not True and wide:
+        return bytes([(mt << 5) | wide]) + v.to_bytes(1 << (wide - 24), "big")
     if wide:
         return bytes([(mt << 5) | 27]) + v.to_bytes(8, "big") if mt == 0 else \
             bytes([(mt << 5) | 25]) + v.to_bytes(2, "big")
@@ -128,35 +136,44 @@ def _head(mt, v, wide=False):
     raise ValueError(v)
 
 
+def _wide(wide):
+    return (lambda k: wide.get(k, False)) if isinstance(wide, dict) else (lambda k: k in wide)
+
+
 def encode_body(f, wide=()):
     """Canonical EncCBOR HeaderBody (Header.hs:160-185).  `wide` names fields to
     encode with non-shortest heads (test corpora only): any field name, or
-    'body' / 'vrf' / 'ocert' / 'pv' for the array heads."""
+    'body' / 'vrf' / 'ocert' / 'pv' for the array heads; a dict {name: 24..27} picks the
+    width per head."""
+    w = _wide(wide)
+
     def u(k):
-        return _head(0, f[k], k in wide)
+        return _head(0, f[k], w(k))
 
     def b(k):
-        return _head(2, len(f[k]), k in wide) + f[k]
+        return _head(2, len(f[k]), w(k)) + f[k]
     prev = b"\xf6" if f["prev_hash"] is None else b("prev_hash")
     return b"".join([
-        _head(4, 10, "body" in wide), u("block_no"), u("slot"), prev, b("cold_vk"), b("vrf_vk"),
-        _head(4, 2, "vrf" in wide), b("vrf_out"), b("vrf_proof"), u("body_size"), b("body_hash"),
-        _head(4, 4, "ocert" in wide), b("hot_vk"), u("n"), u("c0"), b("ocert_sig"),
-        _head(4, 2, "pv" in wide), u("prot_major"), u("prot_minor")])
+        _head(4, 10, w("body")), u("block_no"), u("slot"), prev, b("cold_vk"), b("vrf_vk"),
+        _head(4, 2, w("vrf")), b("vrf_out"), b("vrf_proof"), u("body_size"), b("body_hash"),
+        _head(4, 4, w("ocert")), b("hot_vk"), u("n"), u("c0"), b("ocert_sig"),
+        _head(4, 2, w("pv")), u("prot_major"), u("prot_minor")])
 
 
 def encode_tpraos_body(f, wide=()):
     """Canonical encodeBHBody (15 fields; the OCert and ProtVer groups inlined)."""
+    w = _wide(wide)
+
     def u(k):
-        return _head(0, f[k], k in wide)
+        return _head(0, f[k], w(k))
 
     def b(k):
-        return _head(2, len(f[k]), k in wide) + f[k]
+        return _head(2, len(f[k]), w(k)) + f[k]
     prev = b"\xf6" if f["prev_hash"] is None else b("prev_hash")
     return b"".join([
-        _head(4, 15, "body" in wide), u("block_no"), u("slot"), prev, b("cold_vk"), b("vrf_vk"),
-        _head(4, 2, "vrf" in wide), b("vrf_out"), b("vrf_proof"),
-        _head(4, 2, "leader" in wide), b("leader_out"), b("leader_proof"),
+        _head(4, 15, w("body")), u("block_no"), u("slot"), prev, b("cold_vk"), b("vrf_vk"),
+        _head(4, 2, w("vrf")), b("vrf_out"), b("vrf_proof"),
+        _head(4, 2, w("leader")), b("leader_out"), b("leader_proof"),
         u("body_size"), b("body_hash"), b("hot_vk"), u("n"), u("c0"), b("ocert_sig"),
         u("prot_major"), u("prot_minor")])
 
@@ -170,7 +187,9 @@ def decode_header(arena, off, length, allow_tpraos=False):
     """Decode header bytes arena[off:off+length].  Returns a dict with 'status',
     the fields (None on failure), 'signed' (canonical body bytes, b'' on failure),
     'header_hash' (Blake2b-256 of the stored bytes; zeros on DEC_RANGE) and 'tpraos'
-    (the body had 15 fields; only accepted with allow_tpraos, the block path)."""
+    (the body had 15 fields; only accepted with allow_tpraos, the block path).
+    allow_tpraos=2: TPraos headers only (praos_verify_tpraos_header_bytes): the body
+    must have 15 fields, as k_decode.hip's allow_tp == 2."""
     out = {"status": 0, "fields": None, "signed": b"", "header_hash": bytes(32), "tpraos": False}
     if off > len(arena) or length > len(arena) - off:
         out["status"] = DEC_RANGE
@@ -183,7 +202,7 @@ def decode_header(arena, off, length, allow_tpraos=False):
         body_start = r.pos
         r.canon = True
         arity = r.expect(4)
-        tp = allow_tpraos and arity == 15
+        tp = allow_tpraos == 2 or (bool(allow_tpraos) and arity == 15)
         if arity != (15 if tp else 10):
             raise _Fail(DEC_SYNTAX)
         f = {"block_no": r.uint(), "slot": r.uint()}

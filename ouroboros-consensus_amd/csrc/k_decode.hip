@@ -22,7 +22,11 @@
 // ProtVer inlined), the integrity check of Shelley/Protocol/TPraos.hs:59-76.  The eta
 // certificate goes to vrf_out/vrf_proof; the leader certificate is only needed to
 // re-encode a non-canonical body and is then read back from the arena.  Signed
-// bodies of block batches use a 640-byte stride (max canonical BHBody 598 bytes).
+// bodies of block batches use a 640-byte stride.  The longest canonical body this decoder
+// accepts has every integer at its maximum with bodySize a Word32 (5 bytes) and protMajor <=
+// PRAOS_MAX_PROT_MAJOR (1 byte): 439 bytes (Praos), 586 (TPraos BHBody); both are built by
+// tests/decode_cases.py.  (447 and 598, quoted here before, ignore those limits: 447 = 439
+// with a 9-byte protMajor, 598 = 586 with a 9-byte protMajor and a 9-byte bodySize.)
 //
 // Memory: every field load goes through ld64u (two aligned 8-byte loads and a
 // funnel shift), so a lane walks its ~850-byte header with 8-byte accesses;
@@ -217,8 +221,8 @@ __global__ void __launch_bounds__(NT) k_decode_praos(size_t i0, size_t n, const 
   uint32_t slen = 0xffffffffu;
   if (!r.st) {
     if (canon) {
-      // signed bytes = the stored slice (<= 447 bytes for a canonical Praos body,
-      // <= 598 for TPraos)
+      // signed bytes = the stored slice (<= 439 bytes for a canonical Praos body,
+      // <= 586 for TPraos)
       slen = (uint32_t)(body_end - body_start);
       uint64_t* d = (uint64_t*)sb;
       for (uint32_t k = 0; k < slen; k += 8) {

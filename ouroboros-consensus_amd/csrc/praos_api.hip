@@ -15,7 +15,7 @@ static constexpr size_t C16_TABLES = 16, C16_ENTRIES = 32768;   // radix-2^16 co
 static constexpr size_t CACHED_BYTES = 4 * 32;     // sizeof(ge_cached)
 static constexpr size_t LT_ED_B = 8 * CACHED_BYTES, LT_VRF_B = 16 * CACHED_BYTES;   // per-lane tables (kcommon.hpp)
 static constexpr size_t VRF_MID_BYTES = 28 * 16;    // per-header records of the staged VRF (praos_core.hpp)
-static constexpr uint32_t TP_SIGNED_STRIDE = 640;   // max canonical TPraos BHBody: 598 bytes (k_decode.hip)
+static constexpr uint32_t TP_SIGNED_STRIDE = 640;   // max canonical TPraos BHBody: 586 bytes (k_decode.hip)
 
 #include <pthread.h>
 #include <sched.h>
@@ -1989,7 +1989,7 @@ static bool block_batch_buffers(praos_batch* b) {
   ok &= dalloc(b, &b->seg_hash, 32 * 4 * n) == hipSuccess;
   ok &= dalloc(b, &b->blk_result, n) == hipSuccess;
   ok &= dalloc(b, &b->blk_hash, 32 * n) == hipSuccess;
-  // TPraos BHBody signed bodies are up to 598 bytes: a wider stride than header batches
+  // TPraos BHBody signed bodies are up to 586 bytes: a wider stride than header batches
   b->signed_stride = TP_SIGNED_STRIDE;
   b->body_bytes_len = (size_t)TP_SIGNED_STRIDE * n;
   ok &= dalloc(b, &b->body, b->body_bytes_len + 16) == hipSuccess;

@@ -62,10 +62,12 @@ def rand_segments(r, big=False, pad=0):
     return [bodies, wits, aux, inval]
 
 
-def make_block(r, spkp, era=6, slot=None, c0=None, big=False, wrapped=True, pad=0, segs=None):
+def make_block(r, spkp, era=6, slot=None, c0=None, big=False, wrapped=True, pad=0, segs=None, wide=()):
     """-> (block bytes, header fields, KES seed).  era 2..5: a TPraos block (15-field
     BHBody; 3 segments for Shelley/Allegra/Mary, 4 for Alonzo); 6/7: Praos.  segs: the
-    four segments (each one CBOR item) instead of random ones."""
+    four segments (each one CBOR item) instead of random ones.  wide: heads of the stored body
+    to encode non-shortest (as the oracle's encoders take it); the signature stays over the
+    canonical body, as the node forms it."""
     tp = era in bi.TPRAOS_ERAS
     segs = rand_segments(r, big, pad) if segs is None else list(segs)
     if era in (2, 3, 4):
@@ -85,6 +87,8 @@ def make_block(r, spkp, era=6, slot=None, c0=None, big=False, wrapped=True, pad=
         f["leader_out"], f["leader_proof"] = rbytes(r, 64), rbytes(r, 80)
     body = ch.encode_tpraos_body(f) if tp else ch.encode_body(f)
     kes = orc.kes_sign(seed, min(t, 63), body)  # t > 63: verification must reject
+    if wide:
+        body = ch.encode_tpraos_body(f, wide) if tp else ch.encode_body(f, wide)
     hdr = H(4, 2) + body + H(2, len(kes)) + kes
     inner = H(4, 1 + len(segs)) + hdr + b"".join(segs)
     blk = (H(4, 2) + H(0, era) + inner) if wrapped else inner
