@@ -1037,6 +1037,99 @@ typedef struct {
 int praos_validate_candidates(praos_ctx* ctx, const praos_candidates_in* in, praos_fragments* frags,
                               praos_candidates_out* out);
 
+/* The same call for the TPraos eras (Shelley .. Alonzo, wire indices 1 to 4; additive: ABI version
+ * unchanged).  in: praos_candidates_in's fields with tpraos_eras (a bit mask of wire indices, 0 =
+ * indices 1 to 4) in the place of praos_eras, and extra_entropy (TICKN's, may be NULL, as
+ * praos_replay_immutable_tpraos takes it): each fragment's speculative nonce chain combines it at
+ * every epoch tick, so two fragments that differ only in what they tick to land on different rows.
+ * Fragments are praos_fragments.  The rows are decoded as praos_verify_tpraos_header_bytes decodes
+ * them (the 15-field BHBody; dec's signed_body has the PRAOS_TP_SIGNED_STRIDE stride) and verified
+ * by its kernels under the per-row nonces; the overlay installed with praos_set_overlay applies.
+ *   verdict[i]: PRAOS_V_DOESNT_FIT before the envelope; then the envelope verdicts; then
+ *   PRAOS_V_TPRAOS with failures[i] = the PRAOS_TPF_* set (0 with every other verdict);
+ *   PRAOS_V_INPUT / PRAOS_V_NOT_REACHED as above.
+ * rows_cap, n_rows, eta_idx, etas, n_etas, stats and the two PRAOS_E_ARG cases as above. */
+typedef struct {
+  praos_header_bytes items;       /* N wire items, fragment after fragment */
+  uint32_t n_eras;                /* eras of the block type (7) */
+  uint32_t tpraos_eras;           /* bit mask of the wire indices judged here; 0 = indices 1 to 4 */
+  uint64_t view_end_slot;         /* first slot the ledger view does not cover */
+  praos_epoch_info ei;
+  uint64_t max_major_pv;          /* the envelope limits (praos_envelope) */
+  uint64_t lv_prot_major;
+  uint64_t max_header_size;
+  uint64_t max_body_size;
+  const praos_nonce* extra_entropy; /* may be NULL */
+} praos_tpraos_candidates_in;
+typedef struct {
+  uint8_t* wire_status;           /* N: PRAOS_WIRE_* */
+  uint32_t* row;                  /* N: the item's row, PRAOS_NO_ROW when it has none */
+  uint8_t* verdict;               /* N */
+  uint16_t* failures;             /* N, may be NULL: PRAOS_TPF_* of an item judged PRAOS_V_TPRAOS, else 0 */
+  size_t rows_cap;
+  size_t n_rows;                  /* out */
+  praos_tpraos_out rows;          /* rows_cap per array (any may be NULL) */
+  praos_decoded dec;              /* rows_cap per array; signed_body at PRAOS_TP_SIGNED_STRIDE */
+  uint8_t* leader_out;            /* rows_cap*64, may be NULL */
+  uint8_t* leader_proof;          /* rows_cap*80, may be NULL */
+  uint8_t* eta_idx;               /* rows_cap, may be NULL: the row's nonce, index into etas */
+  praos_nonce* etas;              /* 256, may be NULL */
+  uint32_t n_etas;                /* out */
+  uint64_t stats[5];              /* out: items, unwrapped TPraos items, distinct headers, rows, extra rows */
+} praos_tpraos_candidates_out;
+int praos_validate_candidates_tpraos(praos_ctx* ctx, const praos_tpraos_candidates_in* in, praos_fragments* frags,
+                                     praos_tpraos_candidates_out* out);
+
+/* The same for K candidate fragments of Byron wire headers (wire index 0), each from its own tip
+ * and PBftState (additive: ABI version unchanged).  The items are unwrapped, hashed and
+ * deduplicated on the device as above -- the key is (era 0, Blake2b-256(82 0k || header)), so the
+ * same bytes sent as EBB and as main header are two rows, and size_hint is no part of it -- then
+ * praos_verify_pbft_headers' kernels run once per row, straight from the wire arena, under its
+ * rules (delegs: the Bimap, a duplicate in either column is PRAOS_E_ARG; PRAOS_OPT_KEYCACHE and
+ * praos_pbft_stats apply to the rows), and each fragment is folded on the host as
+ * praos_pbft_update_chain_dep_state folds, in the client's mode:
+ *   verdict[i]: PRAOS_V_INPUT for an item that did not unwrap, is not of era 0 or whose header
+ *   has PRAOS_PBFT_BIT_DECODE; PRAOS_V_DOESNT_FIT when the header's prev hash is not the
+ *   fragment's tip hash (at an Origin tip: not the genesis hash), checked before the envelope, so
+ *   never PRAOS_V_ENV_PREV_HASH; else the fold's verdict and aux.  The fold ends at the first
+ *   failure; items after it, and the items from the first slot >= view_end_slot on, are
+ *   PRAOS_V_NOT_REACHED (aux 0).  processed / chain_stop as in praos_fragment; tip and state on
+ *   return are those at chain_stop.  Every state needs cap >= window_size > 0.
+ * Rows are numbered by first appearance; there is no nonce, so rows = distinct headers.
+ * PRAOS_E_ARG: rows_cap too small (n_rows = the count needed), before any signature is verified. */
+typedef struct {
+  praos_header_bytes items;       /* N wire items, fragment after fragment */
+  uint32_t n_eras;                /* eras of the block type (7) */
+  uint32_t n_delegs;
+  uint64_t view_end_slot;         /* first slot the ledger view does not cover */
+  praos_pbft_params params;
+  const uint8_t* delegs;          /* n_delegs * 56 */
+} praos_pbft_candidates_in;
+typedef struct {
+  praos_pbft_tip tip;             /* in / out */
+  praos_pbft_state state;         /* in / out; cap >= window_size */
+  size_t chain_stop;              /* out: relative to the fragment's first item */
+  size_t processed;               /* out */
+} praos_pbft_fragment;
+typedef struct {
+  size_t k;
+  const size_t* frag_first;       /* k + 1 */
+  praos_pbft_fragment* frag;      /* k */
+} praos_pbft_fragments;
+typedef struct {
+  uint8_t* wire_status;           /* N: PRAOS_WIRE_* */
+  uint32_t* row;                  /* N: the item's row, PRAOS_NO_ROW when it has none */
+  uint8_t* verdict;               /* N */
+  uint64_t* aux;                  /* N, may be NULL: as praos_pbft_update_chain_dep_state reports it */
+  size_t rows_cap;
+  size_t n_rows;                  /* out */
+  praos_pbft_out rows;            /* rows_cap per array; any may be NULL */
+  uint8_t* row_is_ebb;            /* rows_cap, may be NULL: the row's Byron kind is 0 */
+  uint64_t stats[4];              /* out: items, unwrapped Byron items, distinct headers (= rows), signature verifies run */
+} praos_pbft_candidates_out;
+int praos_validate_candidates_pbft(praos_ctx* ctx, const praos_pbft_candidates_in* in, praos_pbft_fragments* frags,
+                                   praos_pbft_candidates_out* out);
+
 /* ---- several GPUs from one process ----
  * A group = one context per entry of devices[] (a device may repeat: several
  * contexts on one GPU), each driven by its own host thread.  Batch calls split the

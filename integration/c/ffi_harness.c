@@ -10,6 +10,8 @@
  *   ffi_harness --validate-chunk-byron <immutable dir> <chunk no> <slots per KES period> <byron epoch slots> <pm>
  *   ffi_harness --pbft-headers <immutable dir> <window> <threshold> <byron epoch slots> <pm> <delegs file>
  *   ffi_harness --candidates <immutable dir> <epoch file> <fragments file>
+ *   ffi_harness --candidates-tpraos <immutable dir> <epoch file> <fragments file>
+ *   ffi_harness --candidates-pbft <immutable dir> <window> <threshold> <byron epoch slots> <pm> <delegs file> <fragments file>
  *
  * --candidates: the ChainSync candidates call as Batch.hs validateCandidateFragments runs it.  The
  *   database's headers are wrapped in the node-to-node encoding here ([5, #6.24(bytes)], the Babbage
@@ -20,6 +22,19 @@
  *   one JSON object: per fragment the verdicts, chain_stop, processed, the tip and the PraosState CBOR
  *   at the stop; the stats; and praos_unwrap_wire_headers' inner spans of the same items relative to
  *   each item's start.
+ *
+ * --candidates-tpraos: the same over a TPraos database (the epoch file has a "tpraos" line), as
+ *   Batch.hs validateCandidateFragmentsTPraos runs it: the headers wrapped as [4, #6.24(bytes)] (the
+ *   Alonzo wire index), praos_validate_candidates_tpraos with the epoch file's extra entropy; the
+ *   output has the phase "candidates_tpraos" and, per fragment, the items' PRAOS_TPF_* sets.
+ *
+ * --candidates-pbft: the Byron call as Batch.hs validateCandidateFragmentsPBft runs it.  The blocks
+ *   of the database's chunk files, in order, are the chain; block h's header is wrapped as
+ *   [0, [[kind, headerSize], #6.24(bytes)]] and the fragments file lists
+ *     frag <first header> <count> <state: encodePBftState hex> <tip: origin | slot:block_no:hash hex:is_ebb>
+ *     view_end <slot>
+ *   Prints per fragment the verdicts, aux, rows, chain_stop, processed, the tip and the PBftState
+ *   CBOR at the stop, and the stats.
  *
  * --validate-chunk: parseChunkFile as one call, as Batch.hs validateChunkBatch runs it: the chunk
  *   file as read, the secondary index's checksums and block offsets when the index is there and
@@ -1124,9 +1139,11 @@ static int pbft_headers_main(const char* dir, uint64_t window, uint64_t threshol
   return 0;
 }
 
-/* --candidates (see the head of this file) */
-static int candidates_main(const char* dir, const char* epoch_file, const char* frag_file) {
+/* --candidates / --candidates-tpraos (see the head of this file) */
+static int candidates_main(const char* dir, const char* epoch_file, const char* frag_file, int tpraos) {
   read_epoch_file(epoch_file);
+  if (tpraos != g_tpraos) DIE("--candidates%s: the epoch file is %sa TPraos one", tpraos ? "-tpraos" : "", g_tpraos ? "" : "not ");
+  const uint8_t wire_era = tpraos ? 4 : 5;
   chain_t ch;
   read_chain(dir, &ch);
   enum { MAXF = 16 };
@@ -1180,7 +1197,7 @@ static int candidates_main(const char* dir, const char* epoch_file, const char* 
         acap = 2 * (alen + hl + 7);
         arena = realloc(arena, acap);
       }
-      const uint8_t pre[7] = {0x82, 0x05, 0xd8, 0x18, 0x59, (uint8_t)(hl >> 8), (uint8_t)hl};
+      const uint8_t pre[7] = {0x82, wire_era, 0xd8, 0x18, 0x59, (uint8_t)(hl >> 8), (uint8_t)hl};
       memcpy(arena + alen, pre, 7);
       memcpy(arena + alen + 7, ch.bytes + ch.off[h], hl);
       ioff[i] = alen;
@@ -1207,17 +1224,38 @@ static int candidates_main(const char* dir, const char* epoch_file, const char* 
   out.row = calloc(N + 1, 4);
   out.verdict = calloc(N + 1, 1);
   out.rows_cap = N;
-  CK(ctx, praos_validate_candidates(ctx, &in, &fs, &out));
+  uint16_t* failures = calloc(N + 1, 2);
+  if (tpraos) {
+    /* praos_tpraos_candidates_in: the same fields, then TICKN's extra entropy; the out struct has
+     * the failure sets and no per-row output is asked for */
+    praos_tpraos_candidates_in tin;
+    memset(&tin, 0, sizeof tin);
+    tin.items = in.items; tin.n_eras = 7; tin.view_end_slot = view_end; tin.ei = g_ei;
+    tin.max_major_pv = in.max_major_pv; tin.lv_prot_major = in.lv_prot_major;
+    tin.max_header_size = in.max_header_size; tin.max_body_size = in.max_body_size;
+    tin.extra_entropy = &g_extra;
+    praos_tpraos_candidates_out tout;
+    memset(&tout, 0, sizeof tout);
+    tout.wire_status = out.wire_status; tout.row = out.row; tout.verdict = out.verdict; tout.failures = failures;
+    tout.rows_cap = N;
+    CK(ctx, praos_validate_candidates_tpraos(ctx, &tin, &fs, &tout));
+    out.n_rows = tout.n_rows;
+    out.n_etas = tout.n_etas;
+    memcpy(out.stats, tout.stats, sizeof out.stats);
+  } else {
+    CK(ctx, praos_validate_candidates(ctx, &in, &fs, &out));
+  }
   /* the stand-alone unwrap of the same items */
   praos_wire_out wo = {calloc(N + 1, 1), calloc(N + 1, 1), calloc(N + 1, 1), calloc(N + 1, 4), calloc(N + 1, 8),
                        calloc(N + 1, 4), NULL};
   CK(ctx, praos_unwrap_wire_headers(ctx, &in.items, 7, &wo));
   int spans_ok = 1;
   for (size_t q = 0; q < N; q++)
-    spans_ok &= wo.status[q] == PRAOS_WIRE_OK && wo.era[q] == 5 && wo.byron_kind[q] == 0xff &&
+    spans_ok &= wo.status[q] == PRAOS_WIRE_OK && wo.era[q] == wire_era && wo.byron_kind[q] == 0xff &&
                 wo.off[q] == ioff[q] + 7 && wo.len[q] + 7 == ilen[q] && out.wire_status[q] == PRAOS_WIRE_OK;
-  printf("{\"phase\": \"candidates\", \"items\": %zu, \"spans_ok\": %d, \"n_rows\": %zu, \"n_etas\": %u, \"stats\": "
-         "[%llu, %llu, %llu, %llu, %llu], \"fragments\": [", N, spans_ok, out.n_rows, out.n_etas,
+  printf("{\"phase\": \"%s\", \"items\": %zu, \"spans_ok\": %d, \"n_rows\": %zu, \"n_etas\": %u, \"stats\": "
+         "[%llu, %llu, %llu, %llu, %llu], \"fragments\": [", tpraos ? "candidates_tpraos" : "candidates", N, spans_ok,
+         out.n_rows, out.n_etas,
          (unsigned long long)out.stats[0], (unsigned long long)out.stats[1], (unsigned long long)out.stats[2],
          (unsigned long long)out.stats[3], (unsigned long long)out.stats[4]);
   static uint8_t buf[64 + 48 * CAP];
@@ -1232,6 +1270,175 @@ static int candidates_main(const char* dir, const char* epoch_file, const char* 
     hex_out(buf, len);
     printf("\", \"verdicts\": [");
     for (size_t q = first[j]; q < first[j + 1]; q++) printf("%s%u", q > first[j] ? ", " : "", out.verdict[q]);
+    printf("], \"rows\": [");
+    for (size_t q = first[j]; q < first[j + 1]; q++) printf("%s%u", q > first[j] ? ", " : "", out.row[q]);
+    if (tpraos) {
+      printf("], \"failures\": [");
+      for (size_t q = first[j]; q < first[j + 1]; q++) printf("%s%u", q > first[j] ? ", " : "", failures[q]);
+    }
+    printf("]}");
+  }
+  printf("]}\n");
+  fflush(stdout);
+  praos_close(ctx);
+  return 0;
+}
+
+/* --candidates-pbft (see the head of this file) */
+static int candidates_pbft_main(const char* dir, uint64_t window, uint64_t threshold, uint64_t es, uint32_t pm,
+                                const char* delegs_file, const char* frag_file) {
+  uint8_t* delegs = NULL;
+  uint32_t nd = 0;
+  FILE* f = fopen(delegs_file, "r");
+  if (!f) DIE("cannot open %s", delegs_file);
+  char g[128], d[128];
+  while (fscanf(f, "%120s %120s", g, d) == 2) {
+    delegs = realloc(delegs, 56 * (size_t)(nd + 1));
+    hex_in(g, delegs + 56 * (size_t)nd, 28);
+    hex_in(d, delegs + 56 * (size_t)nd + 28, 28);
+    nd++;
+  }
+  fclose(f);
+  /* the chain: every block of every chunk file, its header span and kind */
+  uint8_t** hdr = NULL;
+  uint32_t* hlen = NULL;
+  uint8_t* kind = NULL;
+  size_t nh = 0;
+  for (int chunk = 0;; chunk++) {
+    char p[4096];
+    size_t dl = 0, sl = 0;
+    snprintf(p, sizeof p, "%s/%05d.chunk", dir, chunk);
+    uint8_t* data = slurp(p, &dl);
+    if (!data) break;
+    snprintf(p, sizeof p, "%s/%05d.secondary", dir, chunk);
+    uint8_t* sec = slurp(p, &sl);
+    if (!sec || sl % PRAOS_CHUNK_ENTRY_SIZE) DIE("chunk %d: missing or malformed secondary index", chunk);
+    const size_t n = sl / PRAOS_CHUNK_ENTRY_SIZE;
+    hdr = realloc(hdr, (nh + n + 1) * sizeof *hdr);
+    hlen = realloc(hlen, (nh + n + 1) * sizeof *hlen);
+    kind = realloc(kind, nh + n + 1);
+    for (size_t i = 0; i < n; i++) {
+      const uint8_t* e = sec + PRAOS_CHUNK_ENTRY_SIZE * i;
+      const uint64_t bo = be(e, 8), ho = bo + be(e + 8, 2), hl = be(e + 10, 2);
+      if (bo + 2 > dl || ho + hl > dl) DIE("chunk %d entry %zu outside the chunk file", chunk, i);
+      hdr[nh] = data + ho;                         /* (the chunk's bytes stay allocated) */
+      hlen[nh] = (uint32_t)hl;
+      kind[nh] = data[bo + 1] == 0 ? 0 : 1;
+      nh++;
+    }
+    free(sec);
+  }
+  enum { MAXF = 16 };
+  const size_t cap = window ? (size_t)window : 1;
+  praos_pbft_fragment* fr = calloc(MAXF, sizeof *fr);
+  size_t first[MAXF + 1], from[MAXF], count[MAXF], K = 0, N = 0;
+  uint64_t view_end = ~0ull;
+  f = fopen(frag_file, "r");
+  if (!f) DIE("cannot open %s", frag_file);
+  static char line[1 << 20], st_hex[1 << 20], tip[256];
+  while (fgets(line, sizeof line, f)) {
+    unsigned long long a, b;
+    if (sscanf(line, "view_end %llu", &a) == 1) { view_end = a; continue; }
+    if (sscanf(line, "frag %llu %llu %1048575s %255s", &a, &b, st_hex, tip) != 4) continue;
+    if (K == MAXF) DIE("too many fragments");
+    if (a + b > nh) DIE("fragment %zu outside the chain", K);
+    from[K] = (size_t)a;
+    count[K] = (size_t)b;
+    fr[K].state.cap = cap;
+    fr[K].state.slot = calloc(cap, 8);
+    fr[K].state.genesis_hash = calloc(cap, 28);
+    const size_t sl = strlen(st_hex) / 2;
+    uint8_t* enc = malloc(sl + 1);
+    hex_in(st_hex, enc, sl);
+    if (praos_pbft_state_decode(enc, sl, &fr[K].state) != PRAOS_OK) DIE("fragment %zu: praos_pbft_state_decode", K);
+    free(enc);
+    if (strcmp(tip, "origin") == 0) {
+      fr[K].tip.origin = 1;
+    } else {
+      unsigned long long ts, tb;
+      unsigned te;
+      char hh[128];
+      if (sscanf(tip, "%llu:%llu:%64[0-9a-f]:%u", &ts, &tb, hh, &te) != 4) DIE("fragment %zu: tip", K);
+      fr[K].tip.slot = ts;
+      fr[K].tip.block_no = tb;
+      fr[K].tip.is_ebb = te ? 1 : 0;
+      hex_in(hh, fr[K].tip.hash, 32);
+    }
+    N += count[K];
+    K++;
+  }
+  fclose(f);
+  /* the wire items: 82 00 82 82 0k <hint> d8 18 <byte string head> <header>, the hint the header's
+   * size (24..65535 bytes: heads 18 ll / 19 hh ll and 58 ll / 59 hh ll) */
+  uint8_t* arena = malloc(1);
+  size_t alen = 0, acap = 1, i = 0;
+  uint64_t* ioff = calloc(N + 1, 8);
+  uint32_t* ilen = calloc(N + 1, 4);
+  first[0] = 0;
+  for (size_t j = 0; j < K; j++) {
+    for (size_t h = from[j]; h < from[j] + count[j]; h++, i++) {
+      const uint32_t hl = hlen[h];
+      if (hl < 24 || hl > 65535) DIE("header %zu: %u bytes", h, hl);
+      if (alen + hl + 16 > acap) {
+        acap = 2 * (alen + hl + 16);
+        arena = realloc(arena, acap);
+      }
+      uint8_t pre[16] = {0x82, 0x00, 0x82, 0x82, kind[h]};
+      size_t pl = 5;
+      for (int part = 0; part < 2; part++) {           /* the hint (major type 0), then the byte string's head */
+        const uint8_t mt = part ? 0x40 : 0x00;
+        if (part) { pre[pl++] = 0xd8; pre[pl++] = 0x18; }
+        if (hl < 256) { pre[pl++] = mt | 24; pre[pl++] = (uint8_t)hl; }
+        else { pre[pl++] = mt | 25; pre[pl++] = (uint8_t)(hl >> 8); pre[pl++] = (uint8_t)hl; }
+      }
+      memcpy(arena + alen, pre, pl);
+      memcpy(arena + alen + pl, hdr[h], hl);
+      ioff[i] = alen;
+      ilen[i] = hl + (uint32_t)pl;
+      alen += hl + pl;
+    }
+    first[j + 1] = i;
+  }
+  praos_ctx* ctx = praos_open(0);
+  if (!ctx) DIE("praos_open(0)");
+  praos_pbft_candidates_in in;
+  memset(&in, 0, sizeof in);
+  in.items.n = N; in.items.bytes = arena; in.items.bytes_len = alen; in.items.off = ioff; in.items.len = ilen;
+  in.n_eras = 7;
+  in.n_delegs = nd;
+  in.view_end_slot = view_end;
+  in.params.window_size = window; in.params.threshold = threshold; in.params.epoch_slots = es;
+  in.params.protocol_magic = pm;
+  in.delegs = delegs;
+  praos_pbft_fragments fs = {K, first, fr};
+  praos_pbft_candidates_out out;
+  memset(&out, 0, sizeof out);
+  out.wire_status = calloc(N + 1, 1);
+  out.row = calloc(N + 1, 4);
+  out.verdict = calloc(N + 1, 1);
+  out.aux = calloc(N + 1, 8);
+  out.rows_cap = N;
+  CK(ctx, praos_validate_candidates_pbft(ctx, &in, &fs, &out));
+  printf("{\"phase\": \"candidates_pbft\", \"items\": %zu, \"n_rows\": %zu, \"stats\": [%llu, %llu, %llu, %llu], "
+         "\"fragments\": [", N, out.n_rows, (unsigned long long)out.stats[0], (unsigned long long)out.stats[1],
+         (unsigned long long)out.stats[2], (unsigned long long)out.stats[3]);
+  for (size_t j = 0; j < K; j++) {
+    size_t elen = 0;
+    (void)praos_pbft_state_encode(&fr[j].state, NULL, 0, &elen);
+    uint8_t* enc = malloc(elen + 1);
+    if (praos_pbft_state_encode(&fr[j].state, enc, elen, &elen) != PRAOS_OK) DIE("praos_pbft_state_encode");
+    printf("%s{\"chain_stop\": %zu, \"processed\": %zu, \"tip_origin\": %u, \"tip_is_ebb\": %u, \"tip_slot\": %llu, "
+           "\"tip_block_no\": %llu, \"tip_hash\": \"", j ? ", " : "", fr[j].chain_stop, fr[j].processed, fr[j].tip.origin,
+           fr[j].tip.is_ebb, (unsigned long long)fr[j].tip.slot, (unsigned long long)fr[j].tip.block_no);
+    hex_out(fr[j].tip.hash, 32);
+    printf("\", \"state\": \"");
+    hex_out(enc, elen);
+    free(enc);
+    printf("\", \"verdicts\": [");
+    for (size_t q = first[j]; q < first[j + 1]; q++) printf("%s%u", q > first[j] ? ", " : "", out.verdict[q]);
+    printf("], \"aux\": [");
+    for (size_t q = first[j]; q < first[j + 1]; q++)
+      printf("%s%llu", q > first[j] ? ", " : "", (unsigned long long)out.aux[q]);
     printf("], \"rows\": [");
     for (size_t q = first[j]; q < first[j + 1]; q++) printf("%s%u", q > first[j] ? ", " : "", out.row[q]);
     printf("]}");
@@ -1260,12 +1467,21 @@ int main(int argc, char** argv) {
     return pbft_headers_main(argv[2], strtoull(argv[3], NULL, 10), strtoull(argv[4], NULL, 10), es,
                              (uint32_t)strtoul(argv[6], NULL, 10), argv[7]);
   }
-  if (argc == 5 && strcmp(argv[1], "--candidates") == 0) return candidates_main(argv[2], argv[3], argv[4]);
+  if (argc == 5 && strcmp(argv[1], "--candidates") == 0) return candidates_main(argv[2], argv[3], argv[4], 0);
+  if (argc == 5 && strcmp(argv[1], "--candidates-tpraos") == 0) return candidates_main(argv[2], argv[3], argv[4], 1);
+  if (argc == 9 && strcmp(argv[1], "--candidates-pbft") == 0) {
+    const uint64_t es = strtoull(argv[5], NULL, 10);
+    if (es == 0) DIE("--candidates-pbft: epoch slots must be positive");
+    return candidates_pbft_main(argv[2], strtoull(argv[3], NULL, 10), strtoull(argv[4], NULL, 10), es,
+                                (uint32_t)strtoul(argv[6], NULL, 10), argv[7], argv[8]);
+  }
   if (argc != 4) DIE("usage: %s <immutable dir> <epoch file> <threads> | --chunk <dir> <chunk> <spkp> <members>"
                      " | --validate-chunk <dir> <chunk> <spkp>"
                      " | --validate-chunk-byron <dir> <chunk> <spkp> <byron epoch slots> <protocol magic>"
                      " | --pbft-headers <dir> <window> <threshold> <byron epoch slots> <protocol magic> <delegs file>"
-                     " | --candidates <dir> <epoch file> <fragments file>",
+                     " | --candidates[-tpraos] <dir> <epoch file> <fragments file>"
+                     " | --candidates-pbft <dir> <window> <threshold> <byron epoch slots> <protocol magic> <delegs file>"
+                     " <fragments file>",
                      argv[0]);
   read_epoch_file(argv[2]);
   chain_t ch;

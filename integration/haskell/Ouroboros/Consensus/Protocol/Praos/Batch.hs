@@ -74,6 +74,11 @@ module Ouroboros.Consensus.Protocol.Praos.Batch
   , CandidateLimits (..)
   , CandidatesResult (..)
   , validateCandidateFragments
+  , TPraosCandidatesResult (..)
+  , validateCandidateFragmentsTPraos
+  , PBftCandidateFragment (..)
+  , PBftCandidatesResult (..)
+  , validateCandidateFragmentsPBft
     -- * Error reconstruction (typed constructors: module Batch.Errors)
   , verdictToError
   ) where
@@ -231,6 +236,20 @@ foreign import ccall safe "praos_pbft_state_decode" c_pbft_state_decode
 foreign import ccall safe "praos_unwrap_wire_headers" c_unwrap_wire_headers
   :: Ptr PraosCtx -> Ptr () -> Word32 -> Ptr () -> IO CInt
 foreign import ccall safe "praos_validate_candidates" c_validate_candidates
+  :: Ptr PraosCtx -> Ptr () -> Ptr () -> Ptr () -> IO CInt
+-- additive again: the candidates calls for fragments of TPraos and of Byron headers.  The structs
+-- validateCandidateFragmentsTPraos and validateCandidateFragmentsPBft poke and peek (checked
+-- against the C compiler by tests/test_candidates_eras_abi.py; "layout-eras": the other layout
+-- lines belong to the tests named above):
+-- layout-eras praos_tpraos_candidates_in (128 bytes): items@0 n_eras@40 tpraos_eras@44 view_end_slot@48 ei@56 max_major_pv@88 lv_prot_major@96 max_header_size@104 max_body_size@112 extra_entropy@120
+-- layout-eras praos_tpraos_candidates_out (336 bytes): wire_status@0 row@8 verdict@16 failures@24 rows_cap@32 n_rows@40 rows@48 dec@88 leader_out@256 leader_proof@264 eta_idx@272 etas@280 n_etas@288 stats@296
+-- layout-eras praos_pbft_candidates_in (96 bytes): items@0 n_eras@40 n_delegs@44 view_end_slot@48 params@56 delegs@88
+-- layout-eras praos_pbft_fragment (104 bytes): tip@0 state@56 chain_stop@88 processed@96
+-- layout-eras praos_pbft_fragments (24 bytes): k@0 frag_first@8 frag@16
+-- layout-eras praos_pbft_candidates_out (152 bytes): wire_status@0 row@8 verdict@16 aux@24 rows_cap@32 n_rows@40 rows@48 row_is_ebb@112 stats@120
+foreign import ccall safe "praos_validate_candidates_tpraos" c_validate_candidates_tpraos
+  :: Ptr PraosCtx -> Ptr () -> Ptr () -> Ptr () -> IO CInt
+foreign import ccall safe "praos_validate_candidates_pbft" c_validate_candidates_pbft
   :: Ptr PraosCtx -> Ptr () -> Ptr () -> Ptr () -> IO CInt
 
 abiVersion :: CInt
@@ -1430,6 +1449,237 @@ validateCandidateFragments ctx@(PraosBatchCtx p) (baseSlot, baseNo, epochLen, wi
       , crTips = [t | (t, _, _) <- res]
       , crStates = [e | (_, e, _) <- res]
       , crStats = stats }
+
+-- | 'CandidatesResult' of a TPraos call (verdict 19 = the PRTCL failures) and, per fragment and
+-- item, the PRAOS_TPF_* set ("Batch.Errors" tpraosFailures rebuilds the typed failures from it).
+data TPraosCandidatesResult = TPraosCandidatesResult
+  { tcrResult   :: !CandidatesResult
+  , tcrFailures :: ![[Word16]]
+  }
+
+-- | 'validateCandidateFragments' for fragments of TPraos headers (Shelley .. Alonzo, wire indices 1
+-- to 4): the same pipeline in its TPraos modes.  @extra@: TICKN's extra entropy ('Nothing' =
+-- NeutralNonce), combined at every epoch tick of every fragment's nonce chain.  The states are
+-- PraosState CBOR as there (TPraos travels in the same praos_chain_state).  Replayed from C by
+-- ffi_harness --candidates-tpraos.
+validateCandidateFragmentsTPraos :: PraosBatchCtx -> (Word64, Word64, Word64, Word64) -> CandidateLimits
+                                 -> Maybe BS.ByteString -> BS.ByteString -> [CandidateFragment]
+                                 -> IO TPraosCandidatesResult
+validateCandidateFragmentsTPraos (PraosBatchGroup _ _ _) _ _ _ _ _ =
+  throwIO (PraosBatchError (-2) "validateCandidateFragmentsTPraos: one context, not a group")
+validateCandidateFragmentsTPraos ctx@(PraosBatchCtx p) (baseSlot, baseNo, epochLen, window) lim extra arena frs = do
+  let k = length frs
+      items = concatMap cfItems frs
+      n = length items
+      m = max 1 n
+      counts = map (length . cfItems) frs
+      firsts = VS.fromList (map fromIntegral (scanl (+) 0 counts) :: [CSize])
+      offs = VS.fromList (map fst items)
+      lens = VS.fromList (map snd items)
+      -- room in each fragment's counter map: the pools a state can name (65536, as withChainState
+      -- sizes it) plus one new issuer per item of that fragment; the fragments' arrays lie back to
+      -- back at the running offsets capOffs
+      caps = map (\c -> 65536 + c) counts :: [Int]
+      capOffs = scanl (+) 0 caps
+      capTotal = max 1 (sum caps)
+  wsv <- VSM.replicate m 0 :: IO (VSM.IOVector Word8)
+  rwv <- VSM.replicate m 0 :: IO (VSM.IOVector Word32)
+  vdv <- VSM.replicate m 0 :: IO (VSM.IOVector Word8)
+  flv <- VSM.replicate m 0 :: IO (VSM.IOVector Word16)
+  allocaBytes (304 * max 1 k) $ \fr -> allocaBytes (28 * capTotal) $ \hks ->
+    allocaBytes (8 * capTotal) $ \ctrs -> do
+    fillBytes fr 0 (304 * max 1 k)
+    forM_ (zip3 [0 ..] frs (zip caps capOffs)) $ \(j, f, (cap, capOff)) -> do
+      let fp = fr `plusPtr` (304 * j) :: Ptr ()
+          st = fp `plusPtr` 56 :: Ptr ()
+      case cfTip f of
+        Nothing -> pokeByteOff fp 0 (1 :: Int32)
+        Just (s, b, h) -> do
+          pokeByteOff fp 0 (0 :: Int32) >> pokeByteOff fp 8 s >> pokeByteOff fp 16 b
+          BSU.unsafeUseAsCStringLen (BS.take 32 (h <> BS.replicate 32 0)) $ \(hp, _) ->
+            copyBytes (castPtr fp `plusPtr` 24) hp 32
+      -- praos_chain_state: the counter arrays of fragment j, then the decoded state
+      pokeByteOff st 16 (hks `plusPtr` (28 * capOff) :: Ptr Word8)
+      pokeByteOff st 24 (ctrs `plusPtr` (8 * capOff) :: Ptr Word64)
+      pokeByteOff st 40 (fromIntegral cap :: CSize)
+      BSU.unsafeUseAsCStringLen (cfState f) $ \(src, sl) -> do
+        rc <- c_state_decode (castPtr src) (fromIntegral sl) st
+        when (rc /= 0) $ throwIO (PraosBatchError (fromIntegral rc) "praos_state_decode")
+    stats <- BSU.unsafeUseAsCStringLen arena $ \(ap, alen) ->
+      VS.unsafeWith firsts $ \ffp -> VS.unsafeWith offs $ \offp -> VS.unsafeWith lens $ \lenp ->
+      VSM.unsafeWith wsv $ \wsp -> VSM.unsafeWith rwv $ \rwp -> VSM.unsafeWith vdv $ \vdp ->
+      VSM.unsafeWith flv $ \flp ->
+      allocaBytes 128 $ \cin -> allocaBytes 24 $ \fs -> allocaBytes 336 $ \out -> allocaBytes 36 $ \xe -> do
+        fillBytes cin 0 128 >> fillBytes out 0 336 >> fillBytes xe 0 36
+        -- praos_tpraos_candidates_in: items (praos_header_bytes), n_eras, tpraos_eras (0: 1 to 4),
+        -- horizon, epoch info, limits, TICKN's extra entropy (a praos_nonce: hash, then neutral)
+        pokeByteOff cin 0 (fromIntegral n :: CSize) >> pokeByteOff cin 8 ap
+        pokeByteOff cin 16 (fromIntegral alen :: CSize) >> pokeByteOff cin 24 offp >> pokeByteOff cin 32 lenp
+        pokeByteOff cin 40 (7 :: Word32) >> pokeByteOff cin 44 (0 :: Word32)
+        pokeByteOff cin 48 (clViewEndSlot lim)
+        pokeByteOff cin 56 baseSlot >> pokeByteOff cin 64 baseNo >> pokeByteOff cin 72 epochLen
+        pokeByteOff cin 80 window
+        pokeByteOff cin 88 (clMaxMajorPV lim) >> pokeByteOff cin 96 (clProtMajor lim)
+        pokeByteOff cin 104 (clMaxHeaderSize lim) >> pokeByteOff cin 112 (clMaxBodySize lim)
+        case extra of
+          Nothing -> pokeByteOff xe 32 (1 :: Int32)
+          Just e -> BSU.unsafeUseAsCStringLen (BS.take 32 (e <> BS.replicate 32 0)) $ \(ep, _) ->
+            copyBytes (castPtr xe) ep 32
+        pokeByteOff cin 120 (xe :: Ptr ())
+        pokeByteOff fs 0 (fromIntegral k :: CSize) >> pokeByteOff fs 8 ffp >> pokeByteOff fs 16 fr
+        -- praos_tpraos_candidates_out: the per-item arrays; no per-row outputs are asked for
+        -- (rows_cap = n bounds the rows, every rows / dec / leader pointer stays NULL)
+        pokeByteOff out 0 wsp >> pokeByteOff out 8 rwp >> pokeByteOff out 16 vdp >> pokeByteOff out 24 flp
+        pokeByteOff out 32 (fromIntegral n :: CSize)
+        check ctx (c_validate_candidates_tpraos p (castPtr cin) (castPtr fs) (castPtr out))
+        s0 <- peekByteOff out 296
+        s1 <- peekByteOff out 304
+        s2 <- peekByteOff out 312
+        s3 <- peekByteOff out 320
+        s4 <- peekByteOff out 328
+        pure (s0, s1, s2, s3, s4)
+    vd <- VS.freeze vdv
+    fl <- VS.freeze flv
+    res <- mapM (\j -> do
+      let fp = fr `plusPtr` (304 * j) :: Ptr ()
+      origin <- peekByteOff fp 0 :: IO Int32
+      tip <- if origin /= 0 then pure Nothing else do
+        s <- peekByteOff fp 8
+        b <- peekByteOff fp 16
+        h <- BS.packCStringLen (castPtr fp `plusPtr` 24, 32)
+        pure (Just (s, b, h))
+      enc <- encodeChainState (fp `plusPtr` 56)
+      stop <- peekByteOff fp 288 :: IO CSize
+      done <- peekByteOff fp 296 :: IO CSize
+      pure (tip, enc, (fromIntegral stop, fromIntegral done))) [0 .. k - 1]
+    let starts = scanl (+) 0 counts
+    pure TPraosCandidatesResult
+      { tcrResult = CandidatesResult
+          { crVerdicts = [VS.toList (VS.slice a c vd) | (a, c) <- zip starts counts]
+          , crStops = [x | (_, _, x) <- res]
+          , crTips = [t | (t, _, _) <- res]
+          , crStates = [e | (_, e, _) <- res]
+          , crStats = stats }
+      , tcrFailures = [VS.toList (VS.slice a c fl) | (a, c) <- zip starts counts] }
+
+-- | One peer's candidate of Byron headers: its wire headers (spans in the call's arena), the head
+-- of the fragment and the encodePBftState bytes of the PBftState there.
+data PBftCandidateFragment = PBftCandidateFragment
+  { pcfItems :: ![(Word64, Word32)]
+  , pcfTip   :: !PBftTipC
+  , pcfState :: !BS.ByteString
+  }
+
+data PBftCandidatesResult = PBftCandidatesResult
+  { pcrVerdicts :: ![[Word8]]      -- ^ per fragment, per item: PRAOS_V_* (25 DoesntFit, 255 not reached)
+  , pcrAux      :: ![[Word64]]     -- ^ expected block number / minimum slot / the count n
+  , pcrStops    :: ![(Int, Int)]   -- ^ per fragment: (chain_stop, processed)
+  , pcrTips     :: ![PBftTipC]     -- ^ the head at each fragment's stop
+  , pcrStates   :: ![BS.ByteString] -- ^ encodePBftState of the state there
+  , pcrStats    :: !(Word64, Word64, Word64, Word64) -- ^ items, unwrapped Byron items, distinct headers, signature verifies
+  }
+
+-- | 'validateCandidateFragments' for fragments of Byron headers (wire index 0) under one delegation
+-- map: the items are unwrapped, hashed and deduplicated on the GPU, the PBFT signature is verified
+-- once per distinct header, and each fragment is folded from its own tip and PBftState with the
+-- client's DoesntFit check ahead of the envelope.  @viewEnd@: the first slot the ledger view does
+-- not cover ('maxBound': no horizon).  Replayed from C by ffi_harness --candidates-pbft.
+validateCandidateFragmentsPBft :: PraosBatchCtx -> PBftParamsC -> [(BS.ByteString, BS.ByteString)] -> Word64
+                               -> BS.ByteString -> [PBftCandidateFragment] -> IO PBftCandidatesResult
+validateCandidateFragmentsPBft (PraosBatchGroup _ _ _) _ _ _ _ _ =
+  throwIO (PraosBatchError (-2) "validateCandidateFragmentsPBft: one context, not a group")
+validateCandidateFragmentsPBft ctx@(PraosBatchCtx p) PBftParamsC{pbWindowSize, pbThreshold, pbEpochSlots, pbProtocolMagic}
+                               delegs viewEnd arena frs = do
+  let k = length frs
+      items = concatMap pcfItems frs
+      n = length items
+      m = max 1 n
+      nd = length delegs
+      counts = map (length . pcfItems) frs
+      firsts = VS.fromList (map fromIntegral (scanl (+) 0 counts) :: [CSize])
+      offs = VS.fromList (map fst items)
+      lens = VS.fromList (map snd items)
+      cap = fromIntegral (max 1 pbWindowSize) :: Int
+      dl = VS.fromList (concatMap (\(g, d) -> BS.unpack (pad28 g) ++ BS.unpack (pad28 d)) delegs)
+      pad28 b = BS.take 28 (b <> BS.replicate 28 0)
+  wsv <- VSM.replicate m 0 :: IO (VSM.IOVector Word8)
+  rwv <- VSM.replicate m 0 :: IO (VSM.IOVector Word32)
+  vdv <- VSM.replicate m 0 :: IO (VSM.IOVector Word8)
+  axv <- VSM.replicate m 0 :: IO (VSM.IOVector Word64)
+  -- the fragments' window arrays lie back to back: cap signers each
+  allocaBytes (104 * max 1 k) $ \fr -> allocaBytes (8 * cap * max 1 k) $ \sslots ->
+    allocaBytes (28 * cap * max 1 k) $ \shashes -> do
+    fillBytes fr 0 (104 * max 1 k)
+    forM_ (zip [0 ..] frs) $ \(j, f) -> do
+      let fp = fr `plusPtr` (104 * j) :: Ptr ()
+          stp = fp `plusPtr` 56 :: Ptr ()
+      case pcfTip f of
+        Nothing -> pokeByteOff fp 0 (1 :: Word8)
+        Just (s, b, h, e) -> do
+          pokeByteOff fp 1 (if e then 1 else 0 :: Word8)
+          pokeByteOff fp 8 s >> pokeByteOff fp 16 b
+          BSU.unsafeUseAsCStringLen (BS.take 32 (h <> BS.replicate 32 0)) $ \(hp, _) ->
+            copyBytes (castPtr fp `plusPtr` 24) hp 32
+      -- praos_pbft_state: the arrays of fragment j, then the decoded state
+      pokeByteOff stp 0 (fromIntegral cap :: Word64) >> pokeByteOff stp 8 (0 :: Word64)
+      pokeByteOff stp 16 (sslots `plusPtr` (8 * cap * j) :: Ptr Word64)
+      pokeByteOff stp 24 (shashes `plusPtr` (28 * cap * j) :: Ptr Word8)
+      BSU.unsafeUseAsCStringLen (pcfState f) $ \(sp, sl) ->
+        check ctx (c_pbft_state_decode (castPtr sp) (fromIntegral sl) (castPtr stp))
+    stats <- BSU.unsafeUseAsCStringLen arena $ \(ap, alen) ->
+      VS.unsafeWith firsts $ \ffp -> VS.unsafeWith offs $ \offp -> VS.unsafeWith lens $ \lenp ->
+      VS.unsafeWith dl $ \dlp ->
+      VSM.unsafeWith wsv $ \wsp -> VSM.unsafeWith rwv $ \rwp -> VSM.unsafeWith vdv $ \vdp ->
+      VSM.unsafeWith axv $ \axp ->
+      allocaBytes 96 $ \cin -> allocaBytes 24 $ \fs -> allocaBytes 152 $ \out -> do
+        fillBytes cin 0 96 >> fillBytes out 0 152
+        -- praos_pbft_candidates_in: items (praos_header_bytes), n_eras, n_delegs, horizon, params, delegs
+        pokeByteOff cin 0 (fromIntegral n :: CSize) >> pokeByteOff cin 8 ap
+        pokeByteOff cin 16 (fromIntegral alen :: CSize) >> pokeByteOff cin 24 offp >> pokeByteOff cin 32 lenp
+        pokeByteOff cin 40 (7 :: Word32) >> pokeByteOff cin 44 (fromIntegral nd :: Word32)
+        pokeByteOff cin 48 viewEnd
+        pokeByteOff cin 56 pbWindowSize >> pokeByteOff cin 64 pbThreshold >> pokeByteOff cin 72 pbEpochSlots
+        pokeByteOff cin 80 pbProtocolMagic >> pokeByteOff cin 84 (0 :: Word32)
+        pokeByteOff cin 88 (if nd == 0 then nullPtr else dlp)
+        pokeByteOff fs 0 (fromIntegral k :: CSize) >> pokeByteOff fs 8 ffp >> pokeByteOff fs 16 fr
+        -- praos_pbft_candidates_out: the per-item arrays; no per-row outputs are asked for (rows_cap
+        -- = n bounds the rows, every rows pointer stays NULL)
+        pokeByteOff out 0 wsp >> pokeByteOff out 8 rwp >> pokeByteOff out 16 vdp >> pokeByteOff out 24 axp
+        pokeByteOff out 32 (fromIntegral n :: CSize)
+        check ctx (c_validate_candidates_pbft p (castPtr cin) (castPtr fs) (castPtr out))
+        s0 <- peekByteOff out 120
+        s1 <- peekByteOff out 128
+        s2 <- peekByteOff out 136
+        s3 <- peekByteOff out 144
+        pure (s0, s1, s2, s3)
+    vd <- VS.freeze vdv
+    ax <- VS.freeze axv
+    res <- mapM (\j -> alloca $ \lenq -> do
+      let fp = fr `plusPtr` (104 * j) :: Ptr ()
+          stp = fp `plusPtr` 56 :: Ptr ()
+      origin <- peekByteOff fp 0 :: IO Word8
+      tip <- if origin /= 0 then pure Nothing else do
+        e <- peekByteOff fp 1 :: IO Word8
+        s <- peekByteOff fp 8
+        b <- peekByteOff fp 16
+        h <- BS.packCStringLen (castPtr fp `plusPtr` 24, 32)
+        pure (Just (s, b, h, e /= 0))
+      _ <- c_pbft_state_encode (castPtr stp) nullPtr 0 lenq
+      need <- fromIntegral <$> peek lenq :: IO Int
+      enc <- allocaBytes (max 1 need) $ \ep -> do
+        check ctx (c_pbft_state_encode (castPtr stp) ep (fromIntegral need) lenq)
+        BS.packCStringLen (castPtr ep, need)
+      stop <- peekByteOff fp 88 :: IO CSize
+      done <- peekByteOff fp 96 :: IO CSize
+      pure (tip, enc, (fromIntegral stop, fromIntegral done))) [0 .. k - 1]
+    let starts = scanl (+) 0 counts
+    pure PBftCandidatesResult
+      { pcrVerdicts = [VS.toList (VS.slice a c vd) | (a, c) <- zip starts counts]
+      , pcrAux = [VS.toList (VS.slice a c ax) | (a, c) <- zip starts counts]
+      , pcrStops = [x | (_, _, x) <- res]
+      , pcrTips = [t | (t, _, _) <- res]
+      , pcrStates = [e | (_, e, _) <- res]
+      , pcrStats = stats }
 
 -- ---------------------------------------------------------------- errors
 

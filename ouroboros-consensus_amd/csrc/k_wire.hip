@@ -11,6 +11,7 @@
 //                  flag the representatives, scan the flags (block counts, one block over the
 //                  counts, block-local offsets) so that rows are numbered in order of first
 //                  appearance, write the representatives' spans compacted and each item's row.
+//   k_hdr_row_kind gathers the Byron kind of each row's representative (the PBFT candidates call).
 // Items that failed to unwrap, or whose era is not in the caller's mask, stay out of the set.
 #include "byron_dev.hpp"
 #include "wire_scan.hpp"
@@ -161,6 +162,20 @@ __global__ void __launch_bounds__(NT) k_hdr_map(size_t n, const uint32_t* __rest
   item_row[i] = item_slot[i] == NONE ? NONE : rep_row[item_rep[i]];
 }
 
+// row_is_ebb[row] = 1 when the row's representative is a Byron item of kind 0 (an EBB): a Byron
+// row's kind travels with its span (k_pbft_decode reads a header by its kind).  After k_hdr_rows;
+// rows below rows_cap only, as there.
+__global__ void __launch_bounds__(NT) k_hdr_row_kind(size_t n, const uint32_t* __restrict__ item_slot,
+                                                     const uint32_t* __restrict__ item_rep,
+                                                     const uint32_t* __restrict__ rep_row,
+                                                     const uint8_t* __restrict__ kind, uint32_t rows_cap,
+                                                     uint8_t* __restrict__ row_is_ebb) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || item_slot[i] == NONE || item_rep[i] != (uint32_t)i) return;
+  const uint32_t row = rep_row[i];
+  if (row < rows_cap) row_is_ebb[row] = kind[i] == 0 ? 1 : 0;
+}
+
 }  // namespace
 
 // ---- host launchers
@@ -186,4 +201,12 @@ void launch_hdr_dedup(hipStream_t stream, size_t n, const uint8_t* status, const
   hipLaunchKernelGGL(k_hdr_rows, g, b, 0, stream, n, item_slot, item_rep, blk, ioff, ilen, rows_cap, row_off, row_len,
                      rep_row);
   hipLaunchKernelGGL(k_hdr_map, g, b, 0, stream, n, item_slot, item_rep, rep_row, item_row);
+}
+
+// after launch_hdr_dedup on the same stream: row_is_ebb (rows_cap bytes) of the Byron rows
+void launch_hdr_row_kind(hipStream_t stream, size_t n, const uint32_t* item_slot, const uint32_t* item_rep,
+                         const uint32_t* rep_row, const uint8_t* kind, uint32_t rows_cap, uint8_t* row_is_ebb) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_hdr_row_kind, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, stream, n, item_slot, item_rep,
+                     rep_row, kind, rows_cap, row_is_ebb);
 }

@@ -291,3 +291,5 @@ void launch_hdr_dedup(hipStream_t stream, size_t n, const uint8_t* status, const
                       uint32_t era_mask, uint32_t mask, uint32_t* slot_item, uint32_t* slot_min, uint32_t* item_slot,
                       uint32_t* item_rep, uint32_t* blk, uint32_t* total, const uint64_t* ioff, const uint32_t* ilen,
                       uint32_t rows_cap, uint64_t* row_off, uint32_t* row_len, uint32_t* rep_row, uint32_t* item_row);
+void launch_hdr_row_kind(hipStream_t stream, size_t n, const uint32_t* item_slot, const uint32_t* item_rep,
+                         const uint32_t* rep_row, const uint8_t* kind, uint32_t rows_cap, uint8_t* row_is_ebb);

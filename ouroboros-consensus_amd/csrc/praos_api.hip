@@ -2288,6 +2288,150 @@ int praos_byron_key_hash(praos_ctx* c, const uint8_t* keys64, size_t n, uint8_t*
   return r;
 }
 
+}  // extern "C"
+
+// the delegation table for the device: sorted by the delegate hash's 7 little-endian words
+// (word 0 first, k_pbft.hip hash_cmp), word 7 = the caller's index
+static std::vector<std::array<uint32_t, 8>> pbft_deleg_table(const uint8_t* delegs, uint32_t n_delegs) {
+  std::vector<std::array<uint32_t, 8>> tab(n_delegs);
+  for (uint32_t k = 0; k < n_delegs; k++) {
+    std::memcpy(tab[k].data(), delegs + 56 * (size_t)k + 28, 28);
+    tab[k][7] = k;
+  }
+  std::sort(tab.begin(), tab.end(), [](const std::array<uint32_t, 8>& x, const std::array<uint32_t, 8>& y) {
+    return std::lexicographical_compare(x.begin(), x.begin() + 7, y.begin(), y.begin() + 7);
+  });
+  return tab;
+}
+
+// The body of praos_verify_pbft_headers over device-resident inputs: n header spans (hoff, hlen)
+// into an arena of alen bytes (ld64u's pad behind it; the two bytes in front of every span inside
+// it) and their is_ebb flags, all final in the order of the context's stream.  The working buffers
+// go to b, which the caller frees.  The cached / uncached choice and praos_pbft_stats are over
+// these n headers.
+static int pbft_verify_dev(praos_ctx* c, praos_batch* b, size_t n, const uint8_t* arena, size_t alen,
+                           const uint64_t* hoff, const uint32_t* hlen, const uint8_t* d_ebb,
+                           const praos_pbft_params* p, const uint8_t* delegs, uint32_t n_delegs, praos_pbft_out* out) {
+  const std::vector<std::array<uint32_t, 8>> tab = pbft_deleg_table(delegs, n_delegs);
+  const bool cached = c->keycache > 0 && n >= c->pbft_ck_min;
+  uint8_t *d_bits = nullptr, *d_dhash = nullptr, *d_keys = nullptr, *d_sig = nullptr, *d_hram = nullptr;
+  uint32_t *d_tab = nullptr, *d_vlist = nullptr, *d_vcount = nullptr;
+  int32_t* d_gk = nullptr;
+  bool ok = dalloc(b, &d_tab, 32 * (size_t)n_delegs) == hipSuccess;
+  ok &= dalloc(b, &b->slot, 8 * n) == hipSuccess;
+  ok &= dalloc(b, &b->block_no, 8 * n) == hipSuccess;
+  ok &= dalloc(b, &b->prev_hash, 32 * n) == hipSuccess;
+  ok &= dalloc(b, &b->prev_genesis, n) == hipSuccess;
+  ok &= dalloc(b, &b->header_hash, 32 * n) == hipSuccess;
+  ok &= dalloc(b, &d_bits, n) == hipSuccess;
+  ok &= dalloc(b, &d_gk, 4 * n) == hipSuccess;
+  ok &= dalloc(b, &d_dhash, 28 * n) == hipSuccess;
+  ok &= dalloc(b, &d_keys, 32 * n) == hipSuccess;
+  ok &= dalloc(b, &d_sig, 64 * n) == hipSuccess;
+  ok &= dalloc(b, &d_hram, 64 * n) == hipSuccess;
+  ok &= dalloc(b, &d_vlist, 4 * n) == hipSuccess;
+  ok &= dalloc(b, &d_vcount, 16) == hipSuccess;
+  ok &= dalloc(b, (uint8_t**)&b->tab_ocert, LT_ED_B * n) == hipSuccess;
+  praos_batch::KeyCache& k = b->kc[0];
+  if (cached) {
+    // the delegate keys of a batch are few (7 on mainnet): a small entry space, the keys
+    // past it verify uncached
+    k.cap = 256;
+    while (k.cap < 2 * n) k.cap <<= 1;
+    k.max_entries = (uint32_t)std::min<size_t>(n / 2 + 1, 1024);
+    ok &= dalloc(b, &k.slot_rep, 4 * (size_t)k.cap) == hipSuccess;
+    ok &= dalloc(b, &k.slot_cnt, 4 * (size_t)k.cap) == hipSuccess;
+    ok &= dalloc(b, &k.slot_entry, 4 * (size_t)k.cap) == hipSuccess;
+    ok &= dalloc(b, &k.item_slot, 4 * n) == hipSuccess;
+    ok &= dalloc(b, &k.item_entry, 4 * n) == hipSuccess;
+    ok &= dalloc(b, &k.hit, 4 * n) == hipSuccess;
+    ok &= dalloc(b, &k.miss, 4 * n) == hipSuccess;
+    ok &= dalloc(b, &k.counters, 16) == hipSuccess;
+    ok &= dalloc(b, &k.entry_rep, 4 * (size_t)k.max_entries) == hipSuccess;
+    ok &= dalloc(b, &k.entry_pos, 4 * (size_t)k.max_entries) == hipSuccess;
+    ok &= dalloc(b, &k.kinfo, 36 * (size_t)k.max_entries) == hipSuccess;
+    ok &= dalloc(b, (uint8_t**)&k.ktab, KT_BYTES * k.max_entries) == hipSuccess;
+  }
+  if (!ok) { c->err = "device allocation failed"; return PRAOS_E_OOM; }
+  if (cached) {
+    const int r = ensure_bcomb16(c);
+    if (r != PRAOS_OK) return r;
+  }
+  hipStream_t st = c->stream;
+  if (n_delegs) HIPCHK(c, hipMemcpyAsync(d_tab, tab.data(), 32 * (size_t)n_delegs, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(d_vcount, 0, 16, st));
+  (void)hipGetLastError();
+  launch_pbft_decode(st, n, arena, alen, hoff, hlen, d_ebb, p->epoch_slots, p->protocol_magic, d_tab, n_delegs,
+                     b->slot, b->block_no, b->prev_hash, b->prev_genesis, b->header_hash, d_bits, d_gk, d_dhash, d_keys,
+                     d_sig, d_hram, d_vlist, d_vcount);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(c->ev[0], st));             // the decode's columns are final here
+  // (an ILP-4 build of this kernel, as the OCert misses have below ILP4_BATCH, measured level
+  // with it -- 21,600 headers 2.152 ms against the ILP-4 build's 2.175, 65,536 2.878 against
+  // 2.960 -- and was not kept)
+  auto sig_nc = [&](const uint32_t* list, const uint32_t* count) {   // uncached verifies over a list
+    launch_pbft_sig(st, n, list, count, c->btab, d_keys, d_sig, d_hram, d_bits, b->tab_ocert);
+  };
+  if (cached) {
+    const bool pk = c->pk_on;
+    c->pk_on = false;                                  // the batch's own entries, not the pool-key store
+    const int r = kc_lists(c, b, k, n, d_keys, st, d_vlist, d_vcount, 0);
+    if (r == PRAOS_OK) kc_precompute(c, k, d_keys, 0, st, n);
+    c->pk_on = pk;
+    if (r != PRAOS_OK) return r;
+    launch_pbft_sig_ck(st, n, k.hit, k.counters + 1, k.item_entry, k.kt, k.ki, c->bcomb16, d_keys, d_sig, d_hram,
+                       d_bits);
+    sig_nc(k.miss, k.counters + 2);
+  } else {
+    sig_nc(d_vlist, d_vcount);
+  }
+  HIPCHK(c, hipGetLastError());
+  // every column but the bits comes back on the download stream while the verifies run
+  hipStream_t ds = c->dstream;
+  HIPCHK(c, hipStreamWaitEvent(ds, c->ev[0], 0));
+  // (large columns through the pinned staging buffers; the small ones queued, one wait for all)
+  auto col = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+    if (bytes >= (4u << 20)) return d2h_on(c, dst, src, bytes, ds);
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ds);
+  };
+  HIPCHK(c, col(out->prev_hash, b->prev_hash, 32 * n));
+  HIPCHK(c, col(out->header_hash, b->header_hash, 32 * n));
+  if (out->delegate_hash) HIPCHK(c, col(out->delegate_hash, d_dhash, 28 * n));
+  HIPCHK(c, col(out->slot, b->slot, 8 * n));
+  HIPCHK(c, col(out->block_no, b->block_no, 8 * n));
+  HIPCHK(c, col(out->gk_idx, d_gk, 4 * n));
+  HIPCHK(c, col(out->prev_is_genesis, b->prev_genesis, n));
+  std::memset(c->pbft_raw, 0, sizeof c->pbft_raw);
+  if (cached) HIPCHK(c, hipMemcpyAsync(c->pbft_raw, k.counters, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(c->pbft_raw + 4, d_vcount, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(ds));
+  HIPCHK(c, hipStreamSynchronize(st));
+  c->pbft_stats[0] = cached ? 1 : 0;
+  c->pbft_stats[1] = cached ? std::min(c->pbft_raw[0], k.max_entries) : 0;
+  c->pbft_stats[2] = cached ? c->pbft_raw[1] : 0;
+  c->pbft_stats[3] = cached ? c->pbft_raw[2] : c->pbft_raw[4];
+  HIPCHK(c, hipMemcpy(out->bits, d_bits, n, hipMemcpyDeviceToHost));
+  return PRAOS_OK;
+}
+
+// The candidates call's way in (praos_candidates.hip): n > 0 rows whose spans, flags and arena
+// are already on the device and final (the caller has synchronised the stream that wrote them);
+// out has every column but delegate_hash.
+int rp_pbft_verify_rows(praos_ctx* c, size_t n, const uint8_t* arena, size_t arena_len, const uint64_t* hoff,
+                        const uint32_t* hlen, const uint8_t* d_is_ebb, const praos_pbft_params* p,
+                        const uint8_t* delegs, uint32_t n_delegs, praos_pbft_out* out) {
+  HIPCHK(c, hipSetDevice(c->device));
+  praos_batch* b = new praos_batch();
+  b->owner = c;
+  b->n = n;
+  const int r = pbft_verify_dev(c, b, n, arena, arena_len, hoff, hlen, d_is_ebb, p, delegs, n_delegs, out);
+  (void)hipStreamSynchronize(c->stream);
+  praos_batch_free(c, b);
+  return r;
+}
+
+extern "C" {
+
 int praos_verify_pbft_headers(praos_ctx* c, const praos_header_bytes* in, const uint8_t* is_ebb,
                               const praos_pbft_params* p, const uint8_t* delegs, uint32_t n_delegs,
                               praos_pbft_out* out) {
@@ -2310,16 +2454,6 @@ int praos_verify_pbft_headers(praos_ctx* c, const praos_header_bytes* in, const 
   if (c->device < 0) { c->err = "host-only context: no HIP device"; return PRAOS_E_STATE; }
   if (n == 0) return PRAOS_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  // the delegation table on the device: sorted by the delegate hash's 7 little-endian words
-  // (word 0 first, k_pbft.hip hash_cmp), word 7 = the caller's index
-  std::vector<std::array<uint32_t, 8>> tab(n_delegs);
-  for (uint32_t k = 0; k < n_delegs; k++) {
-    std::memcpy(tab[k].data(), delegs + 56 * (size_t)k + 28, 28);
-    tab[k][7] = k;
-  }
-  std::sort(tab.begin(), tab.end(), [](const std::array<uint32_t, 8>& x, const std::array<uint32_t, 8>& y) {
-    return std::lexicographical_compare(x.begin(), x.begin() + 7, y.begin(), y.begin() + 7);
-  });
   // the arena behind 8 zero bytes: the header hash reads the two bytes before a header (its
   // 82 0k prefix replaces them), and a header may start at offset 0 of the caller's arena
   constexpr size_t FRONT = 8;
@@ -2329,56 +2463,13 @@ int praos_verify_pbft_headers(praos_ctx* c, const praos_header_bytes* in, const 
   praos_batch* b = new praos_batch();
   b->owner = c;
   b->n = n;
-  const bool cached = c->keycache > 0 && n >= c->pbft_ck_min;
   auto run = [&]() -> int {
-    uint8_t *d_ebb = nullptr, *d_bits = nullptr, *d_dhash = nullptr, *d_keys = nullptr, *d_sig = nullptr,
-            *d_hram = nullptr;
-    uint32_t *d_tab = nullptr, *d_vlist = nullptr, *d_vcount = nullptr;
-    int32_t* d_gk = nullptr;
+    uint8_t* d_ebb = nullptr;
     bool ok = dalloc(b, &b->arena, ((alen + 7) & ~(size_t)7) + 16) == hipSuccess;
     ok &= dalloc(b, &b->hoff, 8 * n) == hipSuccess;
     ok &= dalloc(b, &b->hlen, 4 * n) == hipSuccess;
     ok &= dalloc(b, &d_ebb, n) == hipSuccess;
-    ok &= dalloc(b, &d_tab, 32 * (size_t)n_delegs) == hipSuccess;
-    ok &= dalloc(b, &b->slot, 8 * n) == hipSuccess;
-    ok &= dalloc(b, &b->block_no, 8 * n) == hipSuccess;
-    ok &= dalloc(b, &b->prev_hash, 32 * n) == hipSuccess;
-    ok &= dalloc(b, &b->prev_genesis, n) == hipSuccess;
-    ok &= dalloc(b, &b->header_hash, 32 * n) == hipSuccess;
-    ok &= dalloc(b, &d_bits, n) == hipSuccess;
-    ok &= dalloc(b, &d_gk, 4 * n) == hipSuccess;
-    ok &= dalloc(b, &d_dhash, 28 * n) == hipSuccess;
-    ok &= dalloc(b, &d_keys, 32 * n) == hipSuccess;
-    ok &= dalloc(b, &d_sig, 64 * n) == hipSuccess;
-    ok &= dalloc(b, &d_hram, 64 * n) == hipSuccess;
-    ok &= dalloc(b, &d_vlist, 4 * n) == hipSuccess;
-    ok &= dalloc(b, &d_vcount, 16) == hipSuccess;
-    ok &= dalloc(b, (uint8_t**)&b->tab_ocert, LT_ED_B * n) == hipSuccess;
-    praos_batch::KeyCache& k = b->kc[0];
-    if (cached) {
-      // the delegate keys of a batch are few (7 on mainnet): a small entry space, the keys
-      // past it verify uncached
-      k.cap = 256;
-      while (k.cap < 2 * n) k.cap <<= 1;
-      k.max_entries = (uint32_t)std::min<size_t>(n / 2 + 1, 1024);
-      ok &= dalloc(b, &k.slot_rep, 4 * (size_t)k.cap) == hipSuccess;
-      ok &= dalloc(b, &k.slot_cnt, 4 * (size_t)k.cap) == hipSuccess;
-      ok &= dalloc(b, &k.slot_entry, 4 * (size_t)k.cap) == hipSuccess;
-      ok &= dalloc(b, &k.item_slot, 4 * n) == hipSuccess;
-      ok &= dalloc(b, &k.item_entry, 4 * n) == hipSuccess;
-      ok &= dalloc(b, &k.hit, 4 * n) == hipSuccess;
-      ok &= dalloc(b, &k.miss, 4 * n) == hipSuccess;
-      ok &= dalloc(b, &k.counters, 16) == hipSuccess;
-      ok &= dalloc(b, &k.entry_rep, 4 * (size_t)k.max_entries) == hipSuccess;
-      ok &= dalloc(b, &k.entry_pos, 4 * (size_t)k.max_entries) == hipSuccess;
-      ok &= dalloc(b, &k.kinfo, 36 * (size_t)k.max_entries) == hipSuccess;
-      ok &= dalloc(b, (uint8_t**)&k.ktab, KT_BYTES * k.max_entries) == hipSuccess;
-    }
     if (!ok) { c->err = "device allocation failed"; return PRAOS_E_OOM; }
-    if (cached) {
-      const int r = ensure_bcomb16(c);
-      if (r != PRAOS_OK) return r;
-    }
     hipStream_t st = c->stream;
     HIPCHK(c, hipMemsetAsync(b->arena, 0, FRONT, st));
     HIPCHK(c, hipMemsetAsync(b->arena + alen, 0, ((alen + 7) & ~(size_t)7) + 16 - alen, st));
@@ -2386,60 +2477,7 @@ int praos_verify_pbft_headers(praos_ctx* c, const praos_header_bytes* in, const 
     HIPCHK(c, hipMemcpyAsync(b->hoff, off.data(), 8 * n, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(b->hlen, in->len, 4 * n, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_ebb, is_ebb, n, hipMemcpyHostToDevice, st));
-    if (n_delegs) HIPCHK(c, hipMemcpyAsync(d_tab, tab.data(), 32 * (size_t)n_delegs, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(d_vcount, 0, 16, st));
-    (void)hipGetLastError();
-    launch_pbft_decode(st, n, b->arena, alen, b->hoff, b->hlen, d_ebb, p->epoch_slots, p->protocol_magic, d_tab,
-                       n_delegs, b->slot, b->block_no, b->prev_hash, b->prev_genesis, b->header_hash, d_bits, d_gk,
-                       d_dhash, d_keys, d_sig, d_hram, d_vlist, d_vcount);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev[0], st));             // the decode's columns are final here
-    // (an ILP-4 build of this kernel, as the OCert misses have below ILP4_BATCH, measured level
-    // with it -- 21,600 headers 2.152 ms against the ILP-4 build's 2.175, 65,536 2.878 against
-    // 2.960 -- and was not kept)
-    auto sig_nc = [&](const uint32_t* list, const uint32_t* count) {   // uncached verifies over a list
-      launch_pbft_sig(st, n, list, count, c->btab, d_keys, d_sig, d_hram, d_bits, b->tab_ocert);
-    };
-    if (cached) {
-      const bool pk = c->pk_on;
-      c->pk_on = false;                                  // the batch's own entries, not the pool-key store
-      const int r = kc_lists(c, b, k, n, d_keys, st, d_vlist, d_vcount, 0);
-      if (r == PRAOS_OK) kc_precompute(c, k, d_keys, 0, st, n);
-      c->pk_on = pk;
-      if (r != PRAOS_OK) return r;
-      launch_pbft_sig_ck(st, n, k.hit, k.counters + 1, k.item_entry, k.kt, k.ki, c->bcomb16, d_keys, d_sig, d_hram,
-                         d_bits);
-      sig_nc(k.miss, k.counters + 2);
-    } else {
-      sig_nc(d_vlist, d_vcount);
-    }
-    HIPCHK(c, hipGetLastError());
-    // every column but the bits comes back on the download stream while the verifies run
-    hipStream_t ds = c->dstream;
-    HIPCHK(c, hipStreamWaitEvent(ds, c->ev[0], 0));
-    // (large columns through the pinned staging buffers; the small ones queued, one wait for all)
-    auto col = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-      if (bytes >= (4u << 20)) return d2h_on(c, dst, src, bytes, ds);
-      return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ds);
-    };
-    HIPCHK(c, col(out->prev_hash, b->prev_hash, 32 * n));
-    HIPCHK(c, col(out->header_hash, b->header_hash, 32 * n));
-    if (out->delegate_hash) HIPCHK(c, col(out->delegate_hash, d_dhash, 28 * n));
-    HIPCHK(c, col(out->slot, b->slot, 8 * n));
-    HIPCHK(c, col(out->block_no, b->block_no, 8 * n));
-    HIPCHK(c, col(out->gk_idx, d_gk, 4 * n));
-    HIPCHK(c, col(out->prev_is_genesis, b->prev_genesis, n));
-    std::memset(c->pbft_raw, 0, sizeof c->pbft_raw);
-    if (cached) HIPCHK(c, hipMemcpyAsync(c->pbft_raw, k.counters, 16, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(c->pbft_raw + 4, d_vcount, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(ds));
-    HIPCHK(c, hipStreamSynchronize(st));
-    c->pbft_stats[0] = cached ? 1 : 0;
-    c->pbft_stats[1] = cached ? std::min(c->pbft_raw[0], k.max_entries) : 0;
-    c->pbft_stats[2] = cached ? c->pbft_raw[1] : 0;
-    c->pbft_stats[3] = cached ? c->pbft_raw[2] : c->pbft_raw[4];
-    HIPCHK(c, hipMemcpy(out->bits, d_bits, n, hipMemcpyDeviceToHost));
-    return PRAOS_OK;
+    return pbft_verify_dev(c, b, n, b->arena, alen, b->hoff, b->hlen, d_ebb, p, delegs, n_delegs, out);
   };
   const int r = run();
   (void)hipStreamSynchronize(c->stream);
@@ -3174,6 +3212,16 @@ int rp_decode_rows(praos_ctx* c, praos_batch* b, const uint8_t* arena, size_t ar
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, hipEventRecord(b->dec_ev, c->cstream));
+  return PRAOS_OK;
+}
+
+int rp_download_leader(praos_ctx* c, praos_batch* b, uint8_t* leader_out, uint8_t* leader_proof) {
+  if (!c || !b || !b->tp_only) return PRAOS_E_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (b->n == 0 || (!leader_out && !leader_proof)) return PRAOS_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (leader_out) HIPCHK(c, d2h(c, leader_out, b->lead_out, 64 * b->n));
+  if (leader_proof) HIPCHK(c, d2h(c, leader_proof, b->lead_proof, 80 * b->n));
   return PRAOS_OK;
 }
 

@@ -17,6 +17,14 @@
 //     device   the crypto run (rp_run) under the per-row nonces;
 //     host     rp_fold per fragment in the client's mode, reading rows through the item-to-row
 //              map, on at most min(K, 16) threads.
+//   praos_validate_candidates_tpraos   the same pipeline for the TPraos eras (wire indices 1 to 4):
+//                               batch, decode, nonce chain (TICKN's extra entropy) and fold in
+//                               their TPraos modes; one implementation with the call above.
+//   praos_validate_candidates_pbft     K fragments of Byron wire headers (wire index 0), each from
+//                               its own tip and PBftState: the same front half, then
+//                               praos_verify_pbft_headers' kernels over the distinct headers read
+//                               from the wire arena, and the PBFT fold in the client's mode.
+// All three share the front half (front_begin / front_run): only the era mask differs.
 #include <hip/hip_runtime.h>
 
 #include "praos_hip.h"
@@ -104,6 +112,89 @@ void par_for(size_t k, const std::function<void(size_t)>& f) {
   for (auto& t : th) t.join();
 }
 
+// ---- the front half of every candidates call: the wire items go up once, are unwrapped and hashed
+// (k_wire_split), byte-identical headers of the eras in era_mask are found (k_hdr_dedup) and
+// numbered in order of first appearance (the scan kernels), and wire_status, the item-to-row map
+// and the row count come back.  The era mask is all that differs between the calls.
+bool frag_bounds_ok(const size_t* frag_first, size_t k, bool have_frags, size_t n) {
+  return frag_first && (k == 0 || have_frags) && frag_first[0] == 0 && frag_first[k] == n;
+}
+
+// a device, an epoch where the call needs one, and no stored-bytes call in flight on the
+// context's streams
+int front_begin(praos_ctx* c, bool need_epoch) {
+  if (rp_device(c) < 0) { praos_set_error_(c, "host-only context: no HIP device"); return PRAOS_E_STATE; }
+  if (need_epoch && !rp_have_epoch(c)) { praos_set_error_(c, "candidates: no epoch installed (praos_set_epoch)"); return PRAOS_E_STATE; }
+  return praos_verify_drain(c);
+}
+
+struct Front {
+  uint8_t* arena = nullptr;                      // the wire arena (ld64u's pad behind it)
+  ItemBufs d{};
+  uint64_t* d_row_off = nullptr;                 // the rows' spans (room for N)
+  uint32_t* d_row_len = nullptr;
+  uint8_t* d_row_ebb = nullptr;                  // with row_kind: the rows' Byron kind is 0 (room for N)
+  uint32_t R = 0;                                // distinct headers
+  std::vector<uint32_t> base_row;                // item -> row (NONE: outside the set)
+};
+
+// N > 0.  The buffers are carved from the context's scratch and stay valid until the next
+// candidates call; everything is final (the copy stream synchronised) on return.
+int front_run(praos_ctx* c, const praos_header_bytes& items, uint32_t n_eras, uint32_t era_mask, bool row_kind,
+              uint8_t* wire_status, Front& f) {
+  const size_t N = items.n, bytes = items.bytes_len;
+  CHIP(c, hipSetDevice(rp_device(c)));
+  hipStream_t st = rp_copy_stream(c);
+  // the hash set: a power of two, at least 2N slots
+  uint32_t tab = 2;
+  while (tab < 2 * N) tab <<= 1;
+  const size_t nb = (N + NT_ITEMS - 1) / NT_ITEMS;
+  // one device buffer, kept with the context between calls: the wire arena (with ld64u's pad), the
+  // item buffers, the dedup's arrays and the rows' spans and kinds (at most N rows)
+  const size_t arena_sz = ((bytes + 7) & ~(size_t)7) + 16;
+  Carve m;
+  m.size = Carve::up(arena_sz) + ItemBufs::bytes(N) + 4 * Carve::up(4 * N) + Carve::up(4 * nb) + Carve::up(4) +
+           2 * Carve::up(4 * (size_t)tab) + Carve::up(8 * N) + Carve::up(4 * N) + Carve::up(N);
+  m.base = rp_scratch(c, m.size);
+  if (!m.base) { praos_set_error_(c, "candidates: device allocation failed"); return PRAOS_E_OOM; }
+  f.arena = m.take<uint8_t>(arena_sz);
+  ItemBufs& d = f.d;
+  d.carve(m, N);
+  uint32_t* item_slot = m.take<uint32_t>(4 * N);
+  uint32_t* item_rep = m.take<uint32_t>(4 * N);
+  uint32_t* rep_row = m.take<uint32_t>(4 * N);
+  uint32_t* item_row = m.take<uint32_t>(4 * N);
+  uint32_t* blk = m.take<uint32_t>(4 * nb);
+  uint32_t* total = m.take<uint32_t>(4);
+  uint32_t* slot_item = m.take<uint32_t>(4 * (size_t)tab);
+  uint32_t* slot_min = m.take<uint32_t>(4 * (size_t)tab);
+  f.d_row_off = m.take<uint64_t>(8 * N);
+  f.d_row_len = m.take<uint32_t>(4 * N);
+  f.d_row_ebb = m.take<uint8_t>(N);
+
+  const praos_span whole{items.bytes, bytes};
+  f.R = 0;
+  f.base_row.assign(N, NONE);
+  {
+    const int rc = rp_upload_bytes(c, f.arena, &whole, bytes ? 1 : 0);
+    if (rc != PRAOS_OK) return rc;
+  }
+  CHIP(c, hipMemcpyAsync(d.off, items.off, 8 * N, hipMemcpyHostToDevice, st));
+  CHIP(c, hipMemcpyAsync(d.len, items.len, 4 * N, hipMemcpyHostToDevice, st));
+  CHIP(c, hipMemsetAsync(slot_item, 0, 4 * (size_t)tab, st));
+  CHIP(c, hipMemsetAsync(slot_min, 0xff, 4 * (size_t)tab, st));
+  launch_wire_split(st, N, f.arena, bytes, d.off, d.len, n_eras, d.status, d.era, d.kind, d.hint, d.ioff, d.ilen, d.hash);
+  launch_hdr_dedup(st, N, d.status, d.era, d.hash, era_mask, tab - 1, slot_item, slot_min, item_slot, item_rep, blk, total,
+                   d.ioff, d.ilen, (uint32_t)N, f.d_row_off, f.d_row_len, rep_row, item_row);
+  if (row_kind) launch_hdr_row_kind(st, N, item_slot, item_rep, rep_row, d.kind, (uint32_t)N, f.d_row_ebb);
+  CHIP(c, hipGetLastError());
+  CHIP(c, hipMemcpyAsync(&f.R, total, 4, hipMemcpyDeviceToHost, st));
+  CHIP(c, hipMemcpyAsync(wire_status, d.status, N, hipMemcpyDeviceToHost, st));
+  CHIP(c, hipMemcpyAsync(f.base_row.data(), item_row, 4 * N, hipMemcpyDeviceToHost, st));
+  CHIP(c, hipStreamSynchronize(st));
+  return PRAOS_OK;
+}
+
 }  // namespace
 
 extern "C" int praos_unwrap_wire_headers(praos_ctx* c, const praos_header_bytes* items, uint32_t n_eras,
@@ -146,16 +237,19 @@ extern "C" int praos_unwrap_wire_headers(praos_ctx* c, const praos_header_bytes*
 
 namespace {
 
-// the speculative nonce chain of one fragment (praos_replay.hip's chain thread, Praos rules): the
-// epoch nonce tickChainDepState reaches at each item as if every header before it were valid, as
-// runs (first item, nonce), and the evolving nonce after each item.  Dead after an item without
-// a decoded header: the fold stops there whatever comes after.
+// the speculative nonce chain of one fragment (praos_replay.hip's chain thread): the epoch nonce
+// tickChainDepState reaches at each item as if every header before it were valid, as runs (first
+// item, nonce), and the evolving nonce after each item.  extra_entropy NULL: the Praos tick;
+// non-NULL (TPraos calls only, which may also pass NULL): TICKN's tick, the extra entropy combined
+// into every new epoch nonce.  Dead after an item without a decoded header: the fold stops there
+// whatever comes after.
 struct Run {
   size_t first;
   praos_nonce eta;
 };
 void spec_chain(const praos_chain_state& st, const praos_epoch_info& ei, size_t n, const uint32_t* base_row,
-                const praos_decoded& d, const uint8_t* nonce, std::vector<Run>& runs, praos_nonce* evol) {
+                const praos_decoded& d, const uint8_t* nonce, const praos_nonce* extra_entropy, std::vector<Run>& runs,
+                praos_nonce* evol) {
   auto epoch_of = [&](uint64_t s) {
     return s < ei.epoch_base_slot ? ei.epoch_base_no : ei.epoch_base_no + (s - ei.epoch_base_slot) / ei.epoch_length;
   };
@@ -177,6 +271,7 @@ void spec_chain(const praos_chain_state& st, const praos_epoch_info& ei, size_t 
     const uint64_t e_new = epoch_of(slot);
     if (e_new > (origin ? 0 : sp_epoch)) {
       epoch_nonce = praos_host::nonce_combine(candidate, leb);
+      if (extra_entropy) epoch_nonce = praos_host::nonce_combine(epoch_nonce, *extra_entropy);   // TICKN (TPraos)
       leb = lab;
     }
     if (runs.empty() || !praos_host::nonce_eq(runs.back().eta, epoch_nonce)) runs.push_back({i, epoch_nonce});
@@ -199,12 +294,36 @@ void spec_chain(const praos_chain_state& st, const praos_epoch_info& ei, size_t 
 
 }  // namespace
 
-extern "C" int praos_validate_candidates(praos_ctx* c, const praos_candidates_in* in, praos_fragments* frags,
-                                         praos_candidates_out* out) {
-  if (!c || !in || !frags || !out || !items_ok(&in->items)) return PRAOS_E_ARG;
+namespace {
+
+// the outputs of praos_validate_candidates / praos_validate_candidates_tpraos, by pointer.  Exactly
+// one of rows / tp_rows is non-NULL: rows in the Praos call (tpraos false), tp_rows in the TPraos
+// call (tpraos true), where failures, leader_out and leader_proof belong too (NULL in the Praos call).
+struct CandOut {
+  uint8_t* wire_status;
+  uint32_t* row;
+  uint8_t* verdict;
+  uint16_t* failures;            // TPraos
+  size_t rows_cap;
+  size_t* n_rows;
+  uint8_t* eta_idx;
+  praos_nonce* etas;
+  uint32_t* n_etas;
+  uint64_t* stats;               // 5
+  const praos_out* rows;         // Praos
+  const praos_tpraos_out* tp_rows;   // TPraos
+  praos_decoded* dec;
+  uint8_t *leader_out, *leader_proof;   // TPraos, may be NULL
+};
+
+// Both protocols' candidates call.  in->praos_eras is the mask of the wire indices judged (never
+// 0 here); tpraos: the batch, the decode, the nonce chain's tick (extra_entropy, may be NULL) and
+// the fold run in their TPraos modes.
+int candidates_impl(praos_ctx* c, const praos_candidates_in* in, bool tpraos, const praos_nonce* extra_entropy,
+                    praos_fragments* frags, const CandOut* out) {
   const size_t N = in->items.n, K = frags->k, bytes = in->items.bytes_len;
-  if (!frags->frag_first || (K && !frags->frag) || frags->frag_first[0] != 0 || frags->frag_first[K] != N ||
-      in->ei.epoch_length == 0 || (N && (!out->wire_status || !out->row || !out->verdict))) {
+  if (!frag_bounds_ok(frags->frag_first, K, frags->frag != nullptr, N) || in->ei.epoch_length == 0 ||
+      (N && (!out->wire_status || !out->row || !out->verdict))) {
     praos_set_error_(c, "candidates: frag_first must run from 0 to the item count; epoch_length > 0; "
                         "wire_status, row and verdict are required");
     return PRAOS_E_ARG;
@@ -216,67 +335,29 @@ extern "C" int praos_validate_candidates(praos_ctx* c, const praos_candidates_in
       return PRAOS_E_ARG;
     }
   }
-  if (rp_device(c) < 0) { praos_set_error_(c, "host-only context: no HIP device"); return PRAOS_E_STATE; }
-  if (!rp_have_epoch(c)) { praos_set_error_(c, "candidates: no epoch installed (praos_set_epoch)"); return PRAOS_E_STATE; }
   {
-    const int rd = praos_verify_drain(c);      // submitted stored-bytes calls share the context's streams
+    const int rd = front_begin(c, true);
     if (rd != PRAOS_OK) return rd;
   }
-  out->n_rows = 0;
-  out->n_etas = 0;
-  std::memset(out->stats, 0, sizeof out->stats);
+  *out->n_rows = 0;
+  *out->n_etas = 0;
+  std::memset(out->stats, 0, 5 * sizeof(uint64_t));
   out->stats[0] = N;
   for (size_t j = 0; j < K; j++) frags->frag[j].chain_stop = frags->frag[j].processed = 0;
   if (N == 0) return PRAOS_OK;
-  const uint32_t era_mask = in->praos_eras ? in->praos_eras : ((1u << 5) | (1u << 6));
-  CHIP(c, hipSetDevice(rp_device(c)));
-  hipStream_t st = rp_copy_stream(c);
-  // the hash set: a power of two, at least 2N slots
-  uint32_t tab = 2;
-  while (tab < 2 * N) tab <<= 1;
-  const size_t nb = (N + NT_ITEMS - 1) / NT_ITEMS;
-  // one device buffer, kept with the context between calls: the wire arena (with ld64u's pad), the
-  // item buffers, the dedup's arrays and the rows' spans (at most N rows)
-  const size_t arena_sz = ((bytes + 7) & ~(size_t)7) + 16;
-  Carve m;
-  m.size = Carve::up(arena_sz) + ItemBufs::bytes(N) + 4 * Carve::up(4 * N) + Carve::up(4 * nb) + Carve::up(4) +
-           2 * Carve::up(4 * (size_t)tab) + Carve::up(8 * N) + Carve::up(4 * N);
-  m.base = rp_scratch(c, m.size);
-  if (!m.base) { praos_set_error_(c, "candidates: device allocation failed"); return PRAOS_E_OOM; }
-  uint8_t* arena = m.take<uint8_t>(arena_sz);
-  ItemBufs d;
-  d.carve(m, N);
-  uint32_t* item_slot = m.take<uint32_t>(4 * N);
-  uint32_t* item_rep = m.take<uint32_t>(4 * N);
-  uint32_t* rep_row = m.take<uint32_t>(4 * N);
-  uint32_t* item_row = m.take<uint32_t>(4 * N);
-  uint32_t* blk = m.take<uint32_t>(4 * nb);
-  uint32_t* total = m.take<uint32_t>(4);
-  uint32_t* slot_item = m.take<uint32_t>(4 * (size_t)tab);
-  uint32_t* slot_min = m.take<uint32_t>(4 * (size_t)tab);
-  uint64_t* d_row_off = m.take<uint64_t>(8 * N);
-  uint32_t* d_row_len = m.take<uint32_t>(4 * N);
-
-  // ---- device: unwrap + hash, dedup, decode of the distinct headers
-  const praos_span whole{in->items.bytes, bytes};
-  uint32_t R = 0;
-  std::vector<uint32_t> base_row(N);
+  const uint32_t era_mask = in->praos_eras;
+  // ---- device: unwrap + hash, dedup (the shared front half), then the decode of the distinct headers
+  Front f;
   {
-    const int rc = rp_upload_bytes(c, arena, &whole, bytes ? 1 : 0);
+    const int rc = front_run(c, in->items, in->n_eras, era_mask, false, out->wire_status, f);
     if (rc != PRAOS_OK) return rc;
   }
-  CHIP(c, hipMemcpyAsync(d.off, in->items.off, 8 * N, hipMemcpyHostToDevice, st));
-  CHIP(c, hipMemcpyAsync(d.len, in->items.len, 4 * N, hipMemcpyHostToDevice, st));
-  CHIP(c, hipMemsetAsync(slot_item, 0, 4 * (size_t)tab, st));
-  CHIP(c, hipMemsetAsync(slot_min, 0xff, 4 * (size_t)tab, st));
-  launch_wire_split(st, N, arena, bytes, d.off, d.len, in->n_eras, d.status, d.era, d.kind, d.hint, d.ioff, d.ilen, d.hash);
-  launch_hdr_dedup(st, N, d.status, d.era, d.hash, era_mask, tab - 1, slot_item, slot_min, item_slot, item_rep, blk, total,
-                   d.ioff, d.ilen, (uint32_t)N, d_row_off, d_row_len, rep_row, item_row);
-  CHIP(c, hipGetLastError());
-  CHIP(c, hipMemcpyAsync(&R, total, 4, hipMemcpyDeviceToHost, st));
-  CHIP(c, hipMemcpyAsync(out->wire_status, d.status, N, hipMemcpyDeviceToHost, st));
-  CHIP(c, hipMemcpyAsync(base_row.data(), item_row, 4 * N, hipMemcpyDeviceToHost, st));
-  CHIP(c, hipStreamSynchronize(st));
+  hipStream_t st = rp_copy_stream(c);
+  uint8_t* const arena = f.arena;
+  uint64_t* const d_row_off = f.d_row_off;
+  uint32_t* const d_row_len = f.d_row_len;
+  const uint32_t R = f.R;
+  const std::vector<uint32_t>& base_row = f.base_row;
   // a replay batch with room for the distinct headers, whatever rows_cap says: the count the
   // caller needs comes out of the nonce chains over their decoded columns
   praos_batch* b = nullptr;
@@ -287,7 +368,7 @@ extern "C" int praos_validate_candidates(praos_ctx* c, const praos_candidates_in
       if (b) { rp_batch_quiesce(b); rp_batch_keep(c, 0, b); }
     }
   } keep{c, b};
-  b = rp_batch_take(c, 0, std::max<size_t>(R, 1), 8, false);
+  b = rp_batch_take(c, 0, std::max<size_t>(R, 1), 8, tpraos);
   if (!b) { praos_set_error_(c, "candidates: device allocation failed"); return PRAOS_E_OOM; }
   std::vector<uint64_t> row_off(R);
   std::vector<uint32_t> row_len(R);
@@ -313,8 +394,8 @@ extern "C" int praos_validate_candidates(praos_ctx* c, const praos_candidates_in
   std::vector<std::vector<Run>> runs(K);
   std::vector<praos_nonce> evol(N);
   par_for(K, [&](size_t j) {
-    spec_chain(frags->frag[j].state, in->ei, F[j + 1] - F[j], base_row.data() + F[j], dec, nonce_h, runs[j],
-               evol.data() + F[j]);
+    spec_chain(frags->frag[j].state, in->ei, F[j + 1] - F[j], base_row.data() + F[j], dec, nonce_h,
+               tpraos ? extra_entropy : nullptr, runs[j], evol.data() + F[j]);
   });
   std::vector<praos_nonce> etas;
   std::vector<uint8_t> row_eta(R, 0);
@@ -351,13 +432,13 @@ extern "C" int praos_validate_candidates(praos_ctx* c, const praos_candidates_in
       }
     }
   }
-  out->n_etas = (uint32_t)etas.size();
+  *out->n_etas = (uint32_t)etas.size();
   if (too_many) {
     praos_set_error_(c, "candidates: " + std::to_string(etas.size()) + " distinct epoch nonces in one call (at most 256)");
     return PRAOS_E_ARG;
   }
   const size_t R2 = (size_t)R + extra_base.size();
-  out->n_rows = R2;
+  *out->n_rows = R2;
   out->stats[3] = R2;
   out->stats[4] = extra_base.size();
   if (R2 > out->rows_cap) {
@@ -391,7 +472,7 @@ extern "C" int praos_validate_candidates(praos_ctx* c, const praos_candidates_in
       // decoded again from the spans already on the device
       rp_batch_quiesce(b);
       rp_batch_destroy(c, b);
-      b = rp_batch_take(c, 0, R2, 8, false);
+      b = rp_batch_take(c, 0, R2, 8, tpraos);
       if (!b) { praos_set_error_(c, "candidates: device allocation failed"); return PRAOS_E_OOM; }
       rc = rp_decode_rows(c, b, arena, bytes, d_row_off, d_row_len, 0, R2);
       if (rc == PRAOS_OK) rc = rp_download_decoded(c, b, &dec, &nonce_h);
@@ -476,8 +557,9 @@ extern "C" int praos_validate_candidates(praos_ctx* c, const praos_candidates_in
     std::string err;
     uint8_t* v = out->verdict + F[j];
     const int rc = rp_fold(c, &h, f_prev, f_gen, &crypto, &env, &in->ei, &fr.state, etas.data(), (uint32_t)etas.size(),
-                           row_eta.data(), evol.data() + F[j], false, nullptr, v, nullptr, &stop, &done, nullptr, map,
-                           true, &err);
+                           row_eta.data(), evol.data() + F[j], tpraos, tpraos ? extra_entropy : nullptr, v,
+                           tpraos && out->failures ? out->failures + F[j] : nullptr, &stop, &done, nullptr, map, true,
+                           &err);
     if (rc != PRAOS_OK) {
       std::lock_guard<std::mutex> g(err_mu);
       if (first_rc == PRAOS_OK || j < first_j) { first_rc = rc; first_j = j; first_err = err; }
@@ -487,6 +569,9 @@ extern "C" int praos_validate_candidates(praos_ctx* c, const praos_candidates_in
     fr.chain_stop = stop;
     fr.processed = done;
     for (size_t i = done; i < n; i++) v[i] = PRAOS_V_NOT_REACHED;
+    if (tpraos && out->failures)                 // the failure set goes with PRAOS_V_TPRAOS alone
+      for (size_t i = 0; i < n; i++)
+        if (v[i] != PRAOS_V_TPRAOS) out->failures[F[j] + i] = 0;
     fr.tip_is_origin = env.tip_is_origin;
     fr.tip_slot = env.tip_slot;
     fr.tip_block_no = env.tip_block_no;
@@ -499,18 +584,204 @@ extern "C" int praos_validate_candidates(praos_ctx* c, const praos_candidates_in
 
   // ---- the rows' outputs
   if (R2) {
-    if (out->rows.bits) std::memcpy(out->rows.bits, bits_h, 2 * R2);
-    if (out->rows.pool_idx) std::memcpy(out->rows.pool_idx, pidx_h, 4 * R2);
-    if (out->rows.beta || out->rows.leader || out->rows.nonce) {
-      praos_out o = out->rows;
-      o.bits = bits_h;                                         // (required there; the same values again)
-      o.pool_idx = nullptr;
-      const int rc = praos_batch_download(c, b, &o);
+    if (tpraos) {
+      if (out->tp_rows->bits) std::memcpy(out->tp_rows->bits, bits_h, 2 * R2);
+      if (out->tp_rows->pool_idx) std::memcpy(out->tp_rows->pool_idx, pidx_h, 4 * R2);
+      if (out->tp_rows->beta_eta || out->tp_rows->beta_leader || out->tp_rows->nonce) {
+        praos_tpraos_out o = *out->tp_rows;
+        o.bits = bits_h;                                       // (required there; the same values again)
+        o.pool_idx = nullptr;
+        const int rc = praos_batch_download_tpraos(c, b, &o);
+        if (rc != PRAOS_OK) return rc;
+      }
+      const int rc = rp_download_leader(c, b, out->leader_out, out->leader_proof);
       if (rc != PRAOS_OK) return rc;
+    } else {
+      if (out->rows->bits) std::memcpy(out->rows->bits, bits_h, 2 * R2);
+      if (out->rows->pool_idx) std::memcpy(out->rows->pool_idx, pidx_h, 4 * R2);
+      if (out->rows->beta || out->rows->leader || out->rows->nonce) {
+        praos_out o = *out->rows;
+        o.bits = bits_h;                                       // (required there; the same values again)
+        o.pool_idx = nullptr;
+        const int rc = praos_batch_download(c, b, &o);
+        if (rc != PRAOS_OK) return rc;
+      }
     }
-    const int rc = praos_batch_download_decoded(c, b, &out->dec);
+    const int rc = praos_batch_download_decoded(c, b, out->dec);
     if (rc != PRAOS_OK) return rc;
     if (out->eta_idx) std::memcpy(out->eta_idx, row_eta.data(), R2);
+  }
+  return PRAOS_OK;
+}
+
+}  // namespace
+
+extern "C" int praos_validate_candidates(praos_ctx* c, const praos_candidates_in* in, praos_fragments* frags,
+                                         praos_candidates_out* out) {
+  if (!c || !in || !frags || !out || !items_ok(&in->items)) return PRAOS_E_ARG;
+  praos_candidates_in a = *in;
+  if (!a.praos_eras) a.praos_eras = (1u << 5) | (1u << 6);
+  const CandOut o{out->wire_status, out->row, out->verdict, nullptr, out->rows_cap, &out->n_rows, out->eta_idx, out->etas,
+                  &out->n_etas, out->stats, &out->rows, nullptr, &out->dec, nullptr, nullptr};
+  return candidates_impl(c, &a, false, nullptr, frags, &o);
+}
+
+// TPraos (Shelley .. Alonzo, wire indices 1 to 4): the same pipeline with the batch taken, the rows
+// decoded (the 15-field BHBody; k_vrf_nonce gives mkNonceFromOutputVRF of the eta certificate),
+// the nonce chain ticked (TICKN's extra entropy) and the fragments folded in their TPraos modes.
+// The overlay installed with praos_set_overlay applies as in every TPraos batch.
+extern "C" int praos_validate_candidates_tpraos(praos_ctx* c, const praos_tpraos_candidates_in* in,
+                                                praos_fragments* frags, praos_tpraos_candidates_out* out) {
+  if (!c || !in || !frags || !out || !items_ok(&in->items)) return PRAOS_E_ARG;
+  praos_candidates_in a{};
+  a.items = in->items;
+  a.n_eras = in->n_eras;
+  a.praos_eras = in->tpraos_eras ? in->tpraos_eras : ((1u << 1) | (1u << 2) | (1u << 3) | (1u << 4));
+  a.view_end_slot = in->view_end_slot;
+  a.ei = in->ei;
+  a.max_major_pv = in->max_major_pv;
+  a.lv_prot_major = in->lv_prot_major;
+  a.max_header_size = in->max_header_size;
+  a.max_body_size = in->max_body_size;
+  const CandOut o{out->wire_status, out->row, out->verdict, out->failures, out->rows_cap, &out->n_rows, out->eta_idx,
+                  out->etas, &out->n_etas, out->stats, nullptr, &out->rows, &out->dec, out->leader_out, out->leader_proof};
+  return candidates_impl(c, &a, true, in->extra_entropy, frags, &o);
+}
+
+// ---- Byron: K candidate fragments of era-0 wire headers, each from its own tip and PBftState.
+//     device   the front half with era mask 1 << 0 and the rows' kinds (k_hdr_row_kind), then
+//              praos_verify_pbft_headers' kernels over the rows, read from the wire arena;
+//     host     the PBFT fold per fragment in the client's mode, through the item-to-row map.
+bool praos_pbft_delegs_ok_(const uint8_t* delegs, uint32_t n);   // praos_pbft.hip
+
+extern "C" int praos_validate_candidates_pbft(praos_ctx* c, const praos_pbft_candidates_in* in,
+                                              praos_pbft_fragments* frags, praos_pbft_candidates_out* out) {
+  if (!c || !in || !frags || !out || !items_ok(&in->items)) return PRAOS_E_ARG;
+  const size_t N = in->items.n, K = frags->k, bytes = in->items.bytes_len;
+  const praos_pbft_params& p = in->params;
+  if (!frag_bounds_ok(frags->frag_first, K, frags->frag != nullptr, N) || p.epoch_slots == 0 || p.window_size == 0 ||
+      (in->n_delegs && !in->delegs) || (N && (!out->wire_status || !out->row || !out->verdict))) {
+    praos_set_error_(c, "candidates: frag_first must run from 0 to the item count; epoch_slots and window_size > 0; "
+                        "wire_status, row and verdict are required");
+    return PRAOS_E_ARG;
+  }
+  for (size_t j = 0; j < K; j++) {
+    const praos_pbft_state& s = frags->frag[j].state;
+    if (frags->frag_first[j] > frags->frag_first[j + 1] || s.n > s.cap || s.cap < p.window_size || s.n > p.window_size ||
+        !s.slot || !s.genesis_hash) {
+      praos_set_error_(c, "candidates: fragment " + std::to_string(j) +
+                              ": bounds out of order, or a state without n <= window_size <= cap");
+      return PRAOS_E_ARG;
+    }
+  }
+  if (!praos_pbft_delegs_ok_(in->delegs, in->n_delegs)) {
+    praos_set_error_(c, "pbft: duplicate hash in the delegation map");
+    return PRAOS_E_ARG;
+  }
+  {
+    const int rd = front_begin(c, false);
+    if (rd != PRAOS_OK) return rd;
+  }
+  out->n_rows = 0;
+  std::memset(out->stats, 0, sizeof out->stats);
+  out->stats[0] = N;
+  for (size_t j = 0; j < K; j++) frags->frag[j].chain_stop = frags->frag[j].processed = 0;
+  if (N == 0) return PRAOS_OK;
+
+  // ---- device: unwrap + hash, dedup, the rows' kinds
+  Front f;
+  {
+    const int rc = front_run(c, in->items, in->n_eras, 1u << 0, true, out->wire_status, f);
+    if (rc != PRAOS_OK) return rc;
+  }
+  const size_t R = f.R;
+  size_t unwrapped = 0;
+  for (size_t i = 0; i < N; i++) {
+    out->row[i] = f.base_row[i];
+    unwrapped += f.base_row[i] != NONE;
+  }
+  out->stats[1] = unwrapped;
+  out->stats[2] = R;
+  out->n_rows = R;
+  if (R > out->rows_cap) {
+    praos_set_error_(c, "candidates: rows_cap " + std::to_string(out->rows_cap) + " < " + std::to_string(R) + " rows");
+    return PRAOS_E_ARG;
+  }
+
+  // ---- device: decode, delegate look-up and signature of each row.  k_pbft_decode reads the two
+  // bytes in front of a header; a Byron inner span starts at least 8 bytes into its wire item
+  // (82 00 82 82 0k hint d8 18 + the byte string's head), so the wire arena needs no front pad.
+  const size_t Ra = std::max<size_t>(R, 1);
+  std::vector<uint8_t> r_bits(Ra), r_prev(32 * Ra), r_gen(Ra), r_hh(32 * Ra), r_dh, r_ebb(Ra);
+  std::vector<int32_t> r_gk(Ra);
+  std::vector<uint64_t> r_slot(Ra), r_bno(Ra);
+  if (out->rows.delegate_hash) r_dh.resize(28 * Ra);
+  praos_pbft_out rows{r_bits.data(), r_gk.data(), r_slot.data(), r_bno.data(), r_prev.data(), r_gen.data(), r_hh.data(),
+                      out->rows.delegate_hash ? r_dh.data() : nullptr};
+  if (R) {
+    CHIP(c, hipMemcpy(r_ebb.data(), f.d_row_ebb, R, hipMemcpyDeviceToHost));
+    const int rc = rp_pbft_verify_rows(c, R, f.arena, bytes, f.d_row_off, f.d_row_len, f.d_row_ebb, &p, in->delegs,
+                                       in->n_delegs, &rows);
+    if (rc != PRAOS_OK) return rc;
+    uint32_t ps[4] = {0, 0, 0, 0};
+    (void)praos_pbft_stats(c, ps);
+    out->stats[3] = (uint64_t)ps[2] + ps[3];
+  }
+
+  // ---- host: each fragment's fold
+  const size_t* F = frags->frag_first;
+  std::mutex err_mu;
+  int first_rc = PRAOS_OK;
+  size_t first_j = 0;
+  std::string first_err;
+  par_for(K, [&](size_t j) {
+    praos_pbft_fragment& fr = frags->frag[j];
+    const size_t n = F[j + 1] - F[j];
+    const uint32_t* map = out->row + F[j];
+    // the forecast horizon: the client waits at the first header the ledger view does not reach
+    size_t cut = n;
+    for (size_t i = 0; i < n; i++) {
+      const uint32_t r = map[i];
+      if (r == NONE || (r_bits[r] & PRAOS_PBFT_BIT_DECODE)) break;   // (the fold stops here at the latest)
+      if (r_slot[r] >= in->view_end_slot) { cut = i; break; }
+    }
+    size_t stop = 0, done = 0;
+    std::string err;
+    uint8_t* v = out->verdict + F[j];
+    uint64_t* a = out->aux ? out->aux + F[j] : nullptr;
+    const int rc = rp_pbft_fold_client(cut, map, R, &rows, r_ebb.data(), &p, in->delegs, in->n_delegs, &fr.tip, &fr.state,
+                                       v, a, &stop, &done, &err);
+    if (rc != PRAOS_OK) {
+      std::lock_guard<std::mutex> g(err_mu);
+      if (first_rc == PRAOS_OK || j < first_j) { first_rc = rc; first_j = j; first_err = err; }
+      return;
+    }
+    fr.chain_stop = stop;
+    fr.processed = done;
+    for (size_t i = done; i < n; i++) {
+      v[i] = PRAOS_V_NOT_REACHED;
+      if (a) a[i] = 0;
+    }
+  });
+  if (first_rc != PRAOS_OK) {
+    praos_set_error_(c, "candidates: fragment " + std::to_string(first_j) + ": " + first_err);
+    return first_rc;
+  }
+
+  // ---- the rows' outputs
+  if (R) {
+    auto give = [&](void* dst, const void* src, size_t b) {
+      if (dst) std::memcpy(dst, src, b);
+    };
+    give(out->rows.bits, r_bits.data(), R);
+    give(out->rows.gk_idx, r_gk.data(), 4 * R);
+    give(out->rows.slot, r_slot.data(), 8 * R);
+    give(out->rows.block_no, r_bno.data(), 8 * R);
+    give(out->rows.prev_hash, r_prev.data(), 32 * R);
+    give(out->rows.prev_is_genesis, r_gen.data(), R);
+    give(out->rows.header_hash, r_hh.data(), 32 * R);
+    give(out->rows.delegate_hash, r_dh.data(), 28 * R);
+    give(out->row_is_ebb, r_ebb.data(), R);
   }
   return PRAOS_OK;
 }

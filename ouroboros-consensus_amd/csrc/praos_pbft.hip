@@ -8,6 +8,7 @@
 // CPU restatement: tests/pbft_model.py.
 #include "praos_hip.h"
 #include "host_util.hpp"
+#include "replay_internal.hpp"
 #include "sha3.hpp"
 
 #include <algorithm>
@@ -67,6 +68,115 @@ struct Tip {
 
 }  // namespace
 
+// The fold of praos_pbft_update_chain_dep_state (map == nullptr, client == false: header i is row
+// i, would-be verdicts after the first failure) and the ChainSync client's (item i reads row
+// map[i] of h and is_ebb, PRAOS_V_DOESNT_FIT ahead of the envelope, the fold ends at the first
+// failure).  Arguments are checked by the callers.
+static int pbft_fold(size_t n, const uint32_t* map, size_t n_rows, const praos_pbft_out* h, const uint8_t* is_ebb,
+                     const praos_pbft_params* p, const uint8_t* delegs, uint32_t n_delegs, praos_pbft_tip* tip,
+                     praos_pbft_state* st, uint8_t* verdict, uint64_t* aux, size_t* chain_stop, size_t* processed,
+                     bool client, std::string* err) {
+  Window w;
+  for (uint64_t k = 0; k < st->n; k++) {
+    const uint32_t id = w.intern(st->genesis_hash + 28 * k);
+    w.sig.emplace_back(st->slot[k], id);
+    w.counts[id]++;
+  }
+  std::vector<uint32_t> deleg_id(n_delegs);
+  for (uint32_t k = 0; k < n_delegs; k++) deleg_id[k] = w.intern(delegs + 56 * (size_t)k);
+  Tip t{tip->origin != 0, tip->is_ebb != 0, tip->slot, tip->block_no, {0}};
+  std::memcpy(t.hash, tip->hash, 32);
+  // the state and tip at the first failing header
+  bool stopped = false;
+  Window w_stop;
+  Tip t_stop{};
+  *chain_stop = n;
+  size_t done = n;
+  for (size_t i = 0; i < n; i++) {
+    const size_t r = map ? map[i] : i;
+    uint8_t v = PRAOS_V_OK;
+    uint64_t a = 0;
+    bool ebb = false;
+    uint64_t slot = 0, bno = 0;
+    do {
+      if (map && (map[i] == PRAOS_NO_ROW || r >= n_rows)) { v = PRAOS_V_INPUT; break; }
+      ebb = is_ebb[r] != 0;
+      slot = h->slot[r];
+      bno = h->block_no[r];
+      if (h->bits[r] & PRAOS_PBFT_BIT_DECODE) { v = PRAOS_V_INPUT; break; }
+      const bool gen = h->prev_is_genesis[r] != 0;
+      const bool prev_ok = t.origin ? gen : (!gen && std::memcmp(t.hash, h->prev_hash + 32 * r, 32) == 0);
+      if (client && !prev_ok) { v = PRAOS_V_DOESNT_FIT; break; }
+      // ---- validateEnvelope
+      const uint64_t exp_bno = t.origin ? 0 : ((!t.is_ebb && ebb) ? t.block_no : t.block_no + 1);
+      if (bno != exp_bno) { v = PRAOS_V_ENV_BLOCK_NO; a = exp_bno; break; }
+      const uint64_t min_slot = t.origin ? 0 : ((t.is_ebb && !ebb) ? t.slot : t.slot + 1);
+      if (!(slot >= min_slot)) { v = PRAOS_V_ENV_SLOT_NO; a = min_slot; break; }
+      if (!prev_ok) { v = PRAOS_V_ENV_PREV_HASH; break; }
+      if (ebb && slot % p->epoch_slots != 0) { v = PRAOS_V_ENV_EBB_IN_SLOT; a = slot; break; }
+      if (ebb) break;                                    // PBftValidateBoundary: the state is left alone
+      // ---- PBFT updateChainDepState
+      if (h->bits[r] & PRAOS_PBFT_BIT_SIG) { v = PRAOS_V_PBFT_INVALID_SIG; break; }
+      if (!w.sig.empty() && slot < w.sig.back().first) { v = PRAOS_V_PBFT_INVALID_SLOT; break; }
+      if (h->gk_idx[r] < 0) { v = PRAOS_V_PBFT_NOT_DELEGATE; break; }
+      if (h->gk_idx[r] >= (int64_t)n_delegs) {
+        if (err) *err = "pbft: gk_idx of row " + std::to_string(r) + " outside the delegation map";
+        return PRAOS_E_ARG;
+      }
+      const uint32_t id = deleg_id[(size_t)h->gk_idx[r]];
+      const uint64_t after = w.counts[id] + 1 -
+                             ((w.sig.size() == p->window_size && w.sig.front().second == id) ? 1 : 0);
+      if (after > p->threshold) { v = PRAOS_V_PBFT_EXCEEDED; a = after; break; }
+      const bool trim = w.sig.size() == p->window_size;   // the size before the append
+      w.sig.emplace_back(slot, id);
+      w.counts[id]++;
+      if (trim) {
+        w.counts[w.sig.front().second]--;
+        w.sig.pop_front();
+      }
+    } while (false);
+    verdict[i] = v;
+    if (aux) aux[i] = a;
+    if (v != PRAOS_V_OK) {
+      if (!stopped) {
+        stopped = true;
+        *chain_stop = i;
+        w_stop = w;            // nothing of header i has been applied
+        t_stop = t;
+      }
+      if (client) { done = i + 1; break; }   // the client disconnects here
+      continue;                // the working copy skips the invalid header
+    }
+    t.origin = false;
+    t.is_ebb = ebb;
+    t.slot = slot;
+    t.block_no = bno;
+    std::memcpy(t.hash, h->header_hash + 32 * r, 32);
+  }
+  if (processed) *processed = done;
+  const Window& wr = stopped ? w_stop : w;
+  const Tip& tr = stopped ? t_stop : t;
+  st->n = wr.sig.size();
+  for (size_t k = 0; k < wr.sig.size(); k++) {
+    st->slot[k] = wr.sig[k].first;
+    std::memcpy(st->genesis_hash + 28 * k, wr.keys[wr.sig[k].second].data(), 28);
+  }
+  tip->origin = tr.origin ? 1 : 0;
+  tip->is_ebb = tr.is_ebb ? 1 : 0;
+  tip->slot = tr.slot;
+  tip->block_no = tr.block_no;
+  std::memcpy(tip->hash, tr.hash, 32);
+  return PRAOS_OK;
+}
+
+int rp_pbft_fold_client(size_t n, const uint32_t* map, size_t n_rows, const praos_pbft_out* h,
+                        const uint8_t* row_is_ebb, const praos_pbft_params* p, const uint8_t* delegs,
+                        uint32_t n_delegs, praos_pbft_tip* tip, praos_pbft_state* st, uint8_t* verdict, uint64_t* aux,
+                        size_t* chain_stop, size_t* processed, std::string* err_out) {
+  return pbft_fold(n, map, n_rows, h, row_is_ebb, p, delegs, n_delegs, tip, st, verdict, aux, chain_stop, processed,
+                   true, err_out);
+}
+
 extern "C" {
 
 int praos_pbft_update_chain_dep_state(praos_ctx* c, size_t n, const praos_pbft_out* h, const uint8_t* is_ebb,
@@ -91,84 +201,8 @@ int praos_pbft_update_chain_dep_state(praos_ctx* c, size_t n, const praos_pbft_o
       praos_set_error_(c, "pbft: gk_idx of header " + std::to_string(i) + " outside the delegation map");
       return PRAOS_E_ARG;
     }
-  Window w;
-  for (uint64_t k = 0; k < st->n; k++) {
-    const uint32_t id = w.intern(st->genesis_hash + 28 * k);
-    w.sig.emplace_back(st->slot[k], id);
-    w.counts[id]++;
-  }
-  std::vector<uint32_t> deleg_id(n_delegs);
-  for (uint32_t k = 0; k < n_delegs; k++) deleg_id[k] = w.intern(delegs + 56 * (size_t)k);
-  Tip t{tip->origin != 0, tip->is_ebb != 0, tip->slot, tip->block_no, {0}};
-  std::memcpy(t.hash, tip->hash, 32);
-  // the state and tip at the first failing header
-  bool stopped = false;
-  Window w_stop;
-  Tip t_stop{};
-  *chain_stop = n;
-  for (size_t i = 0; i < n; i++) {
-    const bool ebb = is_ebb[i] != 0;
-    const uint64_t slot = h->slot[i], bno = h->block_no[i];
-    uint8_t v = PRAOS_V_OK;
-    uint64_t a = 0;
-    do {
-      if (h->bits[i] & PRAOS_PBFT_BIT_DECODE) { v = PRAOS_V_INPUT; break; }
-      // ---- validateEnvelope
-      const uint64_t exp_bno = t.origin ? 0 : ((!t.is_ebb && ebb) ? t.block_no : t.block_no + 1);
-      if (bno != exp_bno) { v = PRAOS_V_ENV_BLOCK_NO; a = exp_bno; break; }
-      const uint64_t min_slot = t.origin ? 0 : ((t.is_ebb && !ebb) ? t.slot : t.slot + 1);
-      if (!(slot >= min_slot)) { v = PRAOS_V_ENV_SLOT_NO; a = min_slot; break; }
-      const bool gen = h->prev_is_genesis[i] != 0;
-      const bool prev_ok = t.origin ? gen : (!gen && std::memcmp(t.hash, h->prev_hash + 32 * i, 32) == 0);
-      if (!prev_ok) { v = PRAOS_V_ENV_PREV_HASH; break; }
-      if (ebb && slot % p->epoch_slots != 0) { v = PRAOS_V_ENV_EBB_IN_SLOT; a = slot; break; }
-      if (ebb) break;                                    // PBftValidateBoundary: the state is left alone
-      // ---- PBFT updateChainDepState
-      if (h->bits[i] & PRAOS_PBFT_BIT_SIG) { v = PRAOS_V_PBFT_INVALID_SIG; break; }
-      if (!w.sig.empty() && slot < w.sig.back().first) { v = PRAOS_V_PBFT_INVALID_SLOT; break; }
-      if (h->gk_idx[i] < 0) { v = PRAOS_V_PBFT_NOT_DELEGATE; break; }
-      const uint32_t id = deleg_id[(size_t)h->gk_idx[i]];
-      const uint64_t after = w.counts[id] + 1 -
-                             ((w.sig.size() == p->window_size && w.sig.front().second == id) ? 1 : 0);
-      if (after > p->threshold) { v = PRAOS_V_PBFT_EXCEEDED; a = after; break; }
-      const bool trim = w.sig.size() == p->window_size;   // the size before the append
-      w.sig.emplace_back(slot, id);
-      w.counts[id]++;
-      if (trim) {
-        w.counts[w.sig.front().second]--;
-        w.sig.pop_front();
-      }
-    } while (false);
-    verdict[i] = v;
-    if (aux) aux[i] = a;
-    if (v != PRAOS_V_OK) {
-      if (!stopped) {
-        stopped = true;
-        *chain_stop = i;
-        w_stop = w;            // nothing of header i has been applied
-        t_stop = t;
-      }
-      continue;                // the working copy skips the invalid header
-    }
-    t.origin = false;
-    t.is_ebb = ebb;
-    t.slot = slot;
-    t.block_no = bno;
-    std::memcpy(t.hash, h->header_hash + 32 * i, 32);
-  }
-  const Window& wr = stopped ? w_stop : w;
-  const Tip& tr = stopped ? t_stop : t;
-  st->n = wr.sig.size();
-  for (size_t k = 0; k < wr.sig.size(); k++) {
-    st->slot[k] = wr.sig[k].first;
-    std::memcpy(st->genesis_hash + 28 * k, wr.keys[wr.sig[k].second].data(), 28);
-  }
-  tip->origin = tr.origin ? 1 : 0;
-  tip->is_ebb = tr.is_ebb ? 1 : 0;
-  tip->slot = tr.slot;
-  tip->block_no = tr.block_no;
-  std::memcpy(tip->hash, tr.hash, 32);
-  return PRAOS_OK;
+  return pbft_fold(n, nullptr, n, h, is_ebb, p, delegs, n_delegs, tip, st, verdict, aux, chain_stop, nullptr, false,
+                   nullptr);
 }
 
 static size_t put_head(std::vector<uint8_t>& o, uint8_t mt, uint64_t v) {

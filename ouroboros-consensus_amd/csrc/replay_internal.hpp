@@ -85,6 +85,22 @@ uint8_t* rp_scratch(praos_ctx* c, size_t bytes);
 int rp_upload_bytes(praos_ctx* c, uint8_t* dst, const praos_span* spans, size_t nspans);
 int rp_decode_rows(praos_ctx* c, praos_batch* b, const uint8_t* arena, size_t arena_len, const uint64_t* hoff,
                    const uint32_t* hlen, size_t first, size_t n);
+// the leader certificates (output n*64, proof n*80; either may be NULL) of a TPraos batch's rows,
+// after its run
+int rp_download_leader(praos_ctx* c, praos_batch* b, uint8_t* leader_out, uint8_t* leader_proof);
+// The Byron candidates call: praos_verify_pbft_headers' body over n > 0 rows already on the device
+// (praos_api.hip: spans into an arena with ld64u's pad behind it and two bytes in front of every
+// span, is_ebb flags; all final before the call), and the ChainSync client's mode of the PBFT fold
+// (praos_pbft.hip): item i reads row map[i] (PRAOS_NO_ROW: PRAOS_V_INPUT) of h and row_is_ebb,
+// PRAOS_V_DOESNT_FIT before the envelope, the fold ends at the first failure (*processed = items
+// judged).  The caller has checked params, delegs and the state's room; err_out gets the text.
+int rp_pbft_verify_rows(praos_ctx* c, size_t n, const uint8_t* arena, size_t arena_len, const uint64_t* hoff,
+                        const uint32_t* hlen, const uint8_t* d_is_ebb, const praos_pbft_params* p,
+                        const uint8_t* delegs, uint32_t n_delegs, praos_pbft_out* out);
+int rp_pbft_fold_client(size_t n, const uint32_t* map, size_t n_rows, const praos_pbft_out* h,
+                        const uint8_t* row_is_ebb, const praos_pbft_params* p, const uint8_t* delegs,
+                        uint32_t n_delegs, praos_pbft_tip* tip, praos_pbft_state* st, uint8_t* verdict, uint64_t* aux,
+                        size_t* chain_stop, size_t* processed, std::string* err_out);
 // The replay of praos_replay_immutable[_tpraos|_views] over m contexts (praos_replay.hip): batch k
 // is uploaded, decoded and verified on mem[k % m]; the nonce chain and the fold run once, in chain
 // order, the fold and the error text on mem[0].  m = 1 is the single-context replay.  views

@@ -430,6 +430,10 @@ SIGNATURES = {
     # wire headers (the structs are praos_hip.wire's)
     "praos_unwrap_wire_headers": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "praos_validate_candidates": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "praos_validate_candidates_tpraos": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p]),
+    "praos_validate_candidates_pbft": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_void_p]),
 }
 
 _lib = None
