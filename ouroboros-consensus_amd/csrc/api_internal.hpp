@@ -1,0 +1,604 @@
+#pragma once
+// api_internal.hpp -- what the units of the host API share: the context and batch structs, the
+// tuning constants, the staging pool, the allocation / error helpers and the functions that cross
+// unit boundaries (praos_impl).  Included by praos_api / praos_run / praos_fold / praos_debug
+// only; the other host modules (replay, group, candidates, pbft) go through replay_internal.hpp.
+#include "praos_hip.h"
+#include "launch.hpp"
+#include "host_util.hpp"
+#include "replay_internal.hpp"
+#include "chunk_scan.hpp"
+
+static constexpr size_t NT = 256;                  // threads per block of the crypto kernels
+static constexpr size_t NIELS_BYTES = 3 * 32;      // sizeof(ge_niels)
+static constexpr size_t BTAB_N = 128;              // entries per fixed-base table (scalarmult.hpp)
+static constexpr size_t BCOMB_TABLES = 32;         // fixed-base comb: 256^j B, j < 32 (scalarmult.hpp BCOMB_T)
+static constexpr size_t C16_TABLES = 16, C16_ENTRIES = 32768;   // radix-2^16 comb (scalarmult.hpp C16_T, C16_N)
+static constexpr size_t CACHED_BYTES = 4 * 32;     // sizeof(ge_cached)
+static constexpr size_t LT_ED_B = 8 * CACHED_BYTES, LT_VRF_B = 16 * CACHED_BYTES;   // per-lane tables (kcommon.hpp)
+static constexpr size_t VRF_MID_BYTES = 28 * 16;    // per-header records of the staged VRF (praos_core.hpp)
+static constexpr uint32_t TP_SIGNED_STRIDE = 640;   // max canonical TPraos BHBody: 586 bytes (k_decode.hip)
+
+#include <pthread.h>
+#include <sched.h>
+
+#include <algorithm>
+#include <array>
+#include <chrono>
+#include <condition_variable>
+#include <cstdlib>
+#include <cstdio>
+#include <cstring>
+#include <functional>
+#include <map>
+#include <set>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+// A small persistent pool of host threads for the staging copies (pageable caller
+// memory <-> pinned buffers): one job at a time, each worker takes its share.
+class CopyPool {
+ public:
+  explicit CopyPool(unsigned n) : nt_(n) {
+    for (unsigned t = 0; t < nt_; t++) th_.emplace_back([this, t] { loop(t); });
+  }
+  ~CopyPool() {
+    { std::lock_guard<std::mutex> g(m_); stop_ = true; }
+    cv_.notify_all();
+    for (auto& t : th_) t.join();
+  }
+  unsigned size() const { return nt_; }
+  void run(const std::function<void(unsigned)>& f) {
+    std::unique_lock<std::mutex> g(m_);
+    job_ = &f;
+    pending_ = nt_;
+    gen_++;
+    cv_.notify_all();
+    done_.wait(g, [this] { return pending_ == 0; });
+    job_ = nullptr;
+  }
+  // every worker onto the given CPUs (empty: back to the process's own mask)
+  void pin(const std::vector<int>& cpus) {
+    cpu_set_t set;
+    CPU_ZERO(&set);
+    if (cpus.empty()) {
+      if (sched_getaffinity(0, sizeof set, &set) != 0) return;
+    } else {
+      for (int c : cpus) CPU_SET(c, &set);
+    }
+    run([&](unsigned) { (void)pthread_setaffinity_np(pthread_self(), sizeof set, &set); });
+  }
+  // dst[0, n) = src[0, n), split over the workers
+  void copy(void* dst, const void* src, size_t n) {
+    if (n < (1u << 20)) { std::memcpy(dst, src, n); return; }
+    run([&](unsigned t) {
+      const size_t a = n * t / nt_, b = n * (t + 1) / nt_;
+      std::memcpy((uint8_t*)dst + a, (const uint8_t*)src + a, b - a);
+    });
+  }
+
+ private:
+  void loop(unsigned t) {
+    uint64_t seen = 0;
+    for (;;) {
+      const std::function<void(unsigned)>* f;
+      {
+        std::unique_lock<std::mutex> g(m_);
+        cv_.wait(g, [&] { return stop_ || gen_ != seen; });
+        if (stop_) return;
+        seen = gen_;
+        f = job_;
+      }
+      (*f)(t);
+      std::lock_guard<std::mutex> g(m_);
+      if (--pending_ == 0) done_.notify_all();
+    }
+  }
+  unsigned nt_;
+  std::vector<std::thread> th_;
+  std::mutex m_;
+  std::condition_variable cv_, done_;
+  const std::function<void(unsigned)>* job_ = nullptr;
+  unsigned pending_ = 0;
+  uint64_t gen_ = 0;
+  bool stop_ = false;
+};
+
+static constexpr size_t STAGE_PIECE = 16u << 20;    // pinned staging buffers: 2 x 16 MB per context
+static constexpr int PIPE_MAX = 8;                  // chunks of the stored-bytes pipeline
+static constexpr int PIPE_CALLS = 3;                // submitted stored-bytes calls in flight (pipe[0 .. 3))
+static constexpr size_t PIPE_MIN_CHUNK = 49152;     // headers per chunk at least (auto mode)
+// Batches below this many headers (a strong-scaling shard of an epoch over 8 GPUs is 54k) leave
+// most wave slots empty and run latency-bound (PRAOS_VRF_PRIO = -1 raises stage V there)
+static constexpr size_t SMALL_BATCH = 80000;
+static constexpr size_t WIDE_BATCH = 300000;           // the VRF key cache's wide tier: batches from this size on
+static constexpr uint32_t WIDE_MIN_USES = 43;          // ... and keys with this many uses: the break-even of
+                                                       // W_KEY_VRF_WIDE against W_VRF_F_CK_WIDE (tools/workmodel.py)
+// below this many headers the key precomputes run at raised wave priority (PRAOS_KEY_PRIO -1):
+// they head the cached chains (profiles/r04/bb: 96k 3.66 -> 3.57 ms, 108k 4.14 -> 3.83, 160k
+// 5.19 -> 4.88, 300k 8.83 -> 8.67; 432k within noise)
+static constexpr size_t KEY_PRIO_BATCH = 400000;
+// below this many headers stage V, the uncached verifies and the key precompute come from their
+// ILP-4 builds (k_vrf_v4 / k_miss4 / k_keys4): a step's chains are latency-bound there
+// (profiles/r04/y: 96k 4.06 -> 3.64 ms, 108k 4.25 -> 4.10, 112k 4.39 -> 4.15; equal at 120k,
+// slower at 128k)
+static constexpr size_t ILP4_BATCH = 120000;
+// from this many headers on the KES Merkle walk runs once per leaf-key entry (PRAOS_KES_DEDUP -1).
+// Medians of alternating runs, ms per step without / with it, beside the other cuts of DESIGN
+// section 24: 432k 9.907 -> 9.847 (eight runs each, every run with it below every run without);
+// 300k 7.170 -> 7.231 and 160k 4.058 -> 4.117 (four each): slower, the step there is not bound
+// by the instruction count; the KES-only configs[3] 9.355 -> 9.413, inside its spread
+// (profiles/r08_perkey_ab.json)
+static constexpr size_t KES_DEDUP_BATCH = 400000;
+// Byron header batches (praos_verify_pbft_headers) below this many headers verify uncached: the
+// delegate keys' precompute chain (250 doublings, then the table pass) is pure latency there.
+// Measured on an MI355X (tools/pbft_bench.py: 7 delegates in turn, a freshly opened context per
+// variant and pass, medians of 9 runs, cached / uncached ms end to end): 16,384 2.07 / 1.83,
+// 32,768 2.38 / 2.16, 65,536 3.16 / 2.73, 98,304 4.17 / 3.95, 131,072 4.98 / 4.67, 163,840 6.03 /
+// 6.04, 216,000 7.51 / 7.94: the medians cross at about 163,840.  With 7 keys the cache's insert
+// and partition passes serialise on 7 hash slots (0.66 + 0.62 ms at 216,000, kernel trace), which
+// is what moves the crossing this far out.
+static constexpr size_t PBFT_CK_MIN = 163840;
+// below this many headers the KES leaf keys are not cached (every KES check uncached, from the
+// ILP-4 build, beside stage V): a 54k-header shard's stage V and uncached KES waves fit in one
+// round of wave slots (2 per SIMD), and the leaf-key chain -- lists, precompute, tables, k_kes_ck,
+// the step's longest after stage V + join -- is gone (54k 2.44-2.49 -> 2.29-2.37 ms; at 64k the
+// waves no longer fit and it is slower, 2.53 -> 3.05; 80k 2.97 -> 3.47; 108k 3.41 -> 4.59;
+// profiles/r06/i_kes_nocache).  PRAOS_OPT_KES_NOCACHE / PRAOS_KES_NOCACHE=<headers> override it
+// (0: always cached).
+static constexpr size_t KES_NOCACHE_BATCH = 58000;
+// below this many headers (the 1/8-epoch shard of a 432k epoch is 54k) stage V's join runs on the
+// main stream after it waits for U itself (PRAOS_V_MAIN 2) and the uncached verifies keep normal
+// wave priority
+static constexpr size_t SHARD_SMALL = 60000;
+static constexpr int PIPE_AUTO = 8;                 // chunks in auto mode (round 3, equal chunks: 4 -> 21.9M,
+                                                    // 6 -> 23.0M, 8 -> 22.1M headers/s, profiles/r03/e2e_chunks.txt;
+                                                    // round 5 with the first chunk at 1/4 of the others: 6 ->
+                                                    // 25.3-25.6M, 8 -> 26.4-26.6M, profiles/r05/c8_pipe_head)
+struct praos_batch;
+
+// The context's last error.  The replay's worker threads (reader, nonce chain, launcher,
+// fold) can fail at the same time, so every assignment takes a lock; while a replay runs
+// (first_only) only the first message of the call is kept -- the one that stopped it.
+class ErrMsg {
+ public:
+  ErrMsg& operator=(const std::string& m) {
+    std::lock_guard<std::mutex> g(mu_);
+    if (!(first_ && held_)) s_ = m;
+    held_ = true;
+    return *this;
+  }
+  ErrMsg& operator=(const char* m) { return *this = std::string(m); }
+  const char* c_str() {
+    std::lock_guard<std::mutex> g(mu_);
+    return s_.c_str();
+  }
+  void first_only(bool on) {
+    std::lock_guard<std::mutex> g(mu_);
+    first_ = on;
+    held_ = false;
+  }
+
+ private:
+  std::mutex mu_;
+  std::string s_;
+  bool first_ = false, held_ = false;
+};
+
+struct praos_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipStream_t side[3] = {nullptr, nullptr, nullptr};   // concurrent crypto kernels
+  hipStream_t mside[3] = {nullptr, nullptr, nullptr};  // their key-cache misses (uncached verifies)
+  hipEvent_t mdone_ev[3] = {};
+  hipStream_t vstream = nullptr;                       // VRF stage V (no key-cache dependence)
+  hipStream_t vstream2 = nullptr;                      // the odd chunks' stage V of the stored-bytes pipeline
+  hipEvent_t v_ev = nullptr, v2_ev = nullptr;
+  hipEvent_t v0_ev = nullptr, v1_ev = nullptr;         // timing of k_vrf_v on its stream (kernel_ms[6])
+  hipEvent_t kc0_ev = nullptr, kc1_ev = nullptr;       // timing of k_kes_ck on its stream (kernel_ms[7])
+  hipEvent_t u_ev = nullptr;                           // stage U of the uncached VRF keys done
+  int tp_staged = 1;                                  // TPraos VRF through the staged kernels + VRF key cache
+                                                       // (PRAOS_TP_STAGED=0: the one-kernel k_vrf_tp)
+  int vrf_prio = 0;                                   // stage V and join waves at s_setprio 3 (PRAOS_VRF_PRIO 1 / 0;
+                                                       // -1: batches below SMALL_BATCH headers).  Off: with the
+                                                       // uncached verifies raised instead a 54k-header step takes
+                                                       // 2.83 ms against 3.16 (profiles/r04/i, r04/j)
+  int vrf_ilp4 = (int)ILP4_BATCH;                    // stage V from the ILP-4 build (k_vrf_v4.hip): PRAOS_VRF_ILP4
+                                                       // 1 always, 0 never, N > 1: batches below N headers
+                                                       // (profiles/r04/b: V alone 1.71 -> 1.51 ms at 54k; alone
+                                                       // at 108k the step was slower, 4.25 -> 4.37, but with the
+                                                       // ILP-4 uncached verifies and precompute beside it faster,
+                                                       // profiles/r04/y)
+  int v_excl = 0;                                      // the ILP-4 stage V holding its SIMDs alone (k_vrf_v4x):
+                                                       // PRAOS_V_EXCL (54k: 3.30 -> 3.46 ms, off)
+  int miss4 = -1;                                      // uncached OCert / KES verifies from the ILP-4 build
+                                                       // (k_miss4.hip): PRAOS_MISS4 1 / 0, -1 below ILP4_BATCH
+                                                       // (54k: 3.33 -> 3.09 ms; 108k: 4.26 -> 4.66, so not there)
+  int miss_prio = -1;                                  // ... at s_setprio 3: PRAOS_MISS_PRIO 1 / 0, -1 with miss4
+                                                       // from SHARD_SMALL headers on (below it, beside the GCD
+                                                       // inversion's shorter join, normal priority with
+                                                       // v_main 1 was faster: profiles/r06/s_retune)
+  int miss_prio_for(size_t n) const { return miss_prio >= 0 ? miss_prio : (n < SHARD_SMALL ? 0 : 1); }
+  long kes_pair = -1;                                  // k_kes_ck two headers per lane from this many hits on
+                                                       // (PRAOS_KES_PAIR, 0 = never; -1: from 196,608 when the
+                                                       // KES pass runs alone -- beside the OCert / VRF passes
+                                                       // the paired kernel has 4 % fewer VALU instructions
+                                                       // (0.983 G -> 0.941 G per 432k step) and the step is
+                                                       // longer, 9.847 -> 10.113 ms, medians of eight
+                                                       // alternating runs, profiles/r08_perkey_ab.json; its
+                                                       // waves are twice as long and spill 176 bytes per lane)
+  uint32_t kes_pair_min() const {
+    return kes_pair >= 0 ? (uint32_t)kes_pair : ((kernels & 5) ? 0u : 196608u);
+  }
+  int kes_dedup = -1;                                  // KES Merkle path dedup per leaf-key entry (PRAOS_KES_DEDUP
+                                                       // 1 / 0): the representatives walk once, a wave of
+                                                       // k_kes_ck whose paths all equal theirs skips the walk;
+                                                       // -1: from KES_DEDUP_BATCH headers on
+  bool use_kes_dedup(size_t n) const { return kes_dedup > 0 || (kes_dedup < 0 && n >= KES_DEDUP_BATCH); }
+  int vrf_perkey = 1;                                  // pool record per VRF key-cache entry (k_vrf_keyrec): a
+                                                       // wave of the cached stage F / the join whose cold keys
+                                                       // all equal their records' skips the two Blake2b and the
+                                                       // pool search (PRAOS_VRF_PERKEY 1 / 0)
+  hipEvent_t vrec_ev = nullptr;                        // the VRF key records are written (k_vrf_keyrec)
+  int v_main = -1;                                     // stage V on the main stream (PRAOS_V_MAIN; 0 off): no
+                                                       // cross-stream wait between the previous run's end and V;
+                                                       // the join after U and V on the VRF stream (3), or on the
+                                                       // main stream after a wait for U (1; 2: U's two streams
+                                                       // waited for separately).  54k headers (C5 1/8 shard):
+                                                       // 2.354-2.380 ms off, 2.284-2.330 (1), 2.315-2.332 (2),
+                                                       // 2.267-2.297 (3); 108k: 3.418-3.443 off, 3.36-3.42 on
+                                                       // (profiles/r06/k_vmain); -1: 2 below ILP4_BATCH
+                                                       // headers, 3 from it (with the GCD inversion, mode 1 +
+                                                       // normal-priority misses below SHARD_SMALL: 54k
+                                                       // 2.18-2.22 -> 2.17-2.19 ms, 40k 2.19-2.21 -> 2.08; then
+                                                       // mode 2 over mode 1 at 54k 2.16-2.19 -> 2.15, 40k equal
+                                                       // or 2 % faster; over mode 3 at 80k 2.78-2.80 -> 2.76,
+                                                       // 108k 3.24-3.26 -> 3.21-3.22, 216k 5.63-5.70 -> 5.70-5.71;
+                                                       // profiles/r06/s_retune)
+  int vmain_mode(size_t n) const { return v_main >= 0 ? v_main : (n < ILP4_BATCH ? 2 : 3); }
+  int pre_join = -1;                                   // the join's pool part (lookup, key hash, leader / nonce
+                                                       // values) as k_vrf_pool on the VRF miss stream before the
+                                                       // uncached U, off the chain after stage V (PRAOS_PRE_JOIN
+                                                       // 1 / 0, -1 below SMALL_BATCH)
+  int vrf_keys_first = 0;                              // PRAOS_VRF_KEYS_FIRST (see batch_run_impl; 54k: 2.80 ->
+                                                       // 2.85 ms, 108k 4.24 -> 4.27: off, profiles/r04/k)
+  int key4 = -1;                                       // key precompute from the ILP-4 build (k_keys4.hip):
+                                                       // PRAOS_KEY4 1 / 0, -1 below ILP4_BATCH (54k: 2.78-2.84
+                                                       // -> 2.76-2.77 ms; 108k 4.17 -> 4.21, profiles/r04/n)
+  bool use_key4(size_t n) const { return key4 > 0 || (key4 < 0 && n < ILP4_BATCH); }
+  // (round 5 also measured a key precompute with four lanes per key, DPP quad broadcasts: inside a
+  // step its chains were about as long as the ILP-4 build's and its four lanes per key took issue
+  // slots from the rest, 54k 2.72-2.75 -> 2.84-2.88 ms, 108k 3.79-3.84 -> 4.00,
+  // profiles/r05/c11_keyq_nobranch; removed in round 6)
+  int key_mode(size_t n) const { return use_key4(n) ? 1 : 0; }
+  int u4 = -1;                                         // cached stage U from the ILP-4 build (PRAOS_U4 1 / 0,
+                                                       // -1 below ILP4_BATCH; 54k 2.79 -> 2.75 ms, 108k 3.87-3.92
+                                                       // -> 3.81-3.83, profiles/r04/hh)
+  int ck4 = 0;                                         // cached OCert / KES verifies from the ILP-4 build
+                                                       // (PRAOS_CK4 1 / 0, -1 below ILP4_BATCH)
+  bool use_ck4(size_t n) const { return ck4 > 0 || (ck4 < 0 && n < ILP4_BATCH); }
+  bool use_u4(size_t n) const { return u4 > 0 || (u4 < 0 && n < ILP4_BATCH); }
+  bool use_miss4(size_t n) const { return miss4 > 0 || (miss4 < 0 && n < ILP4_BATCH); }
+  int v_ilp4(size_t n) const {
+    const bool on = vrf_ilp4 == 1 || (vrf_ilp4 > 1 && n < (size_t)vrf_ilp4);
+    return on ? (v_excl ? 2 : 1) : 0;
+  }
+  int vrf3 = -1;                                       // VRF as V | U | join (1), V | U + join (0), -1 auto:
+                                                       // the three-kernel form below 300k headers (latency)
+  // wide tier of the VRF key cache (praos_set_vrf_wide / PRAOS_VRF_WIDE): a key with this many uses
+  // in the batch gets positional tables (k_keys.hip); 0 off; -1 auto: WIDE_MIN_USES, the modelled
+  // break-even, in batches from WIDE_BATCH headers on (below it the longer key precompute is on the
+  // step's critical path and few keys reach the threshold)
+  int vrf_wide = -1;
+  int wide_prio = 1;                                   // the VRF key precompute at raised wave priority when it
+                                                       // builds wide tables (PRAOS_WIDE_PRIO 1 / 0)
+  int vrf_wide_cap = 4096;                             // wide keys per batch at most (PRAOS_VRF_WIDE_CAP)
+  uint32_t wide_min(size_t n) const {
+    return vrf_wide > 0 ? (uint32_t)vrf_wide : (vrf_wide < 0 && n >= WIDE_BATCH ? WIDE_MIN_USES : 0u);
+  }
+  // chunked stored-bytes pipeline (praos_verify_header_bytes): a copy stream, per-chunk
+  // events and persistent chunk batches (reused while they are large enough)
+  int pipeline = 0;                                    // PRAOS_OPT_PIPELINE (0 = auto)
+  hipStream_t cstream = nullptr;
+  hipStream_t dstream = nullptr;                       // replay: result downloads (rp_download_results)
+  hipStream_t decstream = nullptr;                     // submitted calls: each landed chunk's decode (off the
+                                                       // copy stream, whose next upload must not wait for it)
+  praos_batch* rp_keep[RP_SLOTS] = {};                 // replay batches kept between calls
+  uint8_t* cand_scratch = nullptr;                     // praos_validate_candidates: wire arena, item
+  size_t cand_scratch_sz = 0;                          // buffers and hash set, kept between calls
+  hipEvent_t up_ev[PIPE_MAX] = {}, done_ev[PIPE_MAX] = {};
+  praos_batch* pipe[PIPE_MAX] = {};
+  // praos_verify_header_bytes_submit: up to PIPE_CALLS calls in flight, on pipe[0 .. PIPE_CALLS) in turn
+  struct PipeCall {
+    bool active = false;
+    praos_out out{};
+    praos_decoded* dec = nullptr;
+    hipEvent_t ev = nullptr;                           // the call's run has ended (ctx stream)
+    uint64_t* off_h = nullptr;                         // pinned: its rebased offsets and lengths (async H2D:
+    uint32_t* len_h = nullptr;                         // a pageable copy would wait for the copy stream)
+    size_t cap = 0;
+  } pcall[PIPE_CALLS];
+  int pcall_next = 0;                                  // the slot the next submit takes: the oldest call's
+  int stream_chunk_v = 1;                              // submitted calls: stage V per landed chunk (1) or in the
+                                                       // run over the whole batch (0); PRAOS_STREAM_CHUNK_V.  C5,
+                                                       // 432k headers, three calls in flight: 13.2-13.4 ms per
+                                                       // call (1) against 15.3-17.6 (0), profiles/r06/l_stream
+  size_t pipe_n[PIPE_MAX] = {}, pipe_bytes[PIPE_MAX] = {};
+  int concurrent = 1;                                  // PRAOS_OPT_CONCURRENT
+  int kernels = 7;                                     // PRAOS_OPT_KERNELS
+  int keycache = 2;                                    // PRAOS_OPT_KEYCACHE (min uses; 0 = off)
+  size_t pbft_ck_min = PBFT_CK_MIN;                    // PRAOS_PBFT_CK_MIN (see PBFT_CK_MIN)
+  uint32_t pbft_stats[4] = {0, 0, 0, 0};               // praos_pbft_stats of the last praos_verify_pbft_headers
+  uint32_t pbft_raw[5] = {0, 0, 0, 0, 0};              // its download: the cache's counters, the verify count
+  size_t kes_nocache = KES_NOCACHE_BATCH;              // PRAOS_KES_NOCACHE (see KES_NOCACHE_BATCH)
+  int kc_min[3] = {0, 0, 0};                           // per cache (cold, VRF, KES leaf) min uses overriding
+                                                       // keycache when > 0 (PRAOS_KC_MIN="c,v,k")
+  int dedup = 1;                                       // PRAOS_OPT_DEDUP
+  // (round 5 measured the cached chains' last kernels -- cached U, the join, the cached OCert /
+  // KES verifies -- at s_setprio 2 / 3 below ILP4_BATCH: U shortened (54k 0.71 -> 0.43 ms) but
+  // stage V stretched past it and the step with it, 54k 2.74-2.76 -> 2.89-2.95 ms,
+  // profiles/r05/c14_ckprio; the option was removed in round 6)
+  int key_wave_prio = -1;                              // key precompute waves at s_setprio 3 (PRAOS_KEY_PRIO 1 / 0;
+                                                       // -1: batches below KEY_PRIO_BATCH headers)
+  hipEvent_t ev[6] = {};
+  hipEvent_t side_ev[4] = {};
+  hipEvent_t miss_ev[4] = {};                          // miss lists ready (OCert, KES, VRF), OCert misses done
+  float kernel_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  bool last_from_bytes = false;
+  bool v_timed = false;                                // the last run launched k_vrf_v
+  bool kes_ck_timed = false;                           // ... and k_kes_ck
+  ErrMsg err;
+  ge_niels* btab = nullptr;
+  ge_niels* bcomb16 = nullptr;                         // radix-2^16 comb of the cached-key chains (48 MB)
+  // pool-key store (PRAOS_OPT_POOL_KEYS, k_keys.hip): cold [0] and VRF [1] key entries and
+  // tables kept across runs; allocated on first use (256 MB of tables each)
+  struct PoolKeyStore {
+    uint32_t slots = 0, cap = 0;
+    uint32_t *pkey = nullptr, *count = nullptr, *base = nullptr, *entry_rep = nullptr, *entry_pos = nullptr;
+    uint32_t* kinfo = nullptr;
+    int32_t* pentry = nullptr;
+    ge_cached* ktab = nullptr;
+    uint32_t *scnt = nullptr, *spos = nullptr;           // per entry: uses this run, start of its hit range
+  } pks[2];                                            // [0] cold keys, [1] VRF keys
+  int pool_keys = -1;                                  // 1 on, 0 off, -1 on inside praos_replay_immutable*
+  bool replaying = false;
+  bool pk_on = false;                                  // this run uses the store
+  bool pk_reset[2] = {false, false};                   // empty store t before the next run that uses it
+  // (round 6 measured key hints for the stored-bytes pipeline -- each header's cold, VRF and KES
+  // leaf keys read on the host while the chunks upload, the key stores filled from them on the
+  // side streams before the last chunk lands -- bit-exact and slower, 432k e2e 15.7 -> 18.4 ms:
+  // the fill shares the GPU with the chunks' stage V and the tail stays throughput-bound;
+  // profiles/r06/h_e2e_hints.  Removed.)
+  // (round 5 measured a per-chunk key prefill in the stored-bytes pipeline -- the landed chunks'
+  // cold, KES leaf and VRF keys stored and their tables built while later chunks upload -- in two
+  // forms, both slower: the GPU is busy with the chunks' stage V during the upload, so the
+  // prefill only moves work there, and a key first seen in the last chunk still needs a
+  // latency-bound chain after it lands (432k, 8 chunks: 16.3-16.4 -> 18.2-18.5 ms,
+  // profiles/r05/c12_prefill_v3; 16.9 -> 19.2 ms, c7_e2e_timeline_pf{0,1}.txt).  Removed in round 6.)
+  // stored-bytes pipeline: the first chunk's size in percent of the others' (PRAOS_PIPE_HEAD):
+  // nothing runs on the GPU until it has landed and been decoded
+  int pipe_head = 25;                                  // (432k headers, 8 chunks: 100 -> 16.9-17.0 ms,
+                                                       // 50 -> 16.5, 25 -> 16.3-16.4, 12 -> 16.2-16.4)
+  // (round 6 measured the KES checks queued while later chunks upload, in two forms, both slower:
+  // uncached per landed chunk, 432k e2e 15.5-16.0 -> 18.2-18.9 ms; with the leaf-key cache over 1,
+  // 2 or 4 groups of landed chunks, 15.8 / 17.0 / 18.2-18.7 ms: the GPU runs the chunks' stage V
+  // during the upload, so the KES work there only stretches V; profiles/r06/g_e2e_kes.  Removed.)
+  int pipe_tail = 100;                                 // ... and the last chunk's (PRAOS_PIPE_TAIL): the run after it
+                                                       // waits for its decode, but a smaller one leaves more of the
+                                                       // batch's stage V after the upload (432k, 8 chunks: 100 ->
+                                                       // 16.4-16.7 ms, 50 -> 17.1-17.3, 25 -> 18.5-18.8;
+                                                       // profiles/r05/c16_pipe_tail)
+  // epoch
+  bool have_epoch = false;
+  std::vector<praos_pool> epoch_pools;                 // praos_set_epoch's inputs as installed (a call
+  praos_params epoch_params{};                         // with the same pools and parameters only swaps eta0)
+  praos_params params{};
+  uint32_t eta0[8] = {0};
+  int eta0_neutral = 1;
+  uint32_t npools = 0;
+  uint32_t* d_pool_hash = nullptr;   // sorted, 7 words each
+  uint32_t* d_pool_vrf = nullptr;    // 8 words
+  uint32_t* d_pool_x = nullptr;      // 4 words
+  int32_t* d_pool_map = nullptr;     // sorted idx -> caller idx
+  uint32_t* d_eta0 = nullptr;
+  std::vector<praos_pool> pools;     // caller order
+  std::map<std::string, int32_t> pool_by_hash;
+  // TPraos overlay schedule (praos_set_overlay): d, ascInv, epochs, genesis delegates
+  // sorted by genesis key hash; device table: delegate hash (7 words + 0) | VRF hash (8)
+  bool ovl_on = false;
+  uint64_t ovl_d_num = 0, ovl_d_den = 1, ovl_asc_inv = 1, ovl_base = 0, ovl_len = 1;
+  std::vector<praos_gen_deleg> gen_delegs;
+  std::set<std::string> gen_delegate_hashes;
+  uint32_t* d_gen = nullptr;
+  // caller ranges page-locked with praos_host_register: uploads from them skip the staging
+  std::mutex reg_mu;
+  std::vector<std::pair<uintptr_t, size_t>> registered;
+  // host <-> device staging for large transfers from pageable caller memory
+  uint8_t* pin[2] = {nullptr, nullptr};
+  uint8_t* zero_h = nullptr;                           // pinned zeros: an arena's tail padding by DMA (a fill
+                                                       // kernel on the copy stream could wait behind another
+                                                       // stream's kernels on a shared hardware queue)
+  hipEvent_t pin_ev[2] = {};
+  std::unique_ptr<CopyPool> pool;
+  // device buffers of the last freed batch, reused by the next one in allocation
+  // order (hipMalloc / hipFree of ~40 buffers cost ~20 ms per 432k batch)
+  std::vector<void*> spare;
+  std::vector<size_t> spare_sz;
+  // host-side repack arena of praos_batch_upload, kept across calls (a fresh 170 MB
+  // allocation per 432k batch cost its page faults and its unmapping on every call)
+  std::unique_ptr<uint8_t[]> h_arena;
+  size_t h_arena_cap = 0;
+  std::vector<uint64_t> h_off;
+  std::vector<uint32_t> h_len;
+};
+
+struct praos_batch {
+  size_t n = 0;
+  size_t body_bytes_len = 0;
+  uint64_t *slot = nullptr, *ocert_n = nullptr, *ocert_c0 = nullptr, *body_off = nullptr;
+  uint32_t* body_len = nullptr;
+  uint8_t *cold_vk = nullptr, *vrf_vk = nullptr, *vrf_out = nullptr, *vrf_proof = nullptr, *hot_vk = nullptr,
+          *ocert_sig = nullptr, *kes_sig = nullptr, *body = nullptr;
+  uint16_t* bits = nullptr;
+  uint16_t* bits3 = nullptr;   // per-kernel bits: ocert | kes | vrf
+  int32_t *pool_idx = nullptr, *pool_sorted = nullptr;
+  uint8_t *beta = nullptr, *leader = nullptr, *nonce = nullptr;
+  // per-lane point tables of the three crypto kernels (kcommon.hpp lane_tab)
+  ge_cached *tab_ocert = nullptr, *tab_kes = nullptr, *tab_vrf = nullptr;
+  ge_cached* tab_vrfu = nullptr;   // 8-entry lane tables of stage U on uncached VRF keys
+  bool v_done = false;             // stage V already queued on ctx->vstream (stored-bytes pipeline)
+  uint8_t* vrf_mid = nullptr;   // stage V -> stage F record of the two-stage VRF
+  uint8_t* vrf_mid2 = nullptr;  // TPraos: the leader certificate's record (allocated on first use)
+  ge_cached* tab_vrf2 = nullptr; // TPraos: the leader certificate's stage-V lane tables
+  size_t vrf_mid2_n = 0;
+  // TPraos overlay classes of the batch's slots (praos_set_overlay): device copy sized once
+  // per capacity, host arrays kept with the batch (the async upload reads them)
+  int32_t* dcls = nullptr;
+  size_t dcls_n = 0;
+  std::vector<uint64_t> slots_h;
+  std::vector<int32_t> cls_h;
+  // per-run public-key cache (k_keys.hip): [0] cold keys (OCert), [1] VRF keys, [2] KES leaf keys
+  struct KeyCache {
+    uint32_t cap = 0, max_entries = 0;
+    uint32_t *slot_rep = nullptr, *slot_cnt = nullptr, *entry_rep = nullptr, *entry_pos = nullptr, *kinfo = nullptr;
+    int32_t *slot_entry = nullptr, *item_slot = nullptr, *item_entry = nullptr;
+    uint32_t *counters = nullptr, *hit = nullptr, *miss = nullptr;   // counters: entries, hits, misses
+    ge_cached* ktab = nullptr;
+    uint8_t* rep_ok = nullptr;   // KES leaf keys: the Merkle walk verdict of each entry's representative
+    uint32_t* vrec = nullptr;    // VRF keys: the pool record of each entry (k_vrf_keyrec, VREC_WORDS words)
+    // this run's entry space: the arrays above, or the context's pool-key store
+    ge_cached* kt = nullptr;
+    uint32_t *ki = nullptr, *erep = nullptr, *epos = nullptr;
+    const uint32_t* ebase = nullptr;
+    uint32_t emax = 0;
+    int store = -1;
+    // the wide tier (VRF keys): buffers for wide_alloc keys, allocated when a run first uses it;
+    // wide.min_uses = this run's threshold (0: the tier is off and every hit is in `hit`)
+    KeyWide wide;
+    uint32_t wide_alloc = 0;
+  } kc[3];                       // [2] KES leaf keys
+  uint8_t* kes_leaf = nullptr;   // n*32: the leaf key of each header's KES signature
+  bool kc_used = false;
+  // OCert dedup (k_keys.hip k_ocert_dedup): hash set over the 144-byte OCert tuple,
+  // representative per item, list of representatives, their verify results
+  uint32_t dd_cap = 0;
+  uint32_t *dd_slot = nullptr, *dd_item_rep = nullptr, *dd_reps = nullptr, *dd_counters = nullptr;
+  uint8_t* dd_ok = nullptr;
+  bool dd_used = false;
+  // batches from stored bytes (praos_batch_upload_bytes): the arena and the
+  // decoded HeaderBody fields beyond the SoA above (k_decode.hip)
+  bool from_bytes = false;
+  uint32_t signed_stride = PRAOS_SIGNED_STRIDE;   // bytes per signed body (block batches: TP_SIGNED_STRIDE)
+  uint8_t* arena = nullptr;
+  size_t arena_len = 0;
+  uint64_t *hoff = nullptr, *block_no = nullptr, *prot_major = nullptr, *prot_minor = nullptr;
+  uint32_t *hlen = nullptr, *body_size = nullptr;
+  uint8_t *prev_hash = nullptr, *prev_genesis = nullptr, *body_hash = nullptr, *header_hash = nullptr;
+  uint16_t* dec_status = nullptr;
+  // block-integrity batches (k_block.hip): stored block spans, segment spans
+  // (segment-major [k][i]), per-segment hashes, results
+  bool is_block = false;
+  // several epoch nonces in one batch (praos_batch_set_nonces): device table of 9-word
+  // entries (nonce, neutral flag) and per-header index; host copies for the fold
+  uint32_t* eta_tab = nullptr;
+  uint8_t* eta_idx = nullptr;
+  bool decoded = false;          // praos_batch_decode ran: praos_batch_run skips the decode
+  // TPraos header batches from stored bytes (praos_verify_tpraos_header_bytes): the
+  // decoded leader certificate and its beta
+  bool tp_only = false;
+  uint8_t *lead_out = nullptr, *lead_proof = nullptr, *beta_l = nullptr;
+  uint64_t *blk_off = nullptr, *seg_off = nullptr;
+  uint32_t *blk_len = nullptr, *seg_len = nullptr;
+  uint8_t *nseg = nullptr, *split_status = nullptr, *seg_hash = nullptr, *blk_result = nullptr, *blk_hash = nullptr;
+  // CRC-32 of the block spans (k_crc32.hip): tile list, per-tile registers, results; kept for re-runs
+  uint32_t *crc_first = nullptr, *crc_raw = nullptr, *crc_out = nullptr;
+  uint32_t crc_tiles = 0;
+  // Byron blocks (k_byron.hip): kind per block, the EBBs' epoch, the main blocks' span table,
+  // the failing body comparisons; allocated on first use (byron_buffers)
+  uint8_t *byr_kind = nullptr, *byr_which = nullptr;
+  uint64_t* byr_epoch = nullptr;
+  uint32_t* byr_spans = nullptr;
+  std::vector<void*> owned;
+  std::vector<size_t> owned_sz;
+  praos_ctx* owner = nullptr;
+  // replay batches (rp_batch_alloc): capacity, decode / run events, pinned nonce table
+  size_t cap_n = 0, cap_bytes = 0;
+  hipEvent_t dec_ev = nullptr, run_ev = nullptr;
+  uint32_t* eta_h = nullptr;       // pinned: 9-word entries (nonce, neutral flag)
+  uint8_t* eidx_h = nullptr;       // pinned: per-header index
+  uint16_t* res_bits_h = nullptr;  // pinned: the replay's result downloads (bits, pool index), cap_n each
+  int32_t* res_pidx_h = nullptr;
+  uint8_t* dec_h = nullptr;        // pinned: the replay's decoded-field downloads (DEC_H_BYTES per header)
+};
+
+static constexpr size_t KT_BYTES = 16 * 8 * 4 * 32; // per cached key: 16 tables x 8 cached points
+static constexpr size_t WT_BYTES = 22 * 32 * 4 * 32; // per wide key: 22 positions x 32 cached points (WT_STRIDE)
+static constexpr uint32_t KC_MAX_ENTRIES = 1u << 20;   // a key used twice already pays for its tables
+
+#define HIPCHK(ctx, x)                                                                    \
+  do {                                                                                    \
+    if ((ctx)->device < 0) {                                                              \
+      (ctx)->err = "host-only context: no HIP device";                                    \
+      return PRAOS_E_STATE;                                                               \
+    }                                                                                     \
+    hipError_t e_ = (x);                                                                  \
+    if (e_ != hipSuccess) {                                                               \
+      (ctx)->err = std::string(#x) + ": " + hipGetErrorString(e_);                        \
+      return PRAOS_E_HIP;                                                                 \
+    }                                                                                     \
+  } while (0)
+
+static inline unsigned nblocks(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
+
+template <typename T>
+static hipError_t dalloc(praos_batch* b, T** p, size_t bytes) {
+  void* q = nullptr;
+  size_t sz = bytes ? bytes : 16;
+  const size_t k = b->owned.size();
+  praos_ctx* c = b->owner;
+  hipError_t e = hipSuccess;
+  if (c && k < c->spare.size() && c->spare[k] && c->spare_sz[k] >= sz && c->spare_sz[k] <= 2 * sz + 4096) {
+    q = c->spare[k];                 // the previous batch's buffer at the same position
+    sz = c->spare_sz[k];
+    c->spare[k] = nullptr;
+  } else {
+    e = hipMalloc(&q, sz);
+  }
+  if (e == hipSuccess) { b->owned.push_back(q); b->owned_sz.push_back(sz); *p = (T*)q; }
+  return e;
+}
+
+// The pool part of a ledger view (lvPoolDistr): the caller's pools, the map hash28 -> caller
+// index (OCert counter slots), and on a device the tables the VRF join and the leader test read
+// (hashes sorted, 7 words each | VRF key hashes, 8 | x = -(sigma * c) in Fixed E34, 4 | sorted
+// index -> caller index).  praos_set_epoch installs one in the context; the per-epoch replay
+// (praos_replay_immutable_views) keeps one per view and swaps its device tables in between batches.
+struct rp_view {
+  int device = -1;
+  uint32_t npools = 0;
+  std::vector<praos_pool> pools;
+  std::map<std::string, int32_t> by_hash;
+  uint32_t *d_hash = nullptr, *d_vrf = nullptr, *d_x = nullptr;
+  int32_t* d_map = nullptr;
+};
+
+// The functions that cross the API units' boundaries.
+namespace praos_impl {
+
+// praos_api.hip: the radix-2^16 comb, k_decode_praos over a from-bytes batch, the overlay class
+// of a slot
+int ensure_bcomb16(praos_ctx* c);
+int batch_decode(praos_ctx* c, praos_batch* b);
+int32_t overlay_class(const praos_ctx* c, uint64_t slot);
+
+// praos_run.hip: the key-cache prepass (hash set, entries, hit / miss lists), the entries' key
+// tables, and the crypto step's stream scheduler
+int kc_lists(praos_ctx* c, praos_batch* b, praos_batch::KeyCache& k, size_t n, const uint8_t* keys, hipStream_t st,
+             const uint32_t* list, const uint32_t* count, int which);
+void kc_precompute(praos_ctx* c, praos_batch::KeyCache& k, const uint8_t* keys, int kind, hipStream_t st, size_t n);
+int batch_run_impl(praos_ctx* c, praos_batch* b);
+
+}  // namespace praos_impl

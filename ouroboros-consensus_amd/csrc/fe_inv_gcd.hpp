@@ -13,7 +13,7 @@
 // v is y^-1 2^(30 k) and one multiplication by 2^(-30 k) ends it.  y = 0 gives v = 0, as
 // 0^(p-2) does.
 //
-// Cost per inversion, counted in the gfx950 ISA (tools/microbench/inv_gcd.hip prints both):
+// Cost per inversion, counted in the gfx950 ISA (tools/microbench/inv_bench.py times both):
 // ~13-14 x (30 x ~24 + ~560) VALU instructions, mostly VOP2 selects and subtractions, against
 // Fermat's 254 squarings + 11 products (~32k VALU instructions, most of them 64-bit MACs).
 // The result is the same field element as Fermat's (the caller canonicalises for encoding);

@@ -42,8 +42,6 @@
 #include <unordered_map>
 #include <vector>
 
-void praos_set_error_(praos_ctx* c, const std::string& m);   // praos_api.hip
-
 namespace {
 
 constexpr size_t NT_ITEMS = 256;               // items per block of the k_hdr_* kernels (kcommon.hpp NT)
@@ -652,8 +650,6 @@ extern "C" int praos_validate_candidates_tpraos(praos_ctx* c, const praos_tpraos
 //     device   the front half with era mask 1 << 0 and the rows' kinds (k_hdr_row_kind), then
 //              praos_verify_pbft_headers' kernels over the rows, read from the wire arena;
 //     host     the PBFT fold per fragment in the client's mode, through the item-to-row map.
-bool praos_pbft_delegs_ok_(const uint8_t* delegs, uint32_t n);   // praos_pbft.hip
-
 extern "C" int praos_validate_candidates_pbft(praos_ctx* c, const praos_pbft_candidates_in* in,
                                               praos_pbft_fragments* frags, praos_pbft_candidates_out* out) {
   if (!c || !in || !frags || !out || !items_ok(&in->items)) return PRAOS_E_ARG;

@@ -25,10 +25,6 @@ struct praos_group {
   std::vector<void*> registered;          // praos_group_host_register ranges
 };
 
-void praos_replay_scope_(praos_ctx* c, bool on);   // praos_api.hip
-int praos_ctx_note_registered_(praos_ctx* c, void* p, size_t len, bool add);   // praos_api.hip
-int praos_ctx_device_(praos_ctx* c);                                            // praos_api.hip
-
 namespace {
 
 // [i0, i1) of member k when n items are split over m members
@@ -151,7 +147,7 @@ void praos_group_close(praos_group* g) {
   // ranges the caller left registered are unpinned here (after the members' work has drained)
   std::vector<void*> left;
   left.swap(g->registered);
-  const int dev0 = g->ctx.empty() ? -1 : praos_ctx_device_(g->ctx[0]);
+  const int dev0 = g->ctx.empty() ? -1 : rp_device(g->ctx[0]);
   for (praos_ctx* c : g->ctx) praos_close(c);
   if (dev0 >= 0 && !left.empty()) {
     (void)hipSetDevice(dev0);
@@ -272,7 +268,7 @@ int praos_group_verify_block_integrity(praos_group* g, const praos_header_bytes*
 // member devices all read by DMA), so each member's upload of its shard is a direct copy.
 int praos_group_host_register(praos_group* g, void* p, size_t len) {
   if (!g || !p || len == 0 || g->ctx.empty()) return PRAOS_E_ARG;
-  if (hipSetDevice(praos_ctx_device_(g->ctx[0])) != hipSuccess ||
+  if (hipSetDevice(rp_device(g->ctx[0])) != hipSuccess ||
       hipHostRegister(p, len, hipHostRegisterPortable) != hipSuccess) {
     g->err = "hipHostRegister failed";
     return PRAOS_E_HIP;
@@ -288,7 +284,7 @@ int praos_group_host_unregister(praos_group* g, void* p) {
   if (it == g->registered.end()) { g->err = "range not registered with the group"; return PRAOS_E_ARG; }
   g->registered.erase(it);
   for (praos_ctx* c : g->ctx) praos_ctx_note_registered_(c, p, 0, false);
-  (void)hipSetDevice(praos_ctx_device_(g->ctx[0]));
+  (void)hipSetDevice(rp_device(g->ctx[0]));
   if (hipHostUnregister(p) != hipSuccess) { g->err = "hipHostUnregister failed"; return PRAOS_E_HIP; }
   return PRAOS_OK;
 }

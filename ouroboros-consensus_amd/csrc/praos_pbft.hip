@@ -18,8 +18,6 @@
 #include <string>
 #include <vector>
 
-void praos_set_error_(praos_ctx* c, const std::string& m);   // praos_api.hip
-
 using Hash28 = std::array<uint8_t, 28>;
 
 // hashVerKey on the host: Blake2b-224(SHA3-256(58 40 || xpub64))

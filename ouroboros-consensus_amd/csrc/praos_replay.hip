@@ -63,10 +63,6 @@
 #include <thread>
 #include <vector>
 
-void praos_set_error_(praos_ctx* c, const std::string& m);   // praos_api.hip
-void rp_copy_pin(praos_ctx* c, const std::vector<int>& cpus);  // praos_api.hip
-void praos_replay_scope_(praos_ctx* c, bool on);   // replay call scope: first error kept, pool-key store on
-
 namespace {
 
 bool read_file(const std::string& path, std::vector<uint8_t>& out) {

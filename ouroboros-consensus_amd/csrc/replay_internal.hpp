@@ -1,11 +1,26 @@
 #pragma once
 // replay_internal.hpp -- entry points of libpraos_hip used by the replay driver
-// (praos_replay.hip) for its threaded pipeline; C++ linkage, not part of the C ABI.
+// (praos_replay.hip) for its threaded pipeline, and the few shims the host modules (replay, group,
+// candidates, pbft) and the API units share; C++ linkage, not part of the C ABI.
 #include "praos_hip.h"
 #include <hip/hip_runtime_api.h>
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <vector>
+
+// The context for the other host modules (praos_api.hip): its error text; the replay call scope
+// (first error kept, pool-key store on); the group's page-locked ranges (praos_group_host_register:
+// pinned once, known to every member); the staging copy threads onto the given CPUs (empty: back to
+// the process's own mask).
+void praos_set_error_(praos_ctx* c, const std::string& m);
+void praos_replay_scope_(praos_ctx* c, bool on);
+int praos_ctx_note_registered_(praos_ctx* c, void* p, size_t len, bool add);
+void rp_copy_pin(praos_ctx* c, const std::vector<int>& cpus);
+// Byron's delegation map (praos_pbft.hip): hashVerKey on the host, and the Bimap's rule (no
+// duplicate in either column)
+void praos_pbft_key_hash_host_(const uint8_t* keys64, size_t n, uint8_t* out28);
+bool praos_pbft_delegs_ok_(const uint8_t* delegs, uint32_t n);
 
 struct praos_span {           // a run of stored bytes in host memory (e.g. an mmapped chunk file)
   const uint8_t* p;
@@ -61,7 +76,7 @@ rp_tables rp_view_tables(const rp_view* v);
 // praos_validate_headers_nonces / praos_tpraos_validate_headers_nonces with the evolving nonce
 // after each header precomputed by the caller's nonce chain (used until the first invalid header);
 // view (may be NULL: the context's praos_set_epoch pools) is the ledger view the batch was verified
-// under.
+// under.  (praos_fold.hip)
 int rp_fold(praos_ctx* c, const praos_headers* h, const uint8_t* prev_hash, const uint8_t* prev_is_genesis,
             const praos_out* crypto, praos_envelope* env, const praos_epoch_info* ei, praos_chain_state* st,
             const praos_nonce* etas, uint32_t k, const uint8_t* eta_idx, const praos_nonce* evolving_after,
