@@ -522,6 +522,73 @@ int praos_validate_chunk_cfg(praos_ctx* ctx, const praos_chunk* chunk, const pra
 int praos_verify_byron_integrity(praos_ctx* ctx, const praos_header_bytes* blocks, uint64_t epoch_slots,
                                  uint32_t protocol_magic, uint8_t* result, uint8_t* which);
 
+/* ---- Transaction index of stored blocks (additive: ABI version unchanged) ----
+ * One row per transaction of each stored block, built on the device from the block bytes, and
+ * the per-block statistics db-analyser's ledger-free analyses print.  Replaces, per block,
+ * HasAnalysis.countTxOutputs / blockTxSizes / blockStats (Cardano/Tools/DBAnalyser/Block/
+ * Shelley.hs:61-98, Block/Byron.hs:34-86) and, per row, txId (Blake2b-256 of the stored body).
+ * blocks: whole stored blocks as praos_verify_block_integrity takes them.  A Shelley-based block
+ * is [header, s1 bodies, s2 witness sets, s3 {index: aux}, (s4 [invalid indices])], arrays and
+ * maps definite or indefinite at every level.  Row t of a block with n = |s1|:
+ *   body / wit / aux   spans into blocks->bytes; aux_len = 0: no auxiliary data
+ *   size               1 + body_len + wit_len + (aux_len or 1): sizeTxF, [body, wits, aux / null]
+ *   n_out              items of the array under the body map's first key 1; no key 1: 0
+ *   ex_steps           blocks with s4: the sum mod 2^64 of the steps of the redeemers under the
+ *                      witness set's first key 5, [[tag, index, data, [mem, steps]], ...] or
+ *                      {key: [data, [mem, steps]], ...}; blocks without s4 (and a witness set
+ *                      that is no map or has no key 5): 0
+ *   is_valid           0 when t is listed in s4
+ *   tx_id              Blake2b-256 of the stored body bytes
+ * Byron (cfg->byron != 0): an EBB has no rows; a main block one row per [tx, witnesses] item of
+ * txPayload: body = tx, wit = witnesses, no aux, size = the length of the whole item, n_out =
+ * items of tx[1], ex_steps 0, is_valid 1, tx_id = Blake2b-256 of the tx item.  With cfg->byron
+ * == 0 a Byron item ([0, ...] / [1, ...]) is PRAOS_TXI_DECODE.
+ * A block that is not PRAOS_TXI_OK has n_tx 0, zero statistics and no rows. */
+#define PRAOS_TXI_OK     0u
+#define PRAOS_TXI_DECODE 1u /* not accepted by the block split (k_block.hip / k_byron.hip), or a span outside the arena */
+#define PRAOS_TXI_SHAPE  2u /* s1 / s2 / s4 no array, s3 no map, |s2| /= |s1|, an s3 key or s4 entry not an
+                               unsigned integer < n, a body no map, key 1 no array, key 5 of neither redeemer
+                               form (Byron: tx no array of two items at least, tx[1] no array) */
+typedef struct {
+  uint32_t byron;                 /* non-zero: Byron blocks and EBBs are indexed */
+  uint32_t pad_;
+} praos_txi_cfg;
+typedef struct {                  /* per block; every pointer may be NULL = not returned */
+  uint8_t* status;                /* n: PRAOS_TXI_* */
+  uint32_t* n_tx;                 /* n */
+  uint64_t* txs_size;             /* n: sum of size */
+  uint64_t* n_out;                /* n: sum of n_out */
+  uint64_t* ex_steps;             /* n: sum of ex_steps mod 2^64 */
+  uint64_t* tx_first;             /* n + 1: exclusive prefix sum of n_tx; block i's rows are
+                                     [tx_first[i], tx_first[i + 1]) */
+} praos_txi_stats;
+typedef struct {                  /* per row; caller buffers of cap rows, every pointer may be NULL */
+  size_t cap;
+  size_t n_rows;                  /* out: the rows of the call */
+  uint32_t* block;                /* the row's block */
+  uint64_t* body_off;
+  uint32_t* body_len;
+  uint64_t* wit_off;
+  uint32_t* wit_len;
+  uint64_t* aux_off;
+  uint32_t* aux_len;
+  uint32_t* size;
+  uint32_t* n_out;
+  uint64_t* ex_steps;
+  uint8_t* is_valid;
+  uint8_t* tx_id;                 /* cap * 32 */
+} praos_txi_rows;
+/* stats and rows may be NULL.  When a row array is given and rows->cap < n_rows: PRAOS_E_ARG with
+ * rows->n_rows = the count needed and stats filled; with no row array given cap is not looked at
+ * (the sizing call).  n = 0 is PRAOS_OK with tx_first[0] = 0. */
+int praos_index_block_txs(praos_ctx* ctx, const praos_header_bytes* blocks, const praos_txi_cfg* cfg,
+                          praos_txi_stats* stats, praos_txi_rows* rows);
+/* The same over a praos_block_batch_upload batch, with no second upload (bench; callers that run
+ * praos_block_batch_run and the index over one upload, in either order: the index works in
+ * buffers of its own and leaves the batch's results as they are). */
+int praos_block_batch_tx_index(praos_ctx* ctx, praos_batch* b, const praos_txi_cfg* cfg, praos_txi_stats* stats,
+                               praos_txi_rows* rows);
+
 /* ---- Byron header validation: PBFT (additive as the two sections above: ABI version unchanged) ----
  * validateHeader for Byron = validateEnvelope (HeaderValidation.hs:297-344 with the Byron
  * instance, Byron/Ledger/HeaderValidation.hs:39-75) + PBFT updateChainDepState

@@ -62,6 +62,9 @@ module Ouroboros.Consensus.Protocol.Praos.Batch
   , ChunkParse (..)
   , validateChunkBatch
   , praosVerifyBlockIntegrity
+    -- * Transaction index of stored blocks (db-analyser's block statistics)
+  , BlockTxStats (..)
+  , praosIndexBlockTxs
     -- * Byron header validation (PBFT)
   , PBftParamsC (..)
   , PBftTipC
@@ -209,6 +212,13 @@ foreign import ccall safe "praos_validate_chunk" c_validate_chunk
 -- layout-byron praos_chunk_cfg (24 bytes): slots_per_kes_period@0 byron_epoch_slots@8 byron_protocol_magic@16 pad_@20
 foreign import ccall safe "praos_validate_chunk_cfg" c_validate_chunk_cfg
   :: Ptr PraosCtx -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> Ptr Word8 -> IO CInt
+-- additive as well (ABI version unchanged): the transaction index of stored blocks.  Its structs
+-- (checked against the C compiler by tests/test_txindex_abi.py, which owns the "layout-txi" lines):
+-- layout-txi praos_txi_cfg (8 bytes): byron@0 pad_@4
+-- layout-txi praos_txi_stats (48 bytes): status@0 n_tx@8 txs_size@16 n_out@24 ex_steps@32 tx_first@40
+-- layout-txi praos_txi_rows (112 bytes): cap@0 n_rows@8 block@16 body_off@24 body_len@32 wit_off@40 wit_len@48 aux_off@56 aux_len@64 size@72 n_out@80 ex_steps@88 is_valid@96 tx_id@104
+foreign import ccall safe "praos_index_block_txs" c_index_block_txs
+  :: Ptr PraosCtx -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> IO CInt
 -- additive as well (ABI version unchanged): Byron header validation.  The structs
 -- validatePBftHeaderBatch pokes and peeks (checked against the C compiler by tests/test_pbft_abi.py;
 -- "layout-pbft": the other layout lines belong to the tests named above):
@@ -991,6 +1001,50 @@ praosVerifyBlockIntegrity ctx spkp arena offs lens = do
         PraosBatchCtx p -> c_verify_block_integrity p (castPtr hb) spkp rp nullPtr
         PraosBatchGroup g _ _ -> c_group_verify_block_integrity g (castPtr hb) spkp rp nullPtr
   VS.unsafeFreeze res
+
+-- | Per stored block what db-analyser's ledger-free analyses read off its transactions:
+-- 'HasAnalysis.blockTxSizes' (its length and sum), 'HasAnalysis.countTxOutputs' and the execution
+-- steps of 'HasAnalysis.blockStats' (Cardano/Tools/DBAnalyser/Block/Shelley.hs:61-98,
+-- Block/Byron.hs:34-86).  Status 0, or 1 (the block does not decode) / 2 (not the shape of a block
+-- of transactions), with zero statistics.
+data BlockTxStats = BlockTxStats
+  { btsStatus  :: !(VS.Vector Word8)
+  , btsNumTxs  :: !(VS.Vector Word32)
+  , btsTxsSize :: !(VS.Vector Word64)
+  , btsOutputs :: !(VS.Vector Word64)
+  , btsExSteps :: !(VS.Vector Word64)
+  }
+
+-- | praos_index_block_txs over the blocks @arena[off_i .. off_i + len_i)@ (whole stored blocks, as
+-- 'praosVerifyBlockIntegrity' takes them), statistics only: no row array is asked for, so the
+-- transaction ids are not computed.  @byron@: Byron blocks and EBBs are indexed too.
+praosIndexBlockTxs :: PraosBatchCtx -> Bool -> BS.ByteString -> VS.Vector Word64 -> VS.Vector Word32
+                   -> IO BlockTxStats
+praosIndexBlockTxs ctx byron arena offs lens = do
+  let n = VS.length offs
+  when (VS.length lens /= n) $ throwIO (PraosBatchError (-1) "praosIndexBlockTxs: vector lengths differ")
+  let p = ctxPtr ctx                           -- a group's first member: the index has no group form
+  st <- VSM.new n
+  ntx <- VSM.new n
+  sz <- VSM.new n
+  nout <- VSM.new n
+  ex <- VSM.new n
+  BSU.unsafeUseAsCStringLen arena $ \(ap, alen) ->
+    VS.unsafeWith offs $ \offp -> VS.unsafeWith lens $ \lenp ->
+    VSM.unsafeWith st $ \stp -> VSM.unsafeWith ntx $ \ntxp -> VSM.unsafeWith sz $ \szp ->
+    VSM.unsafeWith nout $ \noutp -> VSM.unsafeWith ex $ \exp_ ->
+    allocaBytes 40 $ \hb -> allocaBytes 8 $ \cfg -> allocaBytes 48 $ \stats -> allocaBytes 112 $ \rows -> do
+      pokeByteOff hb 0 (fromIntegral n :: CSize) >> pokeByteOff hb 8 ap
+      pokeByteOff hb 16 (fromIntegral alen :: CSize)
+      pokeByteOff hb 24 offp >> pokeByteOff hb 32 lenp
+      pokeByteOff cfg 0 (if byron then 1 else 0 :: Word32) >> pokeByteOff cfg 4 (0 :: Word32)
+      fillBytes stats 0 48
+      pokeByteOff stats 0 stp >> pokeByteOff stats 8 ntxp >> pokeByteOff stats 16 szp
+      pokeByteOff stats 24 noutp >> pokeByteOff stats 32 exp_
+      fillBytes rows 0 112                     -- no row arrays: cap is not looked at
+      check ctx $ c_index_block_txs p (castPtr hb) (castPtr cfg) (castPtr stats) (castPtr rows)
+  BlockTxStats <$> VS.unsafeFreeze st <*> VS.unsafeFreeze ntx <*> VS.unsafeFreeze sz <*> VS.unsafeFreeze nout
+               <*> VS.unsafeFreeze ex
 
 -- | One chunk's validation outcome: per block Nothing (its CRC matched the secondary index's
 -- checksum: trusted without the integrity check) or the PRAOS_BLK_* bits (0 = intact), the first

@@ -49,6 +49,7 @@ enum : uint32_t {
   BS_COUNT
 };
 static_assert(BS_COUNT == PRAOS_BYRON_SPANS, "span table width");
+static_assert(BS_TXP_O == PRAOS_BYRON_SPAN_TXP && BS_TXP_L == BS_TXP_O + 1, "the columns k_txindex.hip reads");
 
 __global__ void __launch_bounds__(NT) k_byron_split(size_t n, const uint8_t* __restrict__ arena, uint64_t arena_len,
                                                     const uint64_t* __restrict__ blk_off,

@@ -241,6 +241,44 @@ void launch_byron_integrity(dim3 grid, dim3 block, hipStream_t stream, size_t n,
                             const uint64_t* blk_off, const uint32_t* blk_len, const uint8_t* kind,
                             const uint32_t* spans, uint32_t cfg_pm, const ge_niels* gbtab, ge_cached* tabs,
                             uint8_t* result, uint8_t* which);
+// k_txindex.hip: the transaction index of stored blocks.  Row arrays on the device (the
+// provisional rows, and the selection of final ones a caller asked for: NULL = not written)
+#define PRAOS_BYRON_SPAN_TXP 20   // k_byron.hip's BS_TXP_O; BS_TXP_L follows it
+struct praos_txi_dev_rows {
+  uint32_t* block;
+  uint64_t* body_off;
+  uint32_t* body_len;
+  uint64_t* wit_off;
+  uint32_t* wit_len;
+  uint64_t* aux_off;
+  uint32_t* aux_len;
+  uint32_t* size;
+  uint32_t* n_out;
+  uint64_t* ex_steps;
+  uint8_t* is_valid;
+  uint8_t* tx_id;
+};
+// count: per block the transaction count, PRAOS_TXI_* status and kind, from k_block_split's
+// segment spans and (byron != 0) k_byron_split's kind and txPayload span columns.  emit: the row
+// spans at first[i] + t, one lane per (segment, block); the row arrays zeroed, is_valid set to ones.  rows: n_out, ex_steps, size per row; bad[i] |= 1
+// for a row outside the shapes.  reduce: status and sums per block.  final: the rows of the OK
+// blocks at tfirst[i] + t, with tx_id.
+void launch_txi_count(hipStream_t stream, size_t n, const uint8_t* arena, uint64_t arena_len, const uint64_t* blk_off,
+                      const uint32_t* blk_len, int byron, const uint64_t* seg_off, const uint32_t* seg_len,
+                      const uint8_t* nseg, const uint8_t* split_status, const uint8_t* byr_kind, const uint32_t* txp_o,
+                      const uint32_t* txp_l, uint32_t* cnt, uint8_t* status, uint8_t* kind);
+void launch_txi_emit(hipStream_t stream, size_t n, const uint8_t* arena, const uint64_t* blk_off,
+                     const uint64_t* seg_off, const uint32_t* seg_len, const uint32_t* txp_o, const uint32_t* txp_l,
+                     const uint8_t* kind, const uint8_t* status, const uint32_t* cnt, const uint32_t* first,
+                     const praos_txi_dev_rows* rows);
+void launch_txi_rows(hipStream_t stream, size_t nrows, const uint8_t* arena, const uint8_t* kind,
+                     const praos_txi_dev_rows* rows, uint32_t* bad);
+void launch_txi_reduce(hipStream_t stream, size_t n, const uint32_t* cnt, const uint32_t* first, const uint32_t* bad,
+                       const praos_txi_dev_rows* rows, uint8_t* status, uint32_t* n_tx, uint64_t* txs_size,
+                       uint64_t* n_out, uint64_t* ex_steps);
+void launch_txi_final(hipStream_t stream, size_t nrows, const uint8_t* arena, const uint8_t* status,
+                      const uint32_t* first, const uint32_t* tfirst, const praos_txi_dev_rows* rows,
+                      const praos_txi_dev_rows* out);
 // k_pbft.hip: Byron header validation.  decode: one lane per stored header (columns, the verify
 // inputs keys / sig / hram, the delegate's key hash dhash [n][28] and its index in dtab -- n_delegs
 // x 8 words sorted by the 7 hash words, word 7 the caller's index -- and the list of lanes that

@@ -201,6 +201,30 @@ class ChunkCfg(ctypes.Structure):
                 ("byron_protocol_magic", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
 
 
+# Transaction index of stored blocks (praos_index_block_txs / praos_block_batch_tx_index)
+TXI_OK, TXI_DECODE, TXI_SHAPE = 0, 1, 2
+TXI_STATS_FIELDS = (  # name, dtype (praos_txi_stats; tx_first has n + 1 entries)
+    ("status", np.uint8), ("n_tx", np.uint32), ("txs_size", np.uint64), ("n_out", np.uint64),
+    ("ex_steps", np.uint64), ("tx_first", np.uint64))
+TXI_ROW_FIELDS = (  # name, dtype, record shape (praos_txi_rows)
+    ("block", np.uint32, ()), ("body_off", np.uint64, ()), ("body_len", np.uint32, ()), ("wit_off", np.uint64, ()),
+    ("wit_len", np.uint32, ()), ("aux_off", np.uint64, ()), ("aux_len", np.uint32, ()), ("size", np.uint32, ()),
+    ("n_out", np.uint32, ()), ("ex_steps", np.uint64, ()), ("is_valid", np.uint8, ()), ("tx_id", np.uint8, (32,)))
+
+
+class TxiCfg(ctypes.Structure):
+    _fields_ = [("byron", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
+
+
+class TxiStats(ctypes.Structure):
+    _fields_ = [(name, _CT[dt]) for name, dt in TXI_STATS_FIELDS]
+
+
+class TxiRows(ctypes.Structure):
+    _fields_ = [("cap", ctypes.c_size_t), ("n_rows", ctypes.c_size_t)] + [(name, _CT[dt])
+                                                                          for name, dt, _ in TXI_ROW_FIELDS]
+
+
 # Byron blocks: further PRAOS_BLK_* bits and the failing body comparisons (PRAOS_BYRON_W_*)
 BLK_PBFT_SIG, BLK_PM = 0x08, 0x10
 BYRON_W_DLG, BYRON_W_UPD, BYRON_W_NTX, BYRON_W_WIT, BYRON_W_ROOT = 0x01, 0x02, 0x04, 0x08, 0x10
@@ -407,6 +431,10 @@ SIGNATURES = {
     "praos_pbft_state_encode": (ctypes.c_int, [ctypes.POINTER(PbftStateC), u8p, ctypes.c_size_t,
                                                ctypes.POINTER(ctypes.c_size_t)]),
     "praos_pbft_state_decode": (ctypes.c_int, [u8p, ctypes.c_size_t, ctypes.POINTER(PbftStateC)]),
+    "praos_index_block_txs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HeaderBytes), ctypes.POINTER(TxiCfg),
+                                             ctypes.POINTER(TxiStats), ctypes.POINTER(TxiRows)]),
+    "praos_block_batch_tx_index": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(TxiCfg),
+                                                  ctypes.POINTER(TxiStats), ctypes.POINTER(TxiRows)]),
     "praos_block_batch_upload": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.POINTER(HeaderBytes)]),
     "praos_block_batch_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "praos_block_batch_download": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u8p, u8p]),
@@ -790,6 +818,68 @@ class Context:
         self.check(self.L.praos_verify_block_integrity(self.h, ctypes.byref(hb), slots_per_kes_period, ptr(res),
                                                        ptr(bh)))
         return res, bh
+
+    # ---- stored blocks: the transaction index (k_txindex.hip) ----
+    def _tx_index(self, call, n, byron, rows, cap, out=None):
+        """call(cfg, stats, rows) -> rc.  rows: True (every row array), False (none) or the names
+        wanted; cap: the row capacity (None: sized by a first call without row arrays); out: the
+        (stats, rows) dicts of an earlier call with the same n and cap, written again in place."""
+        cfg = TxiCfg(1 if byron else 0, 0)
+        S = out[0] if out else {name: np.zeros(n + 1 if name == "tx_first" else n, dt)
+                                for name, dt in TXI_STATS_FIELDS}
+        st = TxiStats()
+        for name, dt in TXI_STATS_FIELDS:
+            setattr(st, name, ptr(S[name], _CT[dt]))
+        names = [f[0] for f in TXI_ROW_FIELDS] if rows is True else list(rows or ())
+        rw = TxiRows()
+        if cap is None:
+            self.check(call(cfg, st, rw))
+            cap = int(rw.n_rows)
+        R = out[2] if out else {name: np.zeros((cap,) + shp, dt) for name, dt, shp in TXI_ROW_FIELDS
+                                if name in names}
+        rw = TxiRows()
+        rw.cap = cap
+        for name, dt, _ in TXI_ROW_FIELDS:
+            if name in R:
+                setattr(rw, name, ptr(R[name], _CT[dt]))
+        rc = call(cfg, st, rw)
+        if rc == E_ARG and rw.n_rows > cap:
+            msg = self.L.praos_last_error(self.h)
+            err = PraosError(f"praos rc={rc}: {msg.decode() if msg else ''}")
+            err.needed, err.stats = int(rw.n_rows), S
+            raise err
+        self.check(rc)
+        k = int(rw.n_rows)
+        return S, {name: a[:k] for name, a in R.items()}, R
+
+    def index_block_txs(self, arena, off, length, byron=False, rows=True, cap=None):
+        """The transaction index of the stored blocks arena[off[i]:off[i]+len[i]]
+        (praos_index_block_txs).  Returns (stats, rows): stats = dict of per-block arrays
+        (TXI_STATS_FIELDS; tx_first has n + 1 entries), rows = dict of per-transaction arrays
+        (TXI_ROW_FIELDS, or the names given in rows; False: none, stats only).  byron: Byron
+        blocks and EBBs are indexed too.  cap: capacity of the row arrays (default: sized by a
+        first call); a smaller one raises PraosError with .needed and .stats set."""
+        arena, off, length = self._chunk(arena, off, length)
+        hb = self.header_bytes_struct(arena, off, length)
+        return self._tx_index(lambda cfg, st, rw: self.L.praos_index_block_txs(
+            self.h, ctypes.byref(hb), ctypes.byref(cfg), ctypes.byref(st), ctypes.byref(rw)),
+            len(off), byron, rows, cap)[:2]
+
+    def tx_index_blocks(self, b, n, byron=False, rows=True, cap=None, out=None):
+        """index_block_txs over an upload_blocks batch (praos_block_batch_tx_index): no second
+        upload.  out: tx_index_buffers(n, cap, rows), written in place (a caller indexing batch
+        after batch into its own arrays); then (stats, rows cut to n_rows, the full row arrays)
+        is returned."""
+        r = self._tx_index(lambda cfg, st, rw: self.L.praos_block_batch_tx_index(
+            self.h, b, ctypes.byref(cfg), ctypes.byref(st), ctypes.byref(rw)), n, byron, rows, cap, out)
+        return r if out is not None else r[:2]
+
+    def tx_index_buffers(self, n, cap, rows=True):
+        """Output arrays for tx_index_blocks(..., cap=cap, out=...): (stats, rows, row arrays)."""
+        names = [f[0] for f in TXI_ROW_FIELDS] if rows is True else list(rows or ())
+        S = {name: np.zeros(n + 1 if name == "tx_first" else n, dt) for name, dt in TXI_STATS_FIELDS}
+        R = {name: np.zeros((cap,) + shp, dt) for name, dt, shp in TXI_ROW_FIELDS if name in names}
+        return S, R, R
 
     # ---- ImmutableDB chunk validation (k_crc32.hip, praos_validate_chunk) ----
     def crc32(self, arena, off, length):
