@@ -589,6 +589,86 @@ int praos_index_block_txs(praos_ctx* ctx, const praos_header_bytes* blocks, cons
 int praos_block_batch_tx_index(praos_ctx* ctx, praos_batch* b, const praos_txi_cfg* cfg, praos_txi_stats* stats,
                                praos_txi_rows* rows);
 
+/* ---- Key witnesses of stored blocks' transactions (additive: ABI version unchanged) ----
+ * Every VKey witness and every bootstrap witness of the transactions of stored blocks checked
+ * as an Ed25519 signature over the transaction's txId, on the device and from the bytes as
+ * stored.  Replaces the per-witness signature check the reference runs on the CPU when it
+ * applies a block rather than reapplies it: applyBlockLedgerResult with asoValidation =
+ * STS.ValidateAll (Shelley/Ledger/Ledger.hs:335-352) and applyShelleyTx in the mempool
+ * (Shelley/Ledger/Mempool.hs:215-239); reapplyBlockLedgerResult (Ledger.hs:354-373) skips it.
+ * Signature validity only: whether the right keys signed (witsVKeyNeeded) and every other UTXOW
+ * rule need ledger state and are not checked; key_hash is returned so that a caller holding the
+ * ledger can make that comparison.
+ * blocks: whole stored blocks as praos_index_block_txs takes them.  The call runs that index in
+ * buffers of its own and reads its rows' wit spans and tx_id; a batch's integrity results and
+ * the index's own outputs stay as they are.
+ * Scanned: the witness set of every row of a PRAOS_TXI_OK Shelley-based block (is_valid = 0 rows
+ * too: UTXOW runs before phase 2).  The witness set is a map, definite or indefinite, keys of any
+ * head width.  The value under the FIRST key 0 is the VKey witnesses, items [vkey, sig]; the
+ * value under the FIRST key 2 the bootstrap witnesses, items [vkey, sig, chain_code, attributes].
+ * Each value is an array, definite or indefinite, optionally wrapped in tag 258 (Conway's set
+ * form; accepted in every era, a leniency); each item an array of exactly 2 / 4 elements,
+ * definite or indefinite; vkey a definite byte string of 32 bytes, sig one of 64; chain_code and
+ * attributes are skipped as one item each; other keys are skipped; the walk ends when both keys
+ * have been seen or the map ends.  A witness set that is no map, or has neither key, has no
+ * witnesses.
+ *   PRAOS_TXW_SHAPE    the transaction has no witness rows: key 0 or key 2 present but of another
+ *                      form (no array, a tag other than 258), an item of the wrong arity, a key
+ *                      or signature of the wrong length or type or an indefinite byte string, or
+ *                      a map whose walk ends inside a pair
+ *   PRAOS_TXW_SKIPPED  a Byron row (cfg->byron != 0): no witness rows; Byron's SignTag framing
+ *                      is pinned by nothing in the reference tree
+ * A witness is ok iff libsodium's crypto_sign_verify_detached(sig, tx_id, 32, vkey) accepts, the
+ * same for both kinds (verifyBootstrapWit's address-root comparison is not made).
+ * Witness rows: transactions in the index's row order; inside one transaction the key-0 items in
+ * stored order, then the key-2 items in stored order, whichever key came first in the map. */
+#define PRAOS_TXW_OK      0u
+#define PRAOS_TXW_SHAPE   1u
+#define PRAOS_TXW_SKIPPED 2u
+typedef struct {
+  uint32_t byron;                 /* non-zero: Byron blocks are indexed (their rows SKIPPED) */
+  uint32_t max_lanes;             /* witnesses verified per launch, 0 = the library's default; the
+                                     outputs do not depend on it */
+} praos_txw_cfg;
+typedef struct {                  /* per block; every pointer may be NULL = not returned */
+  uint8_t* status;                /* n: PRAOS_TXI_* */
+  uint32_t* n_tx;                 /* n */
+  uint32_t* n_wit;                /* n: witnesses of the block's transactions */
+  uint32_t* n_bad;                /* n: witnesses that do not verify */
+  uint32_t* n_shape;              /* n: transactions PRAOS_TXW_SHAPE */
+  uint64_t* tx_first;             /* n + 1: exclusive prefix sum of n_tx */
+} praos_txw_blocks;
+typedef struct {                  /* per transaction row; caller buffers of cap rows, every pointer may be NULL */
+  size_t cap;
+  size_t n_rows;                  /* out: the rows of the call */
+  uint32_t* block;                /* the row's block */
+  uint8_t* status;                /* PRAOS_TXW_* */
+  uint32_t* n_vkey;
+  uint32_t* n_boot;
+  uint32_t* n_bad;                /* witnesses of the row that do not verify */
+  uint8_t* tx_id;                 /* cap * 32 */
+  uint64_t* wit_first;            /* cap + 1: exclusive prefix sum of n_vkey + n_boot (n_rows + 1 written) */
+} praos_txw_txs;
+typedef struct {                  /* per witness; caller buffers of cap witnesses, every pointer may be NULL */
+  size_t cap;
+  size_t n_wits;                  /* out: the witnesses of the call */
+  uint32_t* tx;                   /* the witness's transaction row */
+  uint8_t* kind;                  /* 0 VKey witness, 2 bootstrap witness */
+  uint64_t* key_off;              /* the 32 key bytes, into blocks->bytes */
+  uint64_t* sig_off;              /* the 64 signature bytes, into blocks->bytes */
+  uint8_t* ok;                    /* 1: the signature verifies */
+  uint8_t* key_hash;              /* cap * 28: Blake2b-224 of vkey for kind 0, zeros for kind 2 */
+} praos_txw_wits;
+/* blocks_out, txs and wits may be NULL.  When an array of txs (wits) is given and its cap is below
+ * n_rows (n_wits): PRAOS_E_ARG with n_rows and n_wits = the counts needed and blocks_out filled;
+ * with no array given cap is not looked at (the sizing call).  n = 0 is PRAOS_OK. */
+int praos_verify_tx_witnesses(praos_ctx* ctx, const praos_header_bytes* blocks, const praos_txw_cfg* cfg,
+                              praos_txw_blocks* blocks_out, praos_txw_txs* txs, praos_txw_wits* wits);
+/* The same over a praos_block_batch_upload batch, with no second upload; in either order with
+ * praos_block_batch_run and praos_block_batch_tx_index, whose results it leaves as they are. */
+int praos_block_batch_tx_witnesses(praos_ctx* ctx, praos_batch* b, const praos_txw_cfg* cfg,
+                                   praos_txw_blocks* blocks_out, praos_txw_txs* txs, praos_txw_wits* wits);
+
 /* ---- Byron header validation: PBFT (additive as the two sections above: ABI version unchanged) ----
  * validateHeader for Byron = validateEnvelope (HeaderValidation.hs:297-344 with the Byron
  * instance, Byron/Ledger/HeaderValidation.hs:39-75) + PBFT updateChainDepState

@@ -65,6 +65,8 @@ module Ouroboros.Consensus.Protocol.Praos.Batch
     -- * Transaction index of stored blocks (db-analyser's block statistics)
   , BlockTxStats (..)
   , praosIndexBlockTxs
+  , praosVerifyTxWitnesses
+  , BlockWitnessStats (..)
     -- * Byron header validation (PBFT)
   , PBftParamsC (..)
   , PBftTipC
@@ -219,6 +221,14 @@ foreign import ccall safe "praos_validate_chunk_cfg" c_validate_chunk_cfg
 -- layout-txi praos_txi_rows (112 bytes): cap@0 n_rows@8 block@16 body_off@24 body_len@32 wit_off@40 wit_len@48 aux_off@56 aux_len@64 size@72 n_out@80 ex_steps@88 is_valid@96 tx_id@104
 foreign import ccall safe "praos_index_block_txs" c_index_block_txs
   :: Ptr PraosCtx -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> IO CInt
+-- additive as well (ABI version unchanged): the key witnesses of stored blocks' transactions.  Its
+-- structs (checked against the C compiler by tests/test_txwit_abi.py, which owns the "layout-txw" lines):
+-- layout-txw praos_txw_cfg (8 bytes): byron@0 max_lanes@4
+-- layout-txw praos_txw_blocks (48 bytes): status@0 n_tx@8 n_wit@16 n_bad@24 n_shape@32 tx_first@40
+-- layout-txw praos_txw_txs (72 bytes): cap@0 n_rows@8 block@16 status@24 n_vkey@32 n_boot@40 n_bad@48 tx_id@56 wit_first@64
+-- layout-txw praos_txw_wits (64 bytes): cap@0 n_wits@8 tx@16 kind@24 key_off@32 sig_off@40 ok@48 key_hash@56
+foreign import ccall safe "praos_verify_tx_witnesses" c_verify_tx_witnesses
+  :: Ptr PraosCtx -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> IO CInt
 -- additive as well (ABI version unchanged): Byron header validation.  The structs
 -- validatePBftHeaderBatch pokes and peeks (checked against the C compiler by tests/test_pbft_abi.py;
 -- "layout-pbft": the other layout lines belong to the tests named above):
@@ -1001,6 +1011,51 @@ praosVerifyBlockIntegrity ctx spkp arena offs lens = do
         PraosBatchCtx p -> c_verify_block_integrity p (castPtr hb) spkp rp nullPtr
         PraosBatchGroup g _ _ -> c_group_verify_block_integrity g (castPtr hb) spkp rp nullPtr
   VS.unsafeFreeze res
+
+-- | Per stored block the outcome of the signature check of its transactions' key witnesses: the
+-- check 'applyBlockLedgerResult' makes once per witness under @STS.ValidateAll@
+-- (Shelley/Ledger/Ledger.hs:335-352) and 'reapplyBlockLedgerResult' skips.  Status as
+-- 'btsStatus'; a block whose @bwsBad@ and @bwsShape@ are both 0 holds no witness whose signature
+-- fails.  Which keys had to sign is the ledger's to say and is not looked at.
+data BlockWitnessStats = BlockWitnessStats
+  { bwsStatus :: !(VS.Vector Word8)
+  , bwsNumTxs :: !(VS.Vector Word32)
+  , bwsWits   :: !(VS.Vector Word32)    -- ^ VKey and bootstrap witnesses found
+  , bwsBad    :: !(VS.Vector Word32)    -- ^ ... whose signature over the txId does not verify
+  , bwsShape  :: !(VS.Vector Word32)    -- ^ transactions whose witness set is outside the shapes read
+  }
+
+-- | praos_verify_tx_witnesses over the blocks @arena[off_i .. off_i + len_i)@ (whole stored blocks,
+-- as 'praosIndexBlockTxs' takes them), the per-block counts only.  @byron@: Byron blocks are
+-- indexed (their transactions are skipped, not checked).
+praosVerifyTxWitnesses :: PraosBatchCtx -> Bool -> BS.ByteString -> VS.Vector Word64 -> VS.Vector Word32
+                       -> IO BlockWitnessStats
+praosVerifyTxWitnesses ctx byron arena offs lens = do
+  let n = VS.length offs
+  when (VS.length lens /= n) $ throwIO (PraosBatchError (-1) "praosVerifyTxWitnesses: vector lengths differ")
+  let p = ctxPtr ctx                           -- a group's first member: the check has no group form
+  st <- VSM.new n
+  ntx <- VSM.new n
+  nwit <- VSM.new n
+  nbad <- VSM.new n
+  nshape <- VSM.new n
+  BSU.unsafeUseAsCStringLen arena $ \(ap, alen) ->
+    VS.unsafeWith offs $ \offp -> VS.unsafeWith lens $ \lenp ->
+    VSM.unsafeWith st $ \stp -> VSM.unsafeWith ntx $ \ntxp -> VSM.unsafeWith nwit $ \nwitp ->
+    VSM.unsafeWith nbad $ \nbadp -> VSM.unsafeWith nshape $ \nshapep ->
+    allocaBytes 40 $ \hb -> allocaBytes 8 $ \wcfg -> allocaBytes 48 $ \blks -> allocaBytes 72 $ \txs ->
+    allocaBytes 64 $ \wits -> do
+      pokeByteOff hb 0 (fromIntegral n :: CSize) >> pokeByteOff hb 8 ap
+      pokeByteOff hb 16 (fromIntegral alen :: CSize)
+      pokeByteOff hb 24 offp >> pokeByteOff hb 32 lenp
+      pokeByteOff wcfg 0 (if byron then 1 else 0 :: Word32) >> pokeByteOff wcfg 4 (0 :: Word32)
+      fillBytes blks 0 48
+      pokeByteOff blks 0 stp >> pokeByteOff blks 8 ntxp >> pokeByteOff blks 16 nwitp
+      pokeByteOff blks 24 nbadp >> pokeByteOff blks 32 nshapep
+      fillBytes txs 0 72 >> fillBytes wits 0 64      -- no row arrays: the caps are not looked at
+      check ctx $ c_verify_tx_witnesses p (castPtr hb) (castPtr wcfg) (castPtr blks) (castPtr txs) (castPtr wits)
+  BlockWitnessStats <$> VS.unsafeFreeze st <*> VS.unsafeFreeze ntx <*> VS.unsafeFreeze nwit <*> VS.unsafeFreeze nbad
+                    <*> VS.unsafeFreeze nshape
 
 -- | Per stored block what db-analyser's ledger-free analyses read off its transactions:
 -- 'HasAnalysis.blockTxSizes' (its length and sum), 'HasAnalysis.countTxOutputs' and the execution

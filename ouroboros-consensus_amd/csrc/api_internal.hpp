@@ -1,8 +1,9 @@
 #pragma once
 // api_internal.hpp -- what the units of the host API share: the context and batch structs, the
 // tuning constants, the staging pool, the allocation / error helpers and the functions that cross
-// unit boundaries (praos_impl).  Included by praos_api / praos_run / praos_fold / praos_debug
-// only; the other host modules (replay, group, candidates, pbft) go through replay_internal.hpp.
+// unit boundaries (praos_impl).  Included by praos_api / praos_run / praos_fold / praos_debug /
+// praos_txindex / praos_txwit only; the other host modules (replay, group, candidates, pbft) go
+// through replay_internal.hpp.
 #include "praos_hip.h"
 #include "launch.hpp"
 #include "host_util.hpp"
@@ -309,6 +310,8 @@ struct praos_ctx {
   praos_batch* rp_keep[RP_SLOTS] = {};                 // replay batches kept between calls
   uint8_t* cand_scratch = nullptr;                     // praos_validate_candidates: wire arena, item
   size_t cand_scratch_sz = 0;                          // buffers and hash set, kept between calls
+  ge_cached* txw_tabs = nullptr;                       // praos_verify_tx_witnesses: the lane tables of one
+  size_t txw_lanes = 0;                                // slice, kept between calls (grown, never shrunk)
   hipEvent_t up_ev[PIPE_MAX] = {}, done_ev[PIPE_MAX] = {};
   praos_batch* pipe[PIPE_MAX] = {};
   // praos_verify_header_bytes_submit: up to PIPE_CALLS calls in flight, on pipe[0 .. PIPE_CALLS) in turn
@@ -585,8 +588,60 @@ struct rp_view {
   int32_t* d_map = nullptr;
 };
 
+// one device allocation carved into 256-byte aligned parts (praos_txindex / praos_txwit): the
+// layout function runs twice, first to measure (base == nullptr) and then over the allocation
+struct Carve {
+  uint8_t* base = nullptr;
+  size_t off = 0;
+  template <typename T>
+  T* take(size_t bytes) {
+    const size_t at = off;
+    off += (bytes + 255) & ~(size_t)255;
+    return base ? (T*)(base + at) : nullptr;
+  }
+};
+
+struct DevBuf {
+  void* p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+template <typename F>
+static hipError_t carve_alloc(DevBuf& buf, F&& layout) {
+  Carve m;
+  layout(m);
+  const hipError_t e = hipMalloc(&buf.p, m.off ? m.off : 256);
+  if (e != hipSuccess) return e;
+  Carve c;
+  c.base = (uint8_t*)buf.p;
+  layout(c);
+  return hipSuccess;
+}
+
+// The transaction index's device results kept for a pass that follows it (praos_txwit.hip): the
+// call's allocations, owned here, and what that pass reads in them.
+struct txi_keep {
+  void* buf[3] = {nullptr, nullptr, nullptr};
+  const uint8_t* kind = nullptr;      // n: k_txindex.hip's kind of each block (3: a Byron main block)
+  const uint32_t* tfirst = nullptr;   // n + 1: the final rows' prefix sum (total > 0)
+  praos_txi_dev_rows rows{};          // the final rows: block, wit_off, wit_len, tx_id
+  size_t total = 0;
+  txi_keep() = default;
+  txi_keep(const txi_keep&) = delete;
+  txi_keep& operator=(const txi_keep&) = delete;
+  ~txi_keep() {
+    for (void* p : buf)
+      if (p) (void)hipFree(p);
+  }
+};
+
 // The functions that cross the API units' boundaries.
 namespace praos_impl {
+
+// praos_txindex.hip: the index over a block batch.  keep != null: rows is ignored, the final rows
+// stay on the device (no capacity check, no row download) and the buffers pass to *keep
+int txi_run(praos_ctx* c, praos_batch* b, const praos_txi_cfg* cfg, praos_txi_stats* st, praos_txi_rows* rows,
+            txi_keep* keep);
 
 // praos_api.hip: the radix-2^16 comb, k_decode_praos over a from-bytes batch, the overlay class
 // of a slot

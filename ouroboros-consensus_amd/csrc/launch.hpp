@@ -279,6 +279,27 @@ void launch_txi_reduce(hipStream_t stream, size_t n, const uint32_t* cnt, const 
 void launch_txi_final(hipStream_t stream, size_t nrows, const uint8_t* arena, const uint8_t* status,
                       const uint32_t* first, const uint32_t* tfirst, const praos_txi_dev_rows* rows,
                       const praos_txi_dev_rows* out);
+// k_txwit.hip: the key witnesses of the index's final rows.  count: per row the PRAOS_TXW_* status,
+// the VKey / bootstrap counts, their sum and the offsets of the two values (blk_kind: the index's
+// kind per block).  emit: the witness records at wit_first[row] + j (n_wits = the arrays' length).
+// verify: witnesses [w0, w1), lane t on table region t of tabs (LT_ED entries each): ok and the
+// key hash [n_wits][28].  tx: the rows' failing witnesses.  blocks: the sums per block over rows
+// [tfirst[i], tfirst[i + 1]).
+void launch_txw_count(hipStream_t stream, size_t nrows, const uint8_t* arena, uint64_t arena_len,
+                      const uint8_t* blk_kind, const uint32_t* row_block, const uint64_t* wit_off,
+                      const uint32_t* wit_len, uint8_t* status, uint32_t* n_vkey, uint32_t* n_boot, uint32_t* cnt,
+                      uint64_t* v0, uint64_t* v2);
+void launch_txw_emit(hipStream_t stream, size_t nrows, const uint8_t* arena, const uint64_t* wit_off,
+                     const uint32_t* wit_len, const uint32_t* n_vkey, const uint32_t* n_boot, const uint64_t* v0,
+                     const uint64_t* v2, const uint32_t* wit_first, uint64_t n_wits, uint32_t* tx, uint8_t* kind,
+                     uint64_t* key_off, uint64_t* sig_off);
+void launch_txw_verify(hipStream_t stream, size_t w0, size_t w1, const ge_niels* gbtab, const uint8_t* arena,
+                       const uint32_t* tx, const uint8_t* kind, const uint64_t* key_off, const uint64_t* sig_off,
+                       const uint8_t* tx_id, uint8_t* ok, uint8_t* key_hash, ge_cached* tabs);
+void launch_txw_tx(hipStream_t stream, size_t nrows, const uint32_t* wit_first, const uint8_t* ok, uint32_t* n_bad);
+void launch_txw_blocks(hipStream_t stream, size_t n, const uint32_t* tfirst, const uint8_t* status,
+                       const uint32_t* cnt, const uint32_t* tx_bad, uint32_t* n_wit, uint32_t* n_bad,
+                       uint32_t* n_shape);
 // k_pbft.hip: Byron header validation.  decode: one lane per stored header (columns, the verify
 // inputs keys / sig / hram, the delegate's key hash dhash [n][28] and its index in dtab -- n_delegs
 // x 8 words sorted by the 7 hash words, word 7 the caller's index -- and the list of lanes that

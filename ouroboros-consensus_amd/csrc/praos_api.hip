@@ -341,6 +341,7 @@ void praos_close(praos_ctx* c) {
   (void)hipFree(c->d_gen);
   (void)hipFree(c->btab);
   (void)hipFree(c->bcomb16);
+  (void)hipFree(c->txw_tabs);
   for (auto& ps : c->pks) {
     for (void* q : {(void*)ps.pkey, (void*)ps.count, (void*)ps.base, (void*)ps.entry_rep, (void*)ps.entry_pos,
                     (void*)ps.kinfo, (void*)ps.pentry, (void*)ps.ktab, (void*)ps.scnt, (void*)ps.spos})

@@ -6,40 +6,13 @@
 // reduce passes over the provisional rows, the statistics down, the final prefix sum (blocks a
 // row found outside the shapes drop out), and -- when a row array was asked for -- the final pass
 // with the transaction ids and the rows down.  Two host round trips; the device buffers are
-// three allocations carved into their parts.
+// three allocations carved into their parts.  praos_impl::txi_run with a txi_keep is the same
+// call for a pass that follows the index on the device (praos_txwit.hip): the final rows' block,
+// witness span and tx_id columns are built, nothing of them is downloaded, and the allocations
+// pass to the caller.
 #include "api_internal.hpp"
 
 namespace {
-
-// one device allocation carved into 256-byte aligned parts: the layout function runs twice, first
-// to measure (base == nullptr) and then over the allocation
-struct Carve {
-  uint8_t* base = nullptr;
-  size_t off = 0;
-  template <typename T>
-  T* take(size_t bytes) {
-    const size_t at = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return base ? (T*)(base + at) : nullptr;
-  }
-};
-
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
-template <typename F>
-hipError_t carve_alloc(DevBuf& buf, F&& layout) {
-  Carve m;
-  layout(m);
-  const hipError_t e = hipMalloc(&buf.p, m.off ? m.off : 256);
-  if (e != hipSuccess) return e;
-  Carve c;
-  c.base = (uint8_t*)buf.p;
-  layout(c);
-  return hipSuccess;
-}
 
 void rows_layout(Carve& c, size_t rows, praos_txi_dev_rows& r, const praos_txi_rows* want) {
   auto on = [&](const void* p) { return !want || p; };
@@ -63,8 +36,12 @@ bool any_row_array(const praos_txi_rows* r) {
                r->size || r->n_out || r->ex_steps || r->is_valid || r->tx_id);
 }
 
-int txi_run(praos_ctx* c, praos_batch* b, const praos_txi_cfg* cfg, praos_txi_stats* st, praos_txi_rows* rows) {
+}  // namespace
+
+int praos_impl::txi_run(praos_ctx* c, praos_batch* b, const praos_txi_cfg* cfg, praos_txi_stats* st,
+                        praos_txi_rows* rows, txi_keep* keep) {
   const size_t n = b->n;
+  if (keep) rows = nullptr;
   const int byron = cfg->byron != 0;
   if (rows) rows->n_rows = 0;
   if (n == 0) {
@@ -186,21 +163,47 @@ int txi_run(praos_ctx* c, praos_batch* b, const praos_txi_cfg* cfg, praos_txi_st
   h_tfirst[n] = (uint32_t)total;
   if (st && st->tx_first) st->tx_first[n] = total;
   if (rows) rows->n_rows = (size_t)total;
-  if (!any_row_array(rows) || total == 0) return PRAOS_OK;
-  if (rows->cap < total) {
+  // the buffers of a call whose results stay on the device pass to the caller
+  auto hand_over = [&](DevBuf& a, DevBuf& b2, DevBuf& c2, const praos_txi_dev_rows& fr) {
+    keep->buf[0] = a.p;
+    keep->buf[1] = b2.p;
+    keep->buf[2] = c2.p;
+    a.p = b2.p = c2.p = nullptr;
+    keep->kind = kind;
+    keep->tfirst = tfirst;
+    keep->rows = fr;
+    keep->total = (size_t)total;
+  };
+  if (keep && total == 0) {
+    DevBuf none;
+    hand_over(buf_a, buf_b, none, praos_txi_dev_rows{});
+    return PRAOS_OK;
+  }
+  if (!keep && (!any_row_array(rows) || total == 0)) return PRAOS_OK;
+  if (!keep && rows->cap < total) {
     c->err = "praos_index_block_txs: rows->cap too small";
     return PRAOS_E_ARG;
   }
   // ---- the final rows, the transaction ids, the downloads
   praos_txi_dev_rows fr{};
   DevBuf buf_c;
-  if (carve_alloc(buf_c, [&](Carve& m) { rows_layout(m, (size_t)total, fr, rows); }) != hipSuccess) {
+  praos_txi_rows kept{};   // what the pass after the index reads: any non-null pointer selects the array
+  kept.block = (uint32_t*)&kept;
+  kept.wit_off = (uint64_t*)&kept;
+  kept.wit_len = (uint32_t*)&kept;
+  kept.tx_id = (uint8_t*)&kept;
+  if (carve_alloc(buf_c, [&](Carve& m) { rows_layout(m, (size_t)total, fr, keep ? &kept : rows); }) != hipSuccess) {
     c->err = "device allocation failed";
     return PRAOS_E_OOM;
   }
   HIPCHK(c, hipMemcpyAsync(tfirst, h_tfirst.data(), 4 * (n + 1), hipMemcpyHostToDevice, s));
   launch_txi_final(s, (size_t)prov, b->arena, status, first, tfirst, &pr, &fr);
   HIPCHK(c, hipGetLastError());
+  if (keep) {
+    HIPCHK(c, hipStreamSynchronize(s));   // h_tfirst has been read
+    hand_over(buf_a, buf_b, buf_c, fr);
+    return PRAOS_OK;
+  }
   const size_t t = (size_t)total;
   auto down = [&](void* dst, const void* src, size_t bytes) {
     return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
@@ -221,15 +224,13 @@ int txi_run(praos_ctx* c, praos_batch* b, const praos_txi_cfg* cfg, praos_txi_st
   return PRAOS_OK;
 }
 
-}  // namespace
-
 extern "C" {
 
 int praos_block_batch_tx_index(praos_ctx* c, praos_batch* b, const praos_txi_cfg* cfg, praos_txi_stats* stats,
                                praos_txi_rows* rows) {
   if (!c || !b || !b->is_block || !cfg) return PRAOS_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  const int r = txi_run(c, b, cfg, stats, rows);
+  const int r = praos_impl::txi_run(c, b, cfg, stats, rows, nullptr);
   (void)hipStreamSynchronize(c->stream);   // the call's buffers are freed on return
   return r;
 }

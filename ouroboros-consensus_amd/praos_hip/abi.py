@@ -225,6 +225,37 @@ class TxiRows(ctypes.Structure):
                                                                           for name, dt, _ in TXI_ROW_FIELDS]
 
 
+# Key witnesses of stored blocks' transactions (praos_verify_tx_witnesses / praos_block_batch_tx_witnesses)
+TXW_OK, TXW_SHAPE, TXW_SKIPPED = 0, 1, 2
+TXW_BLOCK_FIELDS = (  # name, dtype (praos_txw_blocks; tx_first has n + 1 entries)
+    ("status", np.uint8), ("n_tx", np.uint32), ("n_wit", np.uint32), ("n_bad", np.uint32), ("n_shape", np.uint32),
+    ("tx_first", np.uint64))
+TXW_TX_FIELDS = (  # name, dtype, record shape (praos_txw_txs; wit_first has cap + 1 entries)
+    ("block", np.uint32, ()), ("status", np.uint8, ()), ("n_vkey", np.uint32, ()), ("n_boot", np.uint32, ()),
+    ("n_bad", np.uint32, ()), ("tx_id", np.uint8, (32,)), ("wit_first", np.uint64, ()))
+TXW_WIT_FIELDS = (  # name, dtype, record shape (praos_txw_wits)
+    ("tx", np.uint32, ()), ("kind", np.uint8, ()), ("key_off", np.uint64, ()), ("sig_off", np.uint64, ()),
+    ("ok", np.uint8, ()), ("key_hash", np.uint8, (28,)))
+
+
+class TxwCfg(ctypes.Structure):
+    _fields_ = [("byron", ctypes.c_uint32), ("max_lanes", ctypes.c_uint32)]
+
+
+class TxwBlocks(ctypes.Structure):
+    _fields_ = [(name, _CT[dt]) for name, dt in TXW_BLOCK_FIELDS]
+
+
+class TxwTxs(ctypes.Structure):
+    _fields_ = [("cap", ctypes.c_size_t), ("n_rows", ctypes.c_size_t)] + [(name, _CT[dt])
+                                                                          for name, dt, _ in TXW_TX_FIELDS]
+
+
+class TxwWits(ctypes.Structure):
+    _fields_ = [("cap", ctypes.c_size_t), ("n_wits", ctypes.c_size_t)] + [(name, _CT[dt])
+                                                                          for name, dt, _ in TXW_WIT_FIELDS]
+
+
 # Byron blocks: further PRAOS_BLK_* bits and the failing body comparisons (PRAOS_BYRON_W_*)
 BLK_PBFT_SIG, BLK_PM = 0x08, 0x10
 BYRON_W_DLG, BYRON_W_UPD, BYRON_W_NTX, BYRON_W_WIT, BYRON_W_ROOT = 0x01, 0x02, 0x04, 0x08, 0x10
@@ -435,6 +466,12 @@ SIGNATURES = {
                                              ctypes.POINTER(TxiStats), ctypes.POINTER(TxiRows)]),
     "praos_block_batch_tx_index": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(TxiCfg),
                                                   ctypes.POINTER(TxiStats), ctypes.POINTER(TxiRows)]),
+    "praos_verify_tx_witnesses": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HeaderBytes), ctypes.POINTER(TxwCfg),
+                                                 ctypes.POINTER(TxwBlocks), ctypes.POINTER(TxwTxs),
+                                                 ctypes.POINTER(TxwWits)]),
+    "praos_block_batch_tx_witnesses": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(TxwCfg),
+                                                      ctypes.POINTER(TxwBlocks), ctypes.POINTER(TxwTxs),
+                                                      ctypes.POINTER(TxwWits)]),
     "praos_block_batch_upload": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.POINTER(HeaderBytes)]),
     "praos_block_batch_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
     "praos_block_batch_download": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u8p, u8p]),
@@ -880,6 +917,71 @@ class Context:
         S = {name: np.zeros(n + 1 if name == "tx_first" else n, dt) for name, dt in TXI_STATS_FIELDS}
         R = {name: np.zeros((cap,) + shp, dt) for name, dt, shp in TXI_ROW_FIELDS if name in names}
         return S, R, R
+
+    # ---- stored blocks: the transactions' key witnesses (k_txwit.hip) ----
+    def tx_witness_buffers(self, n, tx_cap, wit_cap, rows=True):
+        """Output arrays for verify_tx_witnesses / tx_witnesses_blocks(..., out=...): (blocks, txs,
+        wits) dicts of n blocks, tx_cap rows (wit_first: tx_cap + 1) and wit_cap witnesses; rows =
+        False: the per-block arrays only."""
+        B = {name: np.zeros(n + 1 if name == "tx_first" else n, dt) for name, dt in TXW_BLOCK_FIELDS}
+        if not rows:
+            return B, {}, {}
+        T = {name: np.zeros((tx_cap + 1 if name == "wit_first" else tx_cap,) + shp, dt)
+             for name, dt, shp in TXW_TX_FIELDS}
+        W = {name: np.zeros((wit_cap,) + shp, dt) for name, dt, shp in TXW_WIT_FIELDS}
+        return B, T, W
+
+    def _tx_witnesses(self, call, n, byron, max_lanes, rows, cap, out):
+        """call(cfg, blocks, txs, wits) -> rc.  rows: every row and witness array (True) or the
+        per-block arrays only; cap: (rows, witnesses) capacities (None: sized by a first call
+        without row arrays); out: tx_witness_buffers of the same n, written again in place."""
+        cfg = TxwCfg(1 if byron else 0, max_lanes)
+        if out is None and rows and cap is None:
+            ts, ws = TxwTxs(), TxwWits()
+            self.check(call(cfg, None, ts, ws))
+            cap = (int(ts.n_rows), int(ws.n_wits))
+        B, T, W = out if out is not None else self.tx_witness_buffers(n, *(cap or (0, 0)), rows=rows)
+        bs, ts, ws = TxwBlocks(), TxwTxs(), TxwWits()
+        for name, dt in TXW_BLOCK_FIELDS:
+            setattr(bs, name, ptr(B[name], _CT[dt]))
+        if T:
+            ts.cap = len(T["block"])
+            for name, dt, _ in TXW_TX_FIELDS:
+                setattr(ts, name, ptr(T[name], _CT[dt]))
+        if W:
+            ws.cap = len(W["tx"])
+            for name, dt, _ in TXW_WIT_FIELDS:
+                setattr(ws, name, ptr(W[name], _CT[dt]))
+        rc = call(cfg, bs, ts, ws)
+        if rc == E_ARG and (T or W) and (ts.n_rows > ts.cap or ws.n_wits > ws.cap):
+            msg = self.L.praos_last_error(self.h)
+            err = PraosError(f"praos rc={rc}: {msg.decode() if msg else ''}")
+            err.needed, err.blocks = (int(ts.n_rows), int(ws.n_wits)), B
+            raise err
+        self.check(rc)
+        nt, nw = int(ts.n_rows), int(ws.n_wits)
+        return (B, {k: a[:nt + 1 if k == "wit_first" else nt] for k, a in T.items()},
+                {k: a[:nw] for k, a in W.items()}, (nt, nw))
+
+    def verify_tx_witnesses(self, arena, off, length, byron=False, max_lanes=0, rows=True, cap=None, out=None):
+        """Every VKey and bootstrap witness of the stored blocks arena[off[i]:off[i]+len[i]]
+        checked over its transaction's txId (praos_verify_tx_witnesses).  Returns (blocks, txs,
+        wits, (n_rows, n_wits)): dicts of per-block (TXW_BLOCK_FIELDS), per-transaction
+        (TXW_TX_FIELDS) and per-witness (TXW_WIT_FIELDS) arrays; rows=False: the per-block arrays
+        only.  cap: (row, witness) capacities (default: sized by a first call); smaller ones raise
+        PraosError with .needed and .blocks set.  max_lanes: witnesses per launch (0: default)."""
+        arena, off, length = self._chunk(arena, off, length)
+        hb = self.header_bytes_struct(arena, off, length)
+        return self._tx_witnesses(lambda cfg, bs, ts, ws: self.L.praos_verify_tx_witnesses(
+            self.h, ctypes.byref(hb), ctypes.byref(cfg), ctypes.byref(bs) if bs is not None else None,
+            ctypes.byref(ts), ctypes.byref(ws)), len(off), byron, max_lanes, rows, cap, out)
+
+    def tx_witnesses_blocks(self, b, n, byron=False, max_lanes=0, rows=True, cap=None, out=None):
+        """verify_tx_witnesses over an upload_blocks batch (praos_block_batch_tx_witnesses): no
+        second upload."""
+        return self._tx_witnesses(lambda cfg, bs, ts, ws: self.L.praos_block_batch_tx_witnesses(
+            self.h, b, ctypes.byref(cfg), ctypes.byref(bs) if bs is not None else None, ctypes.byref(ts),
+            ctypes.byref(ws)), n, byron, max_lanes, rows, cap, out)
 
     # ---- ImmutableDB chunk validation (k_crc32.hip, praos_validate_chunk) ----
     def crc32(self, arena, off, length):
