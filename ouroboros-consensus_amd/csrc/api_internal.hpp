@@ -1,6 +1,6 @@
 #pragma once
 // api_internal.hpp -- what the units of the host API share: the context and batch structs, the
-// tuning constants, the staging pool, the allocation / error helpers and the functions that cross
+// staging pool, the allocation / error helpers and the functions that cross
 // unit boundaries (praos_impl).  Included by praos_api / praos_run / praos_fold / praos_debug /
 // praos_txindex / praos_txwit only; the other host modules (replay, group, candidates, pbft) go
 // through replay_internal.hpp.
@@ -9,6 +9,7 @@
 #include "host_util.hpp"
 #include "replay_internal.hpp"
 #include "chunk_scan.hpp"
+#include "sched.hpp"
 
 static constexpr size_t NT = 256;                  // threads per block of the crypto kernels
 static constexpr size_t NIELS_BYTES = 3 * 32;      // sizeof(ge_niels)
@@ -112,49 +113,6 @@ static constexpr size_t STAGE_PIECE = 16u << 20;    // pinned staging buffers: 2
 static constexpr int PIPE_MAX = 8;                  // chunks of the stored-bytes pipeline
 static constexpr int PIPE_CALLS = 3;                // submitted stored-bytes calls in flight (pipe[0 .. 3))
 static constexpr size_t PIPE_MIN_CHUNK = 49152;     // headers per chunk at least (auto mode)
-// Batches below this many headers (a strong-scaling shard of an epoch over 8 GPUs is 54k) leave
-// most wave slots empty and run latency-bound (PRAOS_VRF_PRIO = -1 raises stage V there)
-static constexpr size_t SMALL_BATCH = 80000;
-static constexpr size_t WIDE_BATCH = 300000;           // the VRF key cache's wide tier: batches from this size on
-static constexpr uint32_t WIDE_MIN_USES = 43;          // ... and keys with this many uses: the break-even of
-                                                       // W_KEY_VRF_WIDE against W_VRF_F_CK_WIDE (tools/workmodel.py)
-// below this many headers the key precomputes run at raised wave priority (PRAOS_KEY_PRIO -1):
-// they head the cached chains (profiles/r04/bb: 96k 3.66 -> 3.57 ms, 108k 4.14 -> 3.83, 160k
-// 5.19 -> 4.88, 300k 8.83 -> 8.67; 432k within noise)
-static constexpr size_t KEY_PRIO_BATCH = 400000;
-// below this many headers stage V, the uncached verifies and the key precompute come from their
-// ILP-4 builds (k_vrf_v4 / k_miss4 / k_keys4): a step's chains are latency-bound there
-// (profiles/r04/y: 96k 4.06 -> 3.64 ms, 108k 4.25 -> 4.10, 112k 4.39 -> 4.15; equal at 120k,
-// slower at 128k)
-static constexpr size_t ILP4_BATCH = 120000;
-// from this many headers on the KES Merkle walk runs once per leaf-key entry (PRAOS_KES_DEDUP -1).
-// Medians of alternating runs, ms per step without / with it, beside the other cuts of DESIGN
-// section 24: 432k 9.907 -> 9.847 (eight runs each, every run with it below every run without);
-// 300k 7.170 -> 7.231 and 160k 4.058 -> 4.117 (four each): slower, the step there is not bound
-// by the instruction count; the KES-only configs[3] 9.355 -> 9.413, inside its spread
-// (profiles/r08_perkey_ab.json)
-static constexpr size_t KES_DEDUP_BATCH = 400000;
-// Byron header batches (praos_verify_pbft_headers) below this many headers verify uncached: the
-// delegate keys' precompute chain (250 doublings, then the table pass) is pure latency there.
-// Measured on an MI355X (tools/pbft_bench.py: 7 delegates in turn, a freshly opened context per
-// variant and pass, medians of 9 runs, cached / uncached ms end to end): 16,384 2.07 / 1.83,
-// 32,768 2.38 / 2.16, 65,536 3.16 / 2.73, 98,304 4.17 / 3.95, 131,072 4.98 / 4.67, 163,840 6.03 /
-// 6.04, 216,000 7.51 / 7.94: the medians cross at about 163,840.  With 7 keys the cache's insert
-// and partition passes serialise on 7 hash slots (0.66 + 0.62 ms at 216,000, kernel trace), which
-// is what moves the crossing this far out.
-static constexpr size_t PBFT_CK_MIN = 163840;
-// below this many headers the KES leaf keys are not cached (every KES check uncached, from the
-// ILP-4 build, beside stage V): a 54k-header shard's stage V and uncached KES waves fit in one
-// round of wave slots (2 per SIMD), and the leaf-key chain -- lists, precompute, tables, k_kes_ck,
-// the step's longest after stage V + join -- is gone (54k 2.44-2.49 -> 2.29-2.37 ms; at 64k the
-// waves no longer fit and it is slower, 2.53 -> 3.05; 80k 2.97 -> 3.47; 108k 3.41 -> 4.59;
-// profiles/r06/i_kes_nocache).  PRAOS_OPT_KES_NOCACHE / PRAOS_KES_NOCACHE=<headers> override it
-// (0: always cached).
-static constexpr size_t KES_NOCACHE_BATCH = 58000;
-// below this many headers (the 1/8-epoch shard of a 432k epoch is 54k) stage V's join runs on the
-// main stream after it waits for U itself (PRAOS_V_MAIN 2) and the uncached verifies keep normal
-// wave priority
-static constexpr size_t SHARD_SMALL = 60000;
 static constexpr int PIPE_AUTO = 8;                 // chunks in auto mode (round 3, equal chunks: 4 -> 21.9M,
                                                     // 6 -> 23.0M, 8 -> 22.1M headers/s, profiles/r03/e2e_chunks.txt;
                                                     // round 5 with the first chunk at 1/4 of the others: 6 ->
@@ -201,105 +159,7 @@ struct praos_ctx {
   hipEvent_t v0_ev = nullptr, v1_ev = nullptr;         // timing of k_vrf_v on its stream (kernel_ms[6])
   hipEvent_t kc0_ev = nullptr, kc1_ev = nullptr;       // timing of k_kes_ck on its stream (kernel_ms[7])
   hipEvent_t u_ev = nullptr;                           // stage U of the uncached VRF keys done
-  int tp_staged = 1;                                  // TPraos VRF through the staged kernels + VRF key cache
-                                                       // (PRAOS_TP_STAGED=0: the one-kernel k_vrf_tp)
-  int vrf_prio = 0;                                   // stage V and join waves at s_setprio 3 (PRAOS_VRF_PRIO 1 / 0;
-                                                       // -1: batches below SMALL_BATCH headers).  Off: with the
-                                                       // uncached verifies raised instead a 54k-header step takes
-                                                       // 2.83 ms against 3.16 (profiles/r04/i, r04/j)
-  int vrf_ilp4 = (int)ILP4_BATCH;                    // stage V from the ILP-4 build (k_vrf_v4.hip): PRAOS_VRF_ILP4
-                                                       // 1 always, 0 never, N > 1: batches below N headers
-                                                       // (profiles/r04/b: V alone 1.71 -> 1.51 ms at 54k; alone
-                                                       // at 108k the step was slower, 4.25 -> 4.37, but with the
-                                                       // ILP-4 uncached verifies and precompute beside it faster,
-                                                       // profiles/r04/y)
-  int v_excl = 0;                                      // the ILP-4 stage V holding its SIMDs alone (k_vrf_v4x):
-                                                       // PRAOS_V_EXCL (54k: 3.30 -> 3.46 ms, off)
-  int miss4 = -1;                                      // uncached OCert / KES verifies from the ILP-4 build
-                                                       // (k_miss4.hip): PRAOS_MISS4 1 / 0, -1 below ILP4_BATCH
-                                                       // (54k: 3.33 -> 3.09 ms; 108k: 4.26 -> 4.66, so not there)
-  int miss_prio = -1;                                  // ... at s_setprio 3: PRAOS_MISS_PRIO 1 / 0, -1 with miss4
-                                                       // from SHARD_SMALL headers on (below it, beside the GCD
-                                                       // inversion's shorter join, normal priority with
-                                                       // v_main 1 was faster: profiles/r06/s_retune)
-  int miss_prio_for(size_t n) const { return miss_prio >= 0 ? miss_prio : (n < SHARD_SMALL ? 0 : 1); }
-  long kes_pair = -1;                                  // k_kes_ck two headers per lane from this many hits on
-                                                       // (PRAOS_KES_PAIR, 0 = never; -1: from 196,608 when the
-                                                       // KES pass runs alone -- beside the OCert / VRF passes
-                                                       // the paired kernel has 4 % fewer VALU instructions
-                                                       // (0.983 G -> 0.941 G per 432k step) and the step is
-                                                       // longer, 9.847 -> 10.113 ms, medians of eight
-                                                       // alternating runs, profiles/r08_perkey_ab.json; its
-                                                       // waves are twice as long and spill 176 bytes per lane)
-  uint32_t kes_pair_min() const {
-    return kes_pair >= 0 ? (uint32_t)kes_pair : ((kernels & 5) ? 0u : 196608u);
-  }
-  int kes_dedup = -1;                                  // KES Merkle path dedup per leaf-key entry (PRAOS_KES_DEDUP
-                                                       // 1 / 0): the representatives walk once, a wave of
-                                                       // k_kes_ck whose paths all equal theirs skips the walk;
-                                                       // -1: from KES_DEDUP_BATCH headers on
-  bool use_kes_dedup(size_t n) const { return kes_dedup > 0 || (kes_dedup < 0 && n >= KES_DEDUP_BATCH); }
-  int vrf_perkey = 1;                                  // pool record per VRF key-cache entry (k_vrf_keyrec): a
-                                                       // wave of the cached stage F / the join whose cold keys
-                                                       // all equal their records' skips the two Blake2b and the
-                                                       // pool search (PRAOS_VRF_PERKEY 1 / 0)
   hipEvent_t vrec_ev = nullptr;                        // the VRF key records are written (k_vrf_keyrec)
-  int v_main = -1;                                     // stage V on the main stream (PRAOS_V_MAIN; 0 off): no
-                                                       // cross-stream wait between the previous run's end and V;
-                                                       // the join after U and V on the VRF stream (3), or on the
-                                                       // main stream after a wait for U (1; 2: U's two streams
-                                                       // waited for separately).  54k headers (C5 1/8 shard):
-                                                       // 2.354-2.380 ms off, 2.284-2.330 (1), 2.315-2.332 (2),
-                                                       // 2.267-2.297 (3); 108k: 3.418-3.443 off, 3.36-3.42 on
-                                                       // (profiles/r06/k_vmain); -1: 2 below ILP4_BATCH
-                                                       // headers, 3 from it (with the GCD inversion, mode 1 +
-                                                       // normal-priority misses below SHARD_SMALL: 54k
-                                                       // 2.18-2.22 -> 2.17-2.19 ms, 40k 2.19-2.21 -> 2.08; then
-                                                       // mode 2 over mode 1 at 54k 2.16-2.19 -> 2.15, 40k equal
-                                                       // or 2 % faster; over mode 3 at 80k 2.78-2.80 -> 2.76,
-                                                       // 108k 3.24-3.26 -> 3.21-3.22, 216k 5.63-5.70 -> 5.70-5.71;
-                                                       // profiles/r06/s_retune)
-  int vmain_mode(size_t n) const { return v_main >= 0 ? v_main : (n < ILP4_BATCH ? 2 : 3); }
-  int pre_join = -1;                                   // the join's pool part (lookup, key hash, leader / nonce
-                                                       // values) as k_vrf_pool on the VRF miss stream before the
-                                                       // uncached U, off the chain after stage V (PRAOS_PRE_JOIN
-                                                       // 1 / 0, -1 below SMALL_BATCH)
-  int vrf_keys_first = 0;                              // PRAOS_VRF_KEYS_FIRST (see batch_run_impl; 54k: 2.80 ->
-                                                       // 2.85 ms, 108k 4.24 -> 4.27: off, profiles/r04/k)
-  int key4 = -1;                                       // key precompute from the ILP-4 build (k_keys4.hip):
-                                                       // PRAOS_KEY4 1 / 0, -1 below ILP4_BATCH (54k: 2.78-2.84
-                                                       // -> 2.76-2.77 ms; 108k 4.17 -> 4.21, profiles/r04/n)
-  bool use_key4(size_t n) const { return key4 > 0 || (key4 < 0 && n < ILP4_BATCH); }
-  // (round 5 also measured a key precompute with four lanes per key, DPP quad broadcasts: inside a
-  // step its chains were about as long as the ILP-4 build's and its four lanes per key took issue
-  // slots from the rest, 54k 2.72-2.75 -> 2.84-2.88 ms, 108k 3.79-3.84 -> 4.00,
-  // profiles/r05/c11_keyq_nobranch; removed in round 6)
-  int key_mode(size_t n) const { return use_key4(n) ? 1 : 0; }
-  int u4 = -1;                                         // cached stage U from the ILP-4 build (PRAOS_U4 1 / 0,
-                                                       // -1 below ILP4_BATCH; 54k 2.79 -> 2.75 ms, 108k 3.87-3.92
-                                                       // -> 3.81-3.83, profiles/r04/hh)
-  int ck4 = 0;                                         // cached OCert / KES verifies from the ILP-4 build
-                                                       // (PRAOS_CK4 1 / 0, -1 below ILP4_BATCH)
-  bool use_ck4(size_t n) const { return ck4 > 0 || (ck4 < 0 && n < ILP4_BATCH); }
-  bool use_u4(size_t n) const { return u4 > 0 || (u4 < 0 && n < ILP4_BATCH); }
-  bool use_miss4(size_t n) const { return miss4 > 0 || (miss4 < 0 && n < ILP4_BATCH); }
-  int v_ilp4(size_t n) const {
-    const bool on = vrf_ilp4 == 1 || (vrf_ilp4 > 1 && n < (size_t)vrf_ilp4);
-    return on ? (v_excl ? 2 : 1) : 0;
-  }
-  int vrf3 = -1;                                       // VRF as V | U | join (1), V | U + join (0), -1 auto:
-                                                       // the three-kernel form below 300k headers (latency)
-  // wide tier of the VRF key cache (praos_set_vrf_wide / PRAOS_VRF_WIDE): a key with this many uses
-  // in the batch gets positional tables (k_keys.hip); 0 off; -1 auto: WIDE_MIN_USES, the modelled
-  // break-even, in batches from WIDE_BATCH headers on (below it the longer key precompute is on the
-  // step's critical path and few keys reach the threshold)
-  int vrf_wide = -1;
-  int wide_prio = 1;                                   // the VRF key precompute at raised wave priority when it
-                                                       // builds wide tables (PRAOS_WIDE_PRIO 1 / 0)
-  int vrf_wide_cap = 4096;                             // wide keys per batch at most (PRAOS_VRF_WIDE_CAP)
-  uint32_t wide_min(size_t n) const {
-    return vrf_wide > 0 ? (uint32_t)vrf_wide : (vrf_wide < 0 && n >= WIDE_BATCH ? WIDE_MIN_USES : 0u);
-  }
   // chunked stored-bytes pipeline (praos_verify_header_bytes): a copy stream, per-chunk
   // events and persistent chunk batches (reused while they are large enough)
   int pipeline = 0;                                    // PRAOS_OPT_PIPELINE (0 = auto)
@@ -325,27 +185,15 @@ struct praos_ctx {
     size_t cap = 0;
   } pcall[PIPE_CALLS];
   int pcall_next = 0;                                  // the slot the next submit takes: the oldest call's
-  int stream_chunk_v = 1;                              // submitted calls: stage V per landed chunk (1) or in the
-                                                       // run over the whole batch (0); PRAOS_STREAM_CHUNK_V.  C5,
-                                                       // 432k headers, three calls in flight: 13.2-13.4 ms per
-                                                       // call (1) against 15.3-17.6 (0), profiles/r06/l_stream
   size_t pipe_n[PIPE_MAX] = {}, pipe_bytes[PIPE_MAX] = {};
   int concurrent = 1;                                  // PRAOS_OPT_CONCURRENT
   int kernels = 7;                                     // PRAOS_OPT_KERNELS
   int keycache = 2;                                    // PRAOS_OPT_KEYCACHE (min uses; 0 = off)
-  size_t pbft_ck_min = PBFT_CK_MIN;                    // PRAOS_PBFT_CK_MIN (see PBFT_CK_MIN)
   uint32_t pbft_stats[4] = {0, 0, 0, 0};               // praos_pbft_stats of the last praos_verify_pbft_headers
   uint32_t pbft_raw[5] = {0, 0, 0, 0, 0};              // its download: the cache's counters, the verify count
-  size_t kes_nocache = KES_NOCACHE_BATCH;              // PRAOS_KES_NOCACHE (see KES_NOCACHE_BATCH)
-  int kc_min[3] = {0, 0, 0};                           // per cache (cold, VRF, KES leaf) min uses overriding
-                                                       // keycache when > 0 (PRAOS_KC_MIN="c,v,k")
   int dedup = 1;                                       // PRAOS_OPT_DEDUP
-  // (round 5 measured the cached chains' last kernels -- cached U, the join, the cached OCert /
-  // KES verifies -- at s_setprio 2 / 3 below ILP4_BATCH: U shortened (54k 0.71 -> 0.43 ms) but
-  // stage V stretched past it and the step with it, 54k 2.74-2.76 -> 2.89-2.95 ms,
-  // profiles/r05/c14_ckprio; the option was removed in round 6)
-  int key_wave_prio = -1;                              // key precompute waves at s_setprio 3 (PRAOS_KEY_PRIO 1 / 0;
-                                                       // -1: batches below KEY_PRIO_BATCH headers)
+  SchedKnobs knobs;                                    // the schedule's knobs (sched.hpp; read from the
+                                                       // environment when the context opens)
   hipEvent_t ev[6] = {};
   hipEvent_t side_ev[4] = {};
   hipEvent_t miss_ev[4] = {};                          // miss lists ready (OCert, KES, VRF), OCert misses done
@@ -368,32 +216,7 @@ struct praos_ctx {
   } pks[2];                                            // [0] cold keys, [1] VRF keys
   int pool_keys = -1;                                  // 1 on, 0 off, -1 on inside praos_replay_immutable*
   bool replaying = false;
-  bool pk_on = false;                                  // this run uses the store
   bool pk_reset[2] = {false, false};                   // empty store t before the next run that uses it
-  // (round 6 measured key hints for the stored-bytes pipeline -- each header's cold, VRF and KES
-  // leaf keys read on the host while the chunks upload, the key stores filled from them on the
-  // side streams before the last chunk lands -- bit-exact and slower, 432k e2e 15.7 -> 18.4 ms:
-  // the fill shares the GPU with the chunks' stage V and the tail stays throughput-bound;
-  // profiles/r06/h_e2e_hints.  Removed.)
-  // (round 5 measured a per-chunk key prefill in the stored-bytes pipeline -- the landed chunks'
-  // cold, KES leaf and VRF keys stored and their tables built while later chunks upload -- in two
-  // forms, both slower: the GPU is busy with the chunks' stage V during the upload, so the
-  // prefill only moves work there, and a key first seen in the last chunk still needs a
-  // latency-bound chain after it lands (432k, 8 chunks: 16.3-16.4 -> 18.2-18.5 ms,
-  // profiles/r05/c12_prefill_v3; 16.9 -> 19.2 ms, c7_e2e_timeline_pf{0,1}.txt).  Removed in round 6.)
-  // stored-bytes pipeline: the first chunk's size in percent of the others' (PRAOS_PIPE_HEAD):
-  // nothing runs on the GPU until it has landed and been decoded
-  int pipe_head = 25;                                  // (432k headers, 8 chunks: 100 -> 16.9-17.0 ms,
-                                                       // 50 -> 16.5, 25 -> 16.3-16.4, 12 -> 16.2-16.4)
-  // (round 6 measured the KES checks queued while later chunks upload, in two forms, both slower:
-  // uncached per landed chunk, 432k e2e 15.5-16.0 -> 18.2-18.9 ms; with the leaf-key cache over 1,
-  // 2 or 4 groups of landed chunks, 15.8 / 17.0 / 18.2-18.7 ms: the GPU runs the chunks' stage V
-  // during the upload, so the KES work there only stretches V; profiles/r06/g_e2e_kes.  Removed.)
-  int pipe_tail = 100;                                 // ... and the last chunk's (PRAOS_PIPE_TAIL): the run after it
-                                                       // waits for its decode, but a smaller one leaves more of the
-                                                       // batch's stage V after the upload (432k, 8 chunks: 100 ->
-                                                       // 16.4-16.7 ms, 50 -> 17.1-17.3, 25 -> 18.5-18.8;
-                                                       // profiles/r05/c16_pipe_tail)
   // epoch
   bool have_epoch = false;
   std::vector<praos_pool> epoch_pools;                 // praos_set_epoch's inputs as installed (a call
@@ -651,9 +474,11 @@ int32_t overlay_class(const praos_ctx* c, uint64_t slot);
 
 // praos_run.hip: the key-cache prepass (hash set, entries, hit / miss lists), the entries' key
 // tables, and the crypto step's stream scheduler
-int kc_lists(praos_ctx* c, praos_batch* b, praos_batch::KeyCache& k, size_t n, const uint8_t* keys, hipStream_t st,
-             const uint32_t* list, const uint32_t* count, int which);
-void kc_precompute(praos_ctx* c, praos_batch::KeyCache& k, const uint8_t* keys, int kind, hipStream_t st, size_t n);
+int kc_lists(praos_ctx* c, praos_batch* b, const RunPlan& P, praos_batch::KeyCache& k, size_t n, const uint8_t* keys,
+             hipStream_t st, const uint32_t* list, const uint32_t* count, int which);
+void kc_precompute(praos_ctx* c, const RunPlan& P, praos_batch::KeyCache& k, const uint8_t* keys, int kind,
+                   hipStream_t st, size_t n);
+RunShape run_shape(const praos_ctx* c, size_t n, bool tp_only, bool v_done);   // the context's options + the batch
 int batch_run_impl(praos_ctx* c, praos_batch* b);
 
 }  // namespace praos_impl

@@ -153,7 +153,6 @@ const char* praos_last_error(praos_ctx* ctx) { return ctx ? ctx->err.c_str() : "
 
 // streams and events of a context (praos_open, and the pipeline's second engine)
 static bool open_streams(praos_ctx* c) {
-  if (const char* kp = std::getenv("PRAOS_KEY_PRIO")) c->key_wave_prio = std::atoi(kp);
   if (hipSetDevice(c->device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
     c->stream = nullptr;
     return false;
@@ -166,33 +165,9 @@ static bool open_streams(praos_ctx* c) {
   (void)hipEventCreateWithFlags(&c->v2_ev, hipEventDisableTiming);
   (void)hipEventCreate(&c->v0_ev);
   (void)hipEventCreateWithFlags(&c->u_ev, hipEventDisableTiming);
-  if (const char* e = std::getenv("PRAOS_VRF3")) c->vrf3 = std::atoi(e) != 0;
-  if (const char* e = std::getenv("PRAOS_VRF_PRIO")) c->vrf_prio = std::atoi(e);
-  if (const char* e = std::getenv("PRAOS_VRF_ILP4")) c->vrf_ilp4 = std::atoi(e);
-  if (const char* e = std::getenv("PRAOS_V_EXCL")) c->v_excl = std::atoi(e);
-  if (const char* e = std::getenv("PRAOS_MISS4")) c->miss4 = std::atoi(e);
-  if (const char* e = std::getenv("PRAOS_KEY4")) c->key4 = std::atoi(e);
-  if (const char* e = std::getenv("PRAOS_U4")) c->u4 = std::atoi(e);
-  if (const char* e = std::getenv("PRAOS_CK4")) c->ck4 = std::atoi(e);
-  if (const char* e = std::getenv("PRAOS_KES_DEDUP")) c->kes_dedup = std::atoi(e);
-  if (const char* e = std::getenv("PRAOS_VRF_PERKEY")) c->vrf_perkey = std::atoi(e);
   (void)hipEventCreateWithFlags(&c->vrec_ev, hipEventDisableTiming);
+  sched_knobs_from_env(c->knobs);                     // the schedule's knobs: sched.hpp's table
   if (const char* e = std::getenv("PRAOS_POOL_KEYS")) (void)praos_set_option(c, PRAOS_OPT_POOL_KEYS, std::atoi(e));
-  if (const char* e = std::getenv("PRAOS_VRF_KEYS_FIRST")) c->vrf_keys_first = std::atoi(e);
-  if (const char* e = std::getenv("PRAOS_VRF_WIDE")) (void)praos_set_vrf_wide(c, std::atoi(e), c->vrf_wide_cap);
-  if (const char* e = std::getenv("PRAOS_WIDE_PRIO")) c->wide_prio = std::atoi(e);
-  if (const char* e = std::getenv("PRAOS_VRF_WIDE_CAP")) (void)praos_set_vrf_wide(c, c->vrf_wide, std::atoi(e));
-  if (const char* e = std::getenv("PRAOS_PRE_JOIN")) c->pre_join = std::atoi(e);
-  if (const char* e = std::getenv("PRAOS_V_MAIN")) c->v_main = std::atoi(e);
-  if (const char* e = std::getenv("PRAOS_STREAM_CHUNK_V")) c->stream_chunk_v = std::atoi(e);
-  if (const char* e = std::getenv("PRAOS_KES_NOCACHE")) c->kes_nocache = (size_t)std::atoll(e);
-  if (const char* e = std::getenv("PRAOS_PBFT_CK_MIN")) c->pbft_ck_min = (size_t)std::atoll(e);
-  if (const char* e = std::getenv("PRAOS_MISS_PRIO")) c->miss_prio = std::atoi(e);
-  if (const char* e = std::getenv("PRAOS_KES_PAIR")) c->kes_pair = std::atol(e);
-  if (const char* e = std::getenv("PRAOS_KC_MIN")) (void)std::sscanf(e, "%d,%d,%d", &c->kc_min[0], &c->kc_min[1], &c->kc_min[2]);
-  if (const char* e = std::getenv("PRAOS_TP_STAGED")) c->tp_staged = std::atoi(e) != 0;
-  if (const char* e = std::getenv("PRAOS_PIPE_HEAD")) c->pipe_head = std::max(5, std::min(100, std::atoi(e)));
-  if (const char* e = std::getenv("PRAOS_PIPE_TAIL")) c->pipe_tail = std::max(5, std::min(100, std::atoi(e)));
   (void)hipEventCreate(&c->v1_ev);
   (void)hipEventCreate(&c->kc0_ev);
   (void)hipEventCreate(&c->kc1_ev);
@@ -1148,7 +1123,7 @@ static int pbft_verify_dev(praos_ctx* c, praos_batch* b, size_t n, const uint8_t
                            const uint64_t* hoff, const uint32_t* hlen, const uint8_t* d_ebb,
                            const praos_pbft_params* p, const uint8_t* delegs, uint32_t n_delegs, praos_pbft_out* out) {
   const std::vector<std::array<uint32_t, 8>> tab = pbft_deleg_table(delegs, n_delegs);
-  const bool cached = c->keycache > 0 && n >= c->pbft_ck_min;
+  const bool cached = c->keycache > 0 && n >= c->knobs.pbft_ck_min;
   uint8_t *d_bits = nullptr, *d_dhash = nullptr, *d_keys = nullptr, *d_sig = nullptr, *d_hram = nullptr;
   uint32_t *d_tab = nullptr, *d_vlist = nullptr, *d_vcount = nullptr;
   int32_t* d_gk = nullptr;
@@ -1208,11 +1183,11 @@ static int pbft_verify_dev(praos_ctx* c, praos_batch* b, size_t n, const uint8_t
     launch_pbft_sig(st, n, list, count, c->btab, d_keys, d_sig, d_hram, d_bits, b->tab_ocert);
   };
   if (cached) {
-    const bool pk = c->pk_on;
-    c->pk_on = false;                                  // the batch's own entries, not the pool-key store
-    const int r = kc_lists(c, b, k, n, d_keys, st, d_vlist, d_vcount, 0);
-    if (r == PRAOS_OK) kc_precompute(c, k, d_keys, 0, st, n);
-    c->pk_on = pk;
+    RunShape shape = run_shape(c, n, false, false);
+    shape.pool_keys = 0;                               // the batch's own entries, not the pool-key store
+    const RunPlan P = plan_run(c->knobs, shape);
+    const int r = kc_lists(c, b, P, k, n, d_keys, st, d_vlist, d_vcount, 0);
+    if (r == PRAOS_OK) kc_precompute(c, P, k, d_keys, 0, st, n);
     if (r != PRAOS_OK) return r;
     launch_pbft_sig_ck(st, n, k.hit, k.counters + 1, k.item_entry, k.kt, k.ki, c->bcomb16, d_keys, d_sig, d_hram,
                        d_bits);
@@ -1619,8 +1594,8 @@ int praos_set_option(praos_ctx* c, int opt, int value) {
   if (opt == PRAOS_OPT_KEYCACHE) { c->keycache = value < 0 ? 0 : value; return PRAOS_OK; }
   if (opt == PRAOS_OPT_DEDUP) { c->dedup = value != 0; return PRAOS_OK; }
   if (opt == PRAOS_OPT_PIPELINE) { c->pipeline = value < 0 ? 0 : std::min(value, PIPE_MAX); return PRAOS_OK; }
-  if (opt == PRAOS_OPT_KES_PAIR) { c->kes_pair = value < 0 ? -1 : value; return PRAOS_OK; }
-  if (opt == PRAOS_OPT_KES_NOCACHE) { c->kes_nocache = value < 0 ? KES_NOCACHE_BATCH : (size_t)value; return PRAOS_OK; }
+  if (opt == PRAOS_OPT_KES_PAIR) { c->knobs.kes_pair = value < 0 ? -1 : value; return PRAOS_OK; }
+  if (opt == PRAOS_OPT_KES_NOCACHE) { c->knobs.kes_nocache = value < 0 ? KES_NOCACHE_BATCH : (size_t)value; return PRAOS_OK; }
   if (opt == PRAOS_OPT_POOL_KEYS) {
     c->pool_keys = value < 0 ? -1 : (value != 0);
     if (value == 2) c->pk_reset[0] = c->pk_reset[1] = true;
@@ -1631,8 +1606,8 @@ int praos_set_option(praos_ctx* c, int opt, int value) {
 
 int praos_set_vrf_wide(praos_ctx* c, int min_uses, int max_keys) {
   if (!c) return PRAOS_E_ARG;
-  c->vrf_wide = min_uses < 0 ? -1 : min_uses;
-  c->vrf_wide_cap = max_keys < 1 ? 4096 : std::min(max_keys, 1 << 16);
+  c->knobs.vrf_wide = sched_clamp_vrf_wide(min_uses);
+  c->knobs.vrf_wide_cap = sched_clamp_vrf_wide_cap(max_keys);
   return PRAOS_OK;
 }
 
@@ -2117,8 +2092,8 @@ static int verify_bytes_pipelined(praos_ctx* c, const praos_header_bytes* in, pr
   {
     // weights: head / 100 for chunk 0, tail / 100 for chunk K-1, 1 for the others
     std::vector<size_t> w(K, 100);
-    w[0] = (size_t)c->pipe_head;
-    if (K > 2) w[K - 1] = (size_t)c->pipe_tail;
+    w[0] = (size_t)c->knobs.pipe_head;
+    if (K > 2) w[K - 1] = (size_t)c->knobs.pipe_tail;
     size_t W = 0, acc = 0;
     for (int k = 0; k < K; k++) W += w[k];
     lo[0] = 0;
@@ -2160,7 +2135,7 @@ static int verify_bytes_pipelined(praos_ctx* c, const praos_header_bytes* in, pr
   const uint32_t* eta = b->eta_tab ? b->eta_tab : c->d_eta0;
   // stage V chunk by chunk under the upload, or (submitted calls, PRAOS_STREAM_CHUNK_V=0) in the
   // run over the whole batch
-  const bool vrf = (c->kernels & 4) != 0 && (!async || c->stream_chunk_v);
+  const bool vrf = (c->kernels & 4) != 0 && (!async || c->knobs.stream_chunk_v);
   uint64_t sent = 0;
   for (int k = 0; k < K; k++) {
     if (need[k] > sent) {
@@ -2186,7 +2161,7 @@ static int verify_bytes_pipelined(praos_ctx* c, const praos_header_bytes* in, pr
       hipStream_t sv = (k & 1) ? c->vstream2 : c->vstream;
       HIPCHK(c, hipStreamWaitEvent(sv, c->done_ev[k], 0));
       launch_vrf_v(sv, n, b->vrf_vk, b->vrf_proof, b->slot, eta, c->eta0_neutral, b->eta_idx, b->tab_vrf,
-                   b->vrf_mid, lo[k], lo[k + 1], 0, 0, c->v_ilp4(n));
+                   b->vrf_mid, lo[k], lo[k + 1], 0, 0, sched_v_ilp4(c->knobs, n));
       HIPCHK(c, hipGetLastError());
     }
   }
@@ -2214,9 +2189,14 @@ static int verify_bytes_pipelined(praos_ctx* c, const praos_header_bytes* in, pr
     return PRAOS_OK;
   }
   // the VRF outputs (pool index, beta, leader and nonce values: 132 of the 134 bytes per
-  // header) are final once the VRF stream is done: they come back while KES still runs
+  // header) are final once the VRF stream and its miss stream are done: they come back while KES
+  // still runs.  (The two-stage VRF writes the uncached keys' outputs, and with a wide tier the
+  // chunk tier's, on the miss stream, which the VRF stream does not wait for: mdone_ev[2], recorded
+  // at the end of the run, covers them.  Without this wait a small batch forced to the two-stage
+  // form lost the race: tests/test_gpu_group.py::test_large_batch_plan_equals_default)
   if (r == PRAOS_OK && c->concurrent) {
     HIPCHK(c, hipStreamWaitEvent(c->cstream, c->side_ev[2], 0));
+    HIPCHK(c, hipStreamWaitEvent(c->cstream, c->mdone_ev[2], 0));
     auto dn = [&](void* dst, const void* src, size_t nb) -> hipError_t {
       return dst && nb ? d2h_on(c, dst, src, nb, c->cstream) : hipSuccess;
     };

@@ -310,3 +310,96 @@ def test_schedule_variants_equal_single_batch(ctx, c5_batch, env, concurrent):
                 assert np.array_equal(D1[k], D2[k]), (chunks, k)
     finally:
         c2.close()
+
+
+def _context_under(env):
+    """a context opened with env set (the schedule's knobs are read when a context opens)"""
+    import praos_hip
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return praos_hip.Context(0)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+
+
+# every auto knob at the value it takes at 432,000 headers (csrc/sched.hpp plan_run; tests/test_sched_plan.py
+# pins the rules): the two-stage VRF, no ILP-4 build, KES Merkle dedup and leaf-key cache, no k_vrf_pool,
+# key precompute at normal and uncached verifies at raised wave priority -- and the wide tier from 2 uses
+# on, so that it has keys at this size
+LARGE_BATCH_ENV = {"PRAOS_VRF3": "0", "PRAOS_VRF_ILP4": "0", "PRAOS_MISS4": "0", "PRAOS_KEY4": "0", "PRAOS_U4": "0",
+                   "PRAOS_KES_DEDUP": "1", "PRAOS_KES_NOCACHE": "0", "PRAOS_PRE_JOIN": "0", "PRAOS_KEY_PRIO": "0",
+                   "PRAOS_MISS_PRIO": "1", "PRAOS_VRF_WIDE": "2"}
+
+
+def test_large_batch_plan_equals_default(ctx, c5_batch):
+    """The schedule of the 432,000-header headline, forced onto the 20,011-header batch, gives the
+    default context's outputs and decoded arrays bit for bit, in one batch and pipelined (8 chunks);
+    and the run did take the large batch's branches: the wide tier and the KES leaf-key cache have
+    entries (at this size the default plan has neither)."""
+    from praos_hip import abi
+    cfg, H, pool_list, corrupted, p, arena, off, ln = c5_batch
+    ctx.set_epoch(cfg["eta0"], pool_list, p)
+    ctx.set_option(abi.OPT_PIPELINE, 1)
+    try:
+        o1, D1 = ctx.verify_header_bytes(arena, off, ln, decoded=True)
+    finally:
+        ctx.set_option(abi.OPT_PIPELINE, 0)
+    c2 = _context_under(LARGE_BATCH_ENV)
+    try:
+        c2.set_epoch(cfg["eta0"], pool_list, p)
+        for chunks in (1, 8):
+            c2.set_option(abi.OPT_PIPELINE, chunks)
+            o2, D2 = c2.verify_header_bytes(arena, off, ln, decoded=True)
+            for k in o1:
+                assert np.array_equal(o1[k], o2[k]), (chunks, k)
+            for k in D1:
+                assert np.array_equal(D1[k], D2[k]), (chunks, k)
+        # resident batches, for the caches' statistics
+        stats, outs = [], []
+        for c in (ctx, c2):
+            b = c.upload(H)
+            try:
+                c.run(b)
+                stats.append(c.batch_stats(b))
+                outs.append(c.download(b, len(off)))
+            finally:
+                c.free(b)
+        for k in outs[0]:
+            assert np.array_equal(outs[0][k], outs[1][k]), k
+        assert stats[0]["vrf_wide_keys"] == 0 and stats[0]["kes_hits"] == 0, stats[0]
+        assert stats[1]["vrf_wide_keys"] > 0 and stats[1]["vrf_wide_hits"] > 0 and stats[1]["kes_hits"] > 0, stats[1]
+    finally:
+        c2.close()
+
+
+def test_tpraos_staged_wide_equals_one_kernel():
+    """Staged TPraos with the VRF key cache's wide tier (both certificates' cached U against the
+    chunk and the wide tables) against the one-kernel k_vrf_tp, on the smallest TPraos chain of
+    tests/test_gpu_tpraos.py (256 headers of 6 pools, 15 % corrupted): every output bit for bit."""
+    from fractions import Fraction
+    from helpers import b2b
+    from praos_hip import abi, fixed
+    p = abi.params(c_raw=fixed.active_slot_log(Fraction(1, 2)))
+    eta0 = b2b(b"tpraos-epoch")
+    outs = []
+    for env in ({"PRAOS_VRF_WIDE": "2"}, {"PRAOS_TP_STAGED": "0"}):
+        c = _context_under(env)
+        try:
+            H, pools, corrupted = c.synthesize(256, 6, p, eta0, b"\x33" * 32, first_slot=5000, slot_stride=3,
+                                               corrupt_per_10000=1500, tpraos=True)
+            sig = [fixed.from_rational(Fraction(1, 6))] * 6
+            c.set_epoch(eta0, [(h, v, s) for (h, v), s in zip(pools, sig)], p)
+            outs.append(c.verify_tpraos_headers(H))
+        finally:
+            c.close()
+    o, o2 = outs
+    assert set(o) == set(o2)
+    for k in o:
+        assert np.array_equal(np.asarray(o[k]), np.asarray(o2[k])), k
+    assert np.count_nonzero(corrupted) and any(int(x) & (0x0400 | 0x0800) for x in o["bits"])
+    assert any(int(x) & ~0x1000 == 0 for x in o["bits"])
