@@ -669,6 +669,77 @@ int praos_verify_tx_witnesses(praos_ctx* ctx, const praos_header_bytes* blocks, 
 int praos_block_batch_tx_witnesses(praos_ctx* ctx, praos_batch* b, const praos_txw_cfg* cfg,
                                    praos_txw_blocks* blocks_out, praos_txw_txs* txs, praos_txw_wits* wits);
 
+/* ---- TxSubmission transactions: wire GenTxs, each checked once (additive: ABI version unchanged) ----
+ * The key-witness check above for transactions as a peer offers them, before the mempool's addTx:
+ * the second caller of that check, applyShelleyTx (Shelley/Ledger/Mempool.hs:215-239).
+ * items: wire GenTx spans in one arena, as praos_unwrap_wire_headers takes wire headers.
+ *   Shelley-based eras  [eraIndex, #6.24(bytes)], the bytes one array [body, wits, aux / null]
+ *                       (era index 1..3) or [body, wits, isValid, aux / null] (era index >= 4)
+ *                       (decodeNS; Shelley/Ledger/Mempool.hs:186-193 wrapCBORinCBOR)
+ *   Byron (era 0)       [0, [kind, payload]], kind 0..3 (Byron/Ledger/Mempool.hs encodeByronGenTx):
+ *                       unwrapped only -- the payload is every byte after the kind up to the end of
+ *                       the item, at least one; no row, no witnesses
+ * The wrapper's heads are taken at any width; its lists and the byte string are definite and the
+ * tag is 24, as for wire headers.  The inner array may be definite (of exactly 3 / 4 items) or
+ * indefinite; body, wits and the last item are one well-formed CBOR item each.
+ * Item status: PRAOS_WIRE_OK / RANGE / SYNTAX / ERA / TRAILING with their meaning above, and
+ *   PRAOS_GTX_SHAPE   no row: the inner bytes are not one such array (wrong count, another type, a
+ *                     malformed item, bytes after the array inside the byte string), the body is
+ *                     no map, the third of four items is neither 0xf4 nor 0xf5, or (era >= 4) the
+ *                     value under the witness set's first key 5 has neither redeemer form
+ *   PRAOS_GTX_BYRON   an era-0 item of the form above; any other era-0 form is SYNTAX
+ * Rows: one per distinct transaction.  With cfg->dedup two items share a row iff their era index
+ * and their inner bytes are equal (Blake2b-256 of the inner bytes, whole hashes compared): the
+ * same body under another witness set or another era index is another row.  Rows are numbered in
+ * order of first appearance; without dedup every PRAOS_WIRE_OK item is its own row.
+ * Witnesses: praos_verify_tx_witnesses' rules over the row's wit span and tx_id, word for word. */
+#define PRAOS_GTX_SHAPE 5
+#define PRAOS_GTX_BYRON 6
+#define PRAOS_GTX_PER_TX_OVERHEAD 4u /* Shelley/Ledger/Mempool.hs:125-143 perTxOverhead */
+typedef struct {
+  uint32_t n_eras;                /* eras of the block type (7 for the reference's CardanoBlock); 1..32 */
+  uint32_t dedup;                 /* non-zero: byte-identical transactions share a row */
+  uint32_t max_lanes;             /* as praos_txw_cfg */
+  uint32_t pad_;
+} praos_gtx_cfg;
+typedef struct {                  /* per item (n entries); every pointer may be NULL = not returned */
+  uint8_t* status;                /* PRAOS_WIRE_* / PRAOS_GTX_* */
+  uint8_t* era;                   /* the wire era index (0xff until it is read) */
+  uint32_t* row;                  /* the item's distinct-transaction row, 0xffffffff: none */
+  uint8_t* byron_kind;            /* PRAOS_GTX_BYRON: 0..3; otherwise 0xff */
+  uint64_t* payload_off;          /* PRAOS_GTX_BYRON: the payload span, into items->bytes; otherwise 0 */
+  uint32_t* payload_len;
+} praos_gtx_items;
+typedef struct {                  /* per distinct transaction; caller buffers of cap rows, every pointer may be NULL */
+  size_t cap;
+  size_t n_rows;                  /* out: the rows of the call */
+  uint32_t* item;                 /* the lowest item index of the class */
+  uint8_t* era;
+  uint64_t* body_off;             /* spans into items->bytes */
+  uint32_t* body_len;
+  uint64_t* wit_off;
+  uint32_t* wit_len;
+  uint64_t* aux_off;
+  uint32_t* aux_len;              /* 0 when the last item is null (0xf6) */
+  uint32_t* size;                 /* 1 + body_len + wit_len + the last item's stored length: sizeTxF */
+  uint32_t* in_block_size;        /* size + PRAOS_GTX_PER_TX_OVERHEAD: txInBlockSize */
+  uint64_t* ex_mem;               /* totExUnits: the sums mod 2^64 over the redeemers under the */
+  uint64_t* ex_steps;             /* witness set's first key 5, both forms; 0 for eras 1..3 */
+  uint8_t* is_valid;              /* the third item (0xf5: 1) for eras >= 4; 1 for eras 1..3 */
+  uint8_t* tx_id;                 /* cap * 32: Blake2b-256 of the body bytes */
+  uint8_t* wstatus;               /* PRAOS_TXW_OK / PRAOS_TXW_SHAPE */
+  uint32_t* n_vkey;
+  uint32_t* n_boot;
+  uint32_t* n_bad;                /* witnesses of the row that do not verify */
+  uint64_t* wit_first;            /* cap + 1: exclusive prefix sum of n_vkey + n_boot (n_rows + 1 written) */
+} praos_gtx_txs;
+/* per_item, txs and wits may be NULL; wits->tx holds the row.  When an array of txs (wits) is given
+ * and its cap is below n_rows (n_wits): PRAOS_E_ARG with n_rows and n_wits = the counts needed and
+ * the per-item arrays filled; with no array given cap is not looked at (the sizing call).  n = 0
+ * is PRAOS_OK. */
+int praos_verify_gen_txs(praos_ctx* ctx, const praos_header_bytes* items, const praos_gtx_cfg* cfg,
+                         praos_gtx_items* per_item, praos_gtx_txs* txs, praos_txw_wits* wits);
+
 /* ---- Byron header validation: PBFT (additive as the two sections above: ABI version unchanged) ----
  * validateHeader for Byron = validateEnvelope (HeaderValidation.hs:297-344 with the Byron
  * instance, Byron/Ledger/HeaderValidation.hs:39-75) + PBFT updateChainDepState

@@ -66,6 +66,8 @@ module Ouroboros.Consensus.Protocol.Praos.Batch
   , BlockTxStats (..)
   , praosIndexBlockTxs
   , praosVerifyTxWitnesses
+  , GenTxResults (..)
+  , praosVerifyGenTxs
   , BlockWitnessStats (..)
     -- * Byron header validation (PBFT)
   , PBftParamsC (..)
@@ -228,6 +230,14 @@ foreign import ccall safe "praos_index_block_txs" c_index_block_txs
 -- layout-txw praos_txw_txs (72 bytes): cap@0 n_rows@8 block@16 status@24 n_vkey@32 n_boot@40 n_bad@48 tx_id@56 wit_first@64
 -- layout-txw praos_txw_wits (64 bytes): cap@0 n_wits@8 tx@16 kind@24 key_off@32 sig_off@40 ok@48 key_hash@56
 foreign import ccall safe "praos_verify_tx_witnesses" c_verify_tx_witnesses
+  :: Ptr PraosCtx -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> IO CInt
+-- additive as well (ABI version unchanged): wire transactions of the TxSubmission inbound side.
+-- Its structs (checked against the C compiler by tests/test_gentx_abi.py, which owns the
+-- "layout-gtx" lines; praos_txw_wits is the struct above):
+-- layout-gtx praos_gtx_cfg (16 bytes): n_eras@0 dedup@4 max_lanes@8 pad_@12
+-- layout-gtx praos_gtx_items (48 bytes): status@0 era@8 row@16 byron_kind@24 payload_off@32 payload_len@40
+-- layout-gtx praos_gtx_txs (168 bytes): cap@0 n_rows@8 item@16 era@24 body_off@32 body_len@40 wit_off@48 wit_len@56 aux_off@64 aux_len@72 size@80 in_block_size@88 ex_mem@96 ex_steps@104 is_valid@112 tx_id@120 wstatus@128 n_vkey@136 n_boot@144 n_bad@152 wit_first@160
+foreign import ccall safe "praos_verify_gen_txs" c_verify_gen_txs
   :: Ptr PraosCtx -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> IO CInt
 -- additive as well (ABI version unchanged): Byron header validation.  The structs
 -- validatePBftHeaderBatch pokes and peeks (checked against the C compiler by tests/test_pbft_abi.py;
@@ -1056,6 +1066,65 @@ praosVerifyTxWitnesses ctx byron arena offs lens = do
       check ctx $ c_verify_tx_witnesses p (castPtr hb) (castPtr wcfg) (castPtr blks) (castPtr txs) (castPtr wits)
   BlockWitnessStats <$> VS.unsafeFreeze st <*> VS.unsafeFreeze ntx <*> VS.unsafeFreeze nwit <*> VS.unsafeFreeze nbad
                     <*> VS.unsafeFreeze nshape
+
+-- | What the TxSubmission inbound side learns about the transactions its peers offered, before
+-- 'addTx': per wire item its status (0 OK, 1..4 the wire wrapper's, 5 not the shape of a
+-- transaction, 6 a Byron item, unwrapped only) and the row of its transaction (0xffffffff: none);
+-- per distinct transaction what the mempool measures ('txInBlockSize', 'totExUnits') and the
+-- outcome of the key-witness signature check 'applyShelleyTx' makes
+-- (Shelley/Ledger/Mempool.hs:215-239): @gtrBad@ witnesses fail, @gtrWitStatus@ 1 when the witness
+-- set is outside the shapes read.  Which keys had to sign is the ledger's to say.
+data GenTxResults = GenTxResults
+  { gtrStatus      :: !(VS.Vector Word8)
+  , gtrRow         :: !(VS.Vector Word32)
+  , gtrTxId        :: !(VS.Vector Word8)     -- ^ rows x 32
+  , gtrInBlockSize :: !(VS.Vector Word32)
+  , gtrExMem       :: !(VS.Vector Word64)
+  , gtrExSteps     :: !(VS.Vector Word64)
+  , gtrWitStatus   :: !(VS.Vector Word8)
+  , gtrBad         :: !(VS.Vector Word32)
+  }
+
+-- | praos_verify_gen_txs over the wire transactions @arena[off_i .. off_i + len_i)@ (GenTxs in the
+-- node-to-node encoding, as the peers sent them), byte-identical transactions sharing a row.  Two
+-- calls: the first, without row arrays, gives the number of distinct transactions.
+praosVerifyGenTxs :: PraosBatchCtx -> Word32 -> BS.ByteString -> VS.Vector Word64 -> VS.Vector Word32
+                  -> IO GenTxResults
+praosVerifyGenTxs ctx nEras arena offs lens = do
+  let n = VS.length offs
+  when (VS.length lens /= n) $ throwIO (PraosBatchError (-1) "praosVerifyGenTxs: vector lengths differ")
+  let p = ctxPtr ctx                           -- a group's first member: the check has no group form
+  st <- VSM.new n
+  row <- VSM.new n
+  BSU.unsafeUseAsCStringLen arena $ \(ap, alen) ->
+    VS.unsafeWith offs $ \offp -> VS.unsafeWith lens $ \lenp ->
+    VSM.unsafeWith st $ \stp -> VSM.unsafeWith row $ \rowp ->
+    allocaBytes 40 $ \hb -> allocaBytes 16 $ \gcfg -> allocaBytes 48 $ \its -> allocaBytes 168 $ \txs ->
+    allocaBytes 64 $ \wits -> do
+      pokeByteOff hb 0 (fromIntegral n :: CSize) >> pokeByteOff hb 8 ap
+      pokeByteOff hb 16 (fromIntegral alen :: CSize)
+      pokeByteOff hb 24 offp >> pokeByteOff hb 32 lenp
+      pokeByteOff gcfg 0 nEras >> pokeByteOff gcfg 4 (1 :: Word32)
+      pokeByteOff gcfg 8 (0 :: Word32) >> pokeByteOff gcfg 12 (0 :: Word32)
+      fillBytes its 0 48
+      pokeByteOff its 0 stp >> pokeByteOff its 16 rowp
+      fillBytes txs 0 168 >> fillBytes wits 0 64     -- no row arrays: the caps are not looked at
+      check ctx $ c_verify_gen_txs p (castPtr hb) (castPtr gcfg) (castPtr its) (castPtr txs) (castPtr wits)
+      rows <- fromIntegral <$> (peekByteOff txs 8 :: IO CSize)
+      txid <- VSM.new (32 * rows)
+      ibs <- VSM.new rows
+      mem <- VSM.new rows
+      steps <- VSM.new rows
+      wst <- VSM.new rows
+      bad <- VSM.new rows
+      VSM.unsafeWith txid $ \txidp -> VSM.unsafeWith ibs $ \ibsp -> VSM.unsafeWith mem $ \memp ->
+        VSM.unsafeWith steps $ \stepsp -> VSM.unsafeWith wst $ \wstp -> VSM.unsafeWith bad $ \badp -> do
+          pokeByteOff txs 0 (fromIntegral rows :: CSize)
+          pokeByteOff txs 88 ibsp >> pokeByteOff txs 96 memp >> pokeByteOff txs 104 stepsp
+          pokeByteOff txs 120 txidp >> pokeByteOff txs 128 wstp >> pokeByteOff txs 152 badp
+          check ctx $ c_verify_gen_txs p (castPtr hb) (castPtr gcfg) (castPtr its) (castPtr txs) (castPtr wits)
+      GenTxResults <$> VS.unsafeFreeze st <*> VS.unsafeFreeze row <*> VS.unsafeFreeze txid <*> VS.unsafeFreeze ibs
+                   <*> VS.unsafeFreeze mem <*> VS.unsafeFreeze steps <*> VS.unsafeFreeze wst <*> VS.unsafeFreeze bad
 
 -- | Per stored block what db-analyser's ledger-free analyses read off its transactions:
 -- 'HasAnalysis.blockTxSizes' (its length and sum), 'HasAnalysis.countTxOutputs' and the execution

@@ -466,6 +466,25 @@ namespace praos_impl {
 int txi_run(praos_ctx* c, praos_batch* b, const praos_txi_cfg* cfg, praos_txi_stats* st, praos_txi_rows* rows,
             txi_keep* keep);
 
+// praos_txwit.hip: the witness passes over T device rows (blk_kind[row_block[p]]: k_txindex.hip's
+// kind of the row's block; wit span; tx_id [T][32]).  Everything is enqueued on the context's
+// stream; the results stay on the device in R, wit_first and the witness count on the host.
+struct txw_rows {
+  DevBuf buf_t, buf_w;
+  uint8_t* st = nullptr;                                  // T: PRAOS_TXW_*
+  uint32_t *nv = nullptr, *nb = nullptr, *cnt = nullptr, *txbad = nullptr, *d_wfirst = nullptr;
+  uint64_t *v0 = nullptr, *v2 = nullptr;
+  uint32_t* tx = nullptr;                                 // W: the witness records
+  uint8_t *kind = nullptr, *ok = nullptr, *kh = nullptr;
+  uint64_t *koff = nullptr, *soff = nullptr;
+  std::vector<uint32_t> wfirst;                           // T + 1
+  uint64_t W = 0;
+};
+int txw_rows_run(praos_ctx* c, const char* who, const uint8_t* arena, uint64_t arena_len, size_t T,
+                 const uint8_t* blk_kind, const uint32_t* row_block, const uint64_t* wit_off, const uint32_t* wit_len,
+                 const uint8_t* tx_id, uint32_t max_lanes, txw_rows& R);
+int txw_rows_down_wits(praos_ctx* c, praos_txw_wits* wits, const txw_rows& R);
+
 // praos_api.hip: the radix-2^16 comb, k_decode_praos over a from-bytes batch, the overlay class
 // of a slot
 int ensure_bcomb16(praos_ctx* c);

@@ -203,6 +203,20 @@ void launch_hdr_dedup(hipStream_t stream, size_t n, const uint8_t* status, const
   hipLaunchKernelGGL(k_hdr_map, g, b, 0, stream, n, item_slot, item_rep, rep_row, item_row);
 }
 
+// the numbering alone, over item_slot / slot_min a caller filled (k_gentx.hip): representatives,
+// rows in order of first appearance, each item's row
+void launch_hdr_number(hipStream_t stream, size_t n, const uint32_t* item_slot, const uint32_t* slot_min,
+                       uint32_t* item_rep, uint32_t* blk, uint32_t* total, const uint64_t* ioff, const uint32_t* ilen,
+                       uint32_t rows_cap, uint64_t* row_off, uint32_t* row_len, uint32_t* rep_row, uint32_t* item_row) {
+  if (!n) return;
+  const dim3 g((unsigned)((n + NT - 1) / NT)), b(NT);
+  hipLaunchKernelGGL(k_hdr_count, g, b, 0, stream, n, item_slot, slot_min, item_rep, blk);
+  hipLaunchKernelGGL(k_hdr_scan, dim3(1), dim3(SCAN_NT), 0, stream, g.x, blk, total);
+  hipLaunchKernelGGL(k_hdr_rows, g, b, 0, stream, n, item_slot, item_rep, blk, ioff, ilen, rows_cap, row_off, row_len,
+                     rep_row);
+  hipLaunchKernelGGL(k_hdr_map, g, b, 0, stream, n, item_slot, item_rep, rep_row, item_row);
+}
+
 // after launch_hdr_dedup on the same stream: row_is_ebb (rows_cap bytes) of the Byron rows
 void launch_hdr_row_kind(hipStream_t stream, size_t n, const uint32_t* item_slot, const uint32_t* item_rep,
                          const uint32_t* rep_row, const uint8_t* kind, uint32_t rows_cap, uint8_t* row_is_ebb) {

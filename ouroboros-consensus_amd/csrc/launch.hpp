@@ -352,3 +352,62 @@ void launch_hdr_dedup(hipStream_t stream, size_t n, const uint8_t* status, const
                       uint32_t rows_cap, uint64_t* row_off, uint32_t* row_len, uint32_t* rep_row, uint32_t* item_row);
 void launch_hdr_row_kind(hipStream_t stream, size_t n, const uint32_t* item_slot, const uint32_t* item_rep,
                          const uint32_t* rep_row, const uint8_t* kind, uint32_t rows_cap, uint8_t* row_is_ebb);
+// launch_hdr_dedup without its hash set: the count / scan / rows / map kernels over item_slot and
+// slot_min as a caller filled them
+void launch_hdr_number(hipStream_t stream, size_t n, const uint32_t* item_slot, const uint32_t* slot_min,
+                       uint32_t* item_rep, uint32_t* blk, uint32_t* total, const uint64_t* ioff, const uint32_t* ilen,
+                       uint32_t rows_cap, uint64_t* row_off, uint32_t* row_len, uint32_t* rep_row, uint32_t* item_row);
+// wire transactions (k_gentx.hip).  Per-item arrays of n entries (hash may be NULL) and the final
+// rows' arrays (n entries each: a call has at most n rows; block: zeros, the row_block of
+// launch_txw_count under a one-entry kind table).  split: unwrap, top-level walk, dedup hash.
+// ident: item_slot / slot_min for launch_hdr_number, every index below *limit (NULL: n) with
+// flag[i] == flag_ok a class of its own.  rep: row_item[row] = the row's representative (row_item
+// set to 0xff by the caller).  rows: provisional rows [0, *total): row_ok, the ExUnits sums, tx_id.
+// final: the kept rows' fields at row_final[row]; item_row from provisional to final rows, the
+// items of refused rows PRAOS_GTX_SHAPE.
+struct praos_gtx_dev_items {
+  uint8_t* status;
+  uint8_t* era;
+  uint8_t* kind;
+  uint8_t* is_valid;
+  uint64_t* ioff;
+  uint32_t* ilen;
+  uint64_t* body_off;
+  uint32_t* body_len;
+  uint64_t* wit_off;
+  uint32_t* wit_len;
+  uint64_t* aux_off;
+  uint32_t* aux_len;
+  uint32_t* size;
+  uint8_t* hash;
+};
+struct praos_gtx_dev_rows {
+  uint32_t* item;
+  uint8_t* era;
+  uint64_t* body_off;
+  uint32_t* body_len;
+  uint64_t* wit_off;
+  uint32_t* wit_len;
+  uint64_t* aux_off;
+  uint32_t* aux_len;
+  uint32_t* size;
+  uint32_t* in_block_size;
+  uint64_t* ex_mem;
+  uint64_t* ex_steps;
+  uint8_t* is_valid;
+  uint8_t* tx_id;
+  uint32_t* block;
+};
+void launch_gtx_split(hipStream_t stream, size_t n, const uint8_t* arena, uint64_t arena_len, const uint64_t* off,
+                      const uint32_t* len, uint32_t n_eras, const praos_gtx_dev_items* items);
+void launch_gtx_ident(hipStream_t stream, size_t n, const uint32_t* limit, const uint8_t* flag, uint8_t flag_ok,
+                      uint32_t* item_slot, uint32_t* slot_min);
+void launch_gtx_rep(hipStream_t stream, size_t n, const uint32_t* item_slot, const uint32_t* item_rep,
+                    const uint32_t* rep_row, uint32_t* row_item);
+void launch_gtx_rows(hipStream_t stream, size_t n, const uint32_t* total, const uint8_t* arena, const uint32_t* row_item,
+                     const praos_gtx_dev_items* items, uint8_t* row_ok, uint64_t* ex_mem, uint64_t* ex_steps,
+                     uint8_t* tx_id);
+void launch_gtx_final(hipStream_t stream, size_t n, const uint32_t* total, const uint32_t* row_item,
+                      const uint8_t* row_ok, const uint32_t* row_final, const uint64_t* ex_mem, const uint64_t* ex_steps,
+                      const uint8_t* tx_id, const praos_gtx_dev_items* items, uint32_t* item_row,
+                      const praos_gtx_dev_rows* rows);

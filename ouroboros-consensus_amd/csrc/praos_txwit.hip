@@ -8,6 +8,10 @@
 // round trips, two of them the index's.  Every slice runs on the context's stream, one after the
 // other over the same tables; a witness's result depends on its own bytes alone, so the outputs do
 // not depend on the slice size.
+//
+// The passes after the index are txw_rows_run, over any device rows (kind table, row block, wit
+// span, tx_id): praos_verify_gen_txs (praos_gentx.hip) runs the same step over the rows of wire
+// transactions, which have no block -- a one-entry kind table and a row_block of zeros.
 #include "api_internal.hpp"
 
 namespace {
@@ -24,6 +28,104 @@ bool any_tx_array(const praos_txw_txs* t) {
 bool any_wit_array(const praos_txw_wits* w) {
   return w && (w->tx || w->kind || w->key_off || w->sig_off || w->ok || w->key_hash);
 }
+
+}  // namespace
+
+namespace praos_impl {
+
+// count, the counts down and their prefix sum up, emit, the verify slices, the per-row reduction:
+// everything is enqueued on the context's stream; R owns the buffers and holds wit_first and W
+int txw_rows_run(praos_ctx* c, const char* who, const uint8_t* arena, uint64_t arena_len, size_t T,
+                 const uint8_t* blk_kind, const uint32_t* row_block, const uint64_t* wit_off, const uint32_t* wit_len,
+                 const uint8_t* tx_id, uint32_t max_lanes, txw_rows& R) {
+  hipStream_t s = c->stream;
+  if (carve_alloc(R.buf_t, [&](Carve& m) {
+        R.st = m.take<uint8_t>(T);
+        R.nv = m.take<uint32_t>(4 * T);
+        R.nb = m.take<uint32_t>(4 * T);
+        R.cnt = m.take<uint32_t>(4 * T);
+        R.d_wfirst = m.take<uint32_t>(4 * (T + 1));
+        R.txbad = m.take<uint32_t>(4 * T);
+        R.v0 = m.take<uint64_t>(8 * T);
+        R.v2 = m.take<uint64_t>(8 * T);
+      }) != hipSuccess) {
+    c->err = "device allocation failed";
+    return PRAOS_E_OOM;
+  }
+  (void)hipGetLastError();
+  launch_txw_count(s, T, arena, arena_len, blk_kind, row_block, wit_off, wit_len, R.st, R.nv, R.nb, R.cnt, R.v0, R.v2);
+  HIPCHK(c, hipGetLastError());
+  std::vector<uint32_t> h_cnt(T);
+  R.wfirst.assign(T + 1, 0);
+  HIPCHK(c, hipMemcpyAsync(h_cnt.data(), R.cnt, 4 * T, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  uint64_t W = 0;
+  for (size_t p = 0; p < T; p++) {
+    R.wfirst[p] = (uint32_t)W;
+    W += h_cnt[p];
+    if (W > 0xfffffff0ull) { c->err = std::string(who) + ": too many witnesses in one call"; return PRAOS_E_ARG; }
+  }
+  R.wfirst[T] = (uint32_t)W;
+  R.W = W;
+  HIPCHK(c, hipMemcpyAsync(R.d_wfirst, R.wfirst.data(), 4 * (T + 1), hipMemcpyHostToDevice, s));
+  if (W) {
+    if (carve_alloc(R.buf_w, [&](Carve& m) {
+          R.tx = m.take<uint32_t>(4 * W);
+          R.kind = m.take<uint8_t>(W);
+          R.koff = m.take<uint64_t>(8 * W);
+          R.soff = m.take<uint64_t>(8 * W);
+          R.ok = m.take<uint8_t>(W);
+          R.kh = m.take<uint8_t>(28 * W);
+        }) != hipSuccess) {
+      c->err = "device allocation failed";
+      return PRAOS_E_OOM;
+    }
+    const size_t lanes = std::min<size_t>((size_t)W, max_lanes ? max_lanes : TXW_LANES);
+    if (c->txw_lanes < lanes) {
+      HIPCHK(c, hipStreamSynchronize(s));
+      (void)hipFree(c->txw_tabs);
+      c->txw_tabs = nullptr;
+      c->txw_lanes = 0;
+      if (hipMalloc(&c->txw_tabs, lanes * LT_ED_B) != hipSuccess) {
+        c->txw_tabs = nullptr;
+        c->err = "device allocation failed";
+        return PRAOS_E_OOM;
+      }
+      c->txw_lanes = lanes;
+    }
+    launch_txw_emit(s, T, arena, wit_off, wit_len, R.nv, R.nb, R.v0, R.v2, R.d_wfirst, W, R.tx, R.kind, R.koff, R.soff);
+    HIPCHK(c, hipGetLastError());
+    for (size_t w0 = 0; w0 < W; w0 += lanes) {
+      launch_txw_verify(s, w0, std::min<size_t>((size_t)W, w0 + lanes), c->btab, arena, R.tx, R.kind, R.koff, R.soff,
+                        tx_id, R.ok, R.kh, c->txw_tabs);
+      HIPCHK(c, hipGetLastError());
+    }
+  }
+  launch_txw_tx(s, T, R.d_wfirst, R.ok, R.txbad);
+  HIPCHK(c, hipGetLastError());
+  return PRAOS_OK;
+}
+
+// the witness records into the caller's arrays (enqueued; the caller synchronises)
+int txw_rows_down_wits(praos_ctx* c, praos_txw_wits* wits, const txw_rows& R) {
+  hipStream_t s = c->stream;
+  const size_t W = (size_t)R.W;
+  if (!W) return PRAOS_OK;
+  auto down = [&](void* dst, const void* src, size_t bytes) {
+    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+  };
+  HIPCHK(c, down(wits->tx, R.tx, 4 * W));
+  HIPCHK(c, down(wits->kind, R.kind, W));
+  HIPCHK(c, down(wits->key_off, R.koff, 8 * W));
+  HIPCHK(c, down(wits->sig_off, R.soff, 8 * W));
+  HIPCHK(c, down(wits->ok, R.ok, W));
+  HIPCHK(c, down(wits->key_hash, R.kh, 28 * W));
+  return PRAOS_OK;
+}
+
+}  // namespace praos_impl
+
+namespace {
 
 int txw_run(praos_ctx* c, praos_batch* b, const praos_txw_cfg* cfg, praos_txw_blocks* bo, praos_txw_txs* txs,
             praos_txw_wits* wits) {
@@ -58,21 +160,16 @@ int txw_run(praos_ctx* c, praos_batch* b, const praos_txw_cfg* cfg, praos_txw_bl
     HIPCHK(c, hipStreamSynchronize(s));
     return PRAOS_OK;
   }
-  // ---- the count pass
-  uint8_t* d_st = nullptr;
-  uint32_t *d_nv = nullptr, *d_nb = nullptr, *d_cnt = nullptr, *d_wfirst = nullptr, *d_txbad = nullptr,
-           *d_bwit = nullptr, *d_bbad = nullptr, *d_bshape = nullptr;
-  uint64_t *d_v0 = nullptr, *d_v2 = nullptr;
-  DevBuf buf_t;
-  if (carve_alloc(buf_t, [&](Carve& m) {
-        d_st = m.take<uint8_t>(T);
-        d_nv = m.take<uint32_t>(4 * T);
-        d_nb = m.take<uint32_t>(4 * T);
-        d_cnt = m.take<uint32_t>(4 * T);
-        d_wfirst = m.take<uint32_t>(4 * (T + 1));
-        d_txbad = m.take<uint32_t>(4 * T);
-        d_v0 = m.take<uint64_t>(8 * T);
-        d_v2 = m.take<uint64_t>(8 * T);
+  // ---- the witness passes over the rows
+  praos_impl::txw_rows R;
+  const int rr = praos_impl::txw_rows_run(c, "praos_verify_tx_witnesses", b->arena, b->arena_len, T, K.kind, K.rows.block,
+                                          K.rows.wit_off, K.rows.wit_len, K.rows.tx_id, cfg->max_lanes, R);
+  if (wits) wits->n_wits = (size_t)R.W;
+  if (rr != PRAOS_OK) return rr;
+  const uint64_t W = R.W;
+  uint32_t *d_bwit = nullptr, *d_bbad = nullptr, *d_bshape = nullptr;
+  DevBuf buf_b;
+  if (carve_alloc(buf_b, [&](Carve& m) {
         d_bwit = m.take<uint32_t>(4 * n);
         d_bbad = m.take<uint32_t>(4 * n);
         d_bshape = m.take<uint32_t>(4 * n);
@@ -80,64 +177,7 @@ int txw_run(praos_ctx* c, praos_batch* b, const praos_txw_cfg* cfg, praos_txw_bl
     c->err = "device allocation failed";
     return PRAOS_E_OOM;
   }
-  (void)hipGetLastError();
-  launch_txw_count(s, T, b->arena, b->arena_len, K.kind, K.rows.block, K.rows.wit_off, K.rows.wit_len, d_st, d_nv, d_nb,
-                   d_cnt, d_v0, d_v2);
-  HIPCHK(c, hipGetLastError());
-  std::vector<uint32_t> h_cnt(T), h_wfirst(T + 1);
-  HIPCHK(c, hipMemcpyAsync(h_cnt.data(), d_cnt, 4 * T, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  uint64_t W = 0;
-  for (size_t p = 0; p < T; p++) {
-    h_wfirst[p] = (uint32_t)W;
-    W += h_cnt[p];
-    if (W > 0xfffffff0ull) { c->err = "praos_verify_tx_witnesses: too many witnesses in one call"; return PRAOS_E_ARG; }
-  }
-  h_wfirst[T] = (uint32_t)W;
-  if (wits) wits->n_wits = (size_t)W;
-  HIPCHK(c, hipMemcpyAsync(d_wfirst, h_wfirst.data(), 4 * (T + 1), hipMemcpyHostToDevice, s));
-  // ---- the witness records and the verifies
-  uint32_t* d_tx = nullptr;
-  uint8_t *d_kind = nullptr, *d_ok = nullptr, *d_kh = nullptr;
-  uint64_t *d_koff = nullptr, *d_soff = nullptr;
-  DevBuf buf_w;
-  if (W) {
-    if (carve_alloc(buf_w, [&](Carve& m) {
-          d_tx = m.take<uint32_t>(4 * W);
-          d_kind = m.take<uint8_t>(W);
-          d_koff = m.take<uint64_t>(8 * W);
-          d_soff = m.take<uint64_t>(8 * W);
-          d_ok = m.take<uint8_t>(W);
-          d_kh = m.take<uint8_t>(28 * W);
-        }) != hipSuccess) {
-      c->err = "device allocation failed";
-      return PRAOS_E_OOM;
-    }
-    const size_t lanes = std::min<size_t>((size_t)W, cfg->max_lanes ? cfg->max_lanes : TXW_LANES);
-    if (c->txw_lanes < lanes) {
-      HIPCHK(c, hipStreamSynchronize(s));
-      (void)hipFree(c->txw_tabs);
-      c->txw_tabs = nullptr;
-      c->txw_lanes = 0;
-      if (hipMalloc(&c->txw_tabs, lanes * LT_ED_B) != hipSuccess) {
-        c->txw_tabs = nullptr;
-        c->err = "device allocation failed";
-        return PRAOS_E_OOM;
-      }
-      c->txw_lanes = lanes;
-    }
-    launch_txw_emit(s, T, b->arena, K.rows.wit_off, K.rows.wit_len, d_nv, d_nb, d_v0, d_v2, d_wfirst, W, d_tx, d_kind,
-                    d_koff, d_soff);
-    HIPCHK(c, hipGetLastError());
-    for (size_t w0 = 0; w0 < W; w0 += lanes) {
-      launch_txw_verify(s, w0, std::min<size_t>((size_t)W, w0 + lanes), c->btab, b->arena, d_tx, d_kind, d_koff, d_soff,
-                        K.rows.tx_id, d_ok, d_kh, c->txw_tabs);
-      HIPCHK(c, hipGetLastError());
-    }
-  }
-  launch_txw_tx(s, T, d_wfirst, d_ok, d_txbad);
-  HIPCHK(c, hipGetLastError());
-  launch_txw_blocks(s, n, K.tfirst, d_st, d_cnt, d_txbad, d_bwit, d_bbad, d_bshape);
+  launch_txw_blocks(s, n, K.tfirst, R.st, R.cnt, R.txbad, d_bwit, d_bbad, d_bshape);
   HIPCHK(c, hipGetLastError());
   auto down = [&](void* dst, const void* src, size_t bytes) {
     return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
@@ -156,21 +196,17 @@ int txw_run(praos_ctx* c, praos_batch* b, const praos_txw_cfg* cfg, praos_txw_bl
   }
   if (want_t) {
     HIPCHK(c, down(txs->block, K.rows.block, 4 * T));
-    HIPCHK(c, down(txs->status, d_st, T));
-    HIPCHK(c, down(txs->n_vkey, d_nv, 4 * T));
-    HIPCHK(c, down(txs->n_boot, d_nb, 4 * T));
-    HIPCHK(c, down(txs->n_bad, d_txbad, 4 * T));
+    HIPCHK(c, down(txs->status, R.st, T));
+    HIPCHK(c, down(txs->n_vkey, R.nv, 4 * T));
+    HIPCHK(c, down(txs->n_boot, R.nb, 4 * T));
+    HIPCHK(c, down(txs->n_bad, R.txbad, 4 * T));
     HIPCHK(c, down(txs->tx_id, K.rows.tx_id, 32 * T));
     if (txs->wit_first)
-      for (size_t p = 0; p <= T; p++) txs->wit_first[p] = h_wfirst[p];
+      for (size_t p = 0; p <= T; p++) txs->wit_first[p] = R.wfirst[p];
   }
-  if (want_w && W) {
-    HIPCHK(c, down(wits->tx, d_tx, 4 * (size_t)W));
-    HIPCHK(c, down(wits->kind, d_kind, (size_t)W));
-    HIPCHK(c, down(wits->key_off, d_koff, 8 * (size_t)W));
-    HIPCHK(c, down(wits->sig_off, d_soff, 8 * (size_t)W));
-    HIPCHK(c, down(wits->ok, d_ok, (size_t)W));
-    HIPCHK(c, down(wits->key_hash, d_kh, 28 * (size_t)W));
+  if (want_w) {
+    const int rw = praos_impl::txw_rows_down_wits(c, wits, R);
+    if (rw != PRAOS_OK) return rw;
   }
   HIPCHK(c, hipStreamSynchronize(s));
   return PRAOS_OK;

@@ -11,6 +11,7 @@
 // decodeListLen / decodeWord8 / decodeTag accept non-shortest forms); lists and the byte string
 // must be definite; the tag must be 24.  Plain integers only: k_wire.hip includes the file for
 // the device and g++ compiles it for the host tests (tests/test_wire_host.py).
+// gen_tx_unwrap, below it, is the same for a transaction (k_gentx.hip, tests/test_gentx_host.py).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -76,6 +77,44 @@ WIRE_HD Item wire_unwrap(const uint8_t* a, uint64_t arena_len, uint64_t pos, uin
     if (!head(c, 0, hint) || hint > 0xffffffffull) return r;
     r.byron_kind = (uint8_t)kind;
     r.size_hint = (uint32_t)hint;
+  }
+  if (!head(c, 6, v) || v != 24) return r;
+  if (!head(c, 2, v) || v > c.end - c.p) return r;
+  r.off = c.p;
+  r.len = (uint32_t)v;
+  r.status = c.p + v == c.end ? OK : TRAILING;
+  return r;
+}
+
+// praos_hip.h PRAOS_GTX_BYRON
+constexpr uint8_t GTX_BYRON = 6;
+
+// The node-to-node wrapper of a transaction (GenTx), as the TxSubmission server receives it.
+//   Shelley-based eras   [eraIndex, #6.24(bytes)]   (decodeNS; Shelley/Ledger/Mempool.hs:186-193)
+//   Byron (era 0)        [0, [kind, payload]]       (Byron/Ledger/Mempool.hs encodeByronGenTx:
+//                        kind 0 tx, 1 delegation certificate, 2 update proposal, 3 update vote)
+// The same rules as wire_unwrap for the heads.  A Byron item is GTX_BYRON with byron_kind set and
+// (off, len) its payload: every byte after the kind up to the end of the item, at least one (what
+// they hold is not looked at); any other era-0 form is SYNTAX.  size_hint stays 0.
+WIRE_HD Item gen_tx_unwrap(const uint8_t* a, uint64_t arena_len, uint64_t pos, uint64_t len, uint32_t n_eras) {
+  Item r{SYNTAX, 0xff, NOT_BYRON, 0u, 0ull, 0u};
+  if (pos > arena_len || len > arena_len - pos) { r.status = RANGE; return r; }
+  Cur c{a, pos, pos + len};
+  uint64_t v;
+  if (!head(c, 4, v) || v != 2) return r;
+  if (!head(c, 0, v) || v > 0xff) return r;           // decodeWord8
+  r.era = (uint8_t)v;
+  if (v >= n_eras) { r.status = ERA; return r; }
+  if (v == 0) {
+    uint64_t kind;
+    if (!head(c, 4, v) || v != 2) return r;
+    if (!head(c, 0, kind) || kind > 3) return r;
+    if (c.p >= c.end || c.end - c.p > 0xffffffffull) return r;
+    r.byron_kind = (uint8_t)kind;
+    r.off = c.p;
+    r.len = (uint32_t)(c.end - c.p);
+    r.status = GTX_BYRON;
+    return r;
   }
   if (!head(c, 6, v) || v != 24) return r;
   if (!head(c, 2, v) || v > c.end - c.p) return r;

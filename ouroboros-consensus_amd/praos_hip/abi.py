@@ -256,6 +256,33 @@ class TxwWits(ctypes.Structure):
                                                                           for name, dt, _ in TXW_WIT_FIELDS]
 
 
+# TxSubmission transactions: wire GenTxs, each checked once (praos_verify_gen_txs)
+GTX_SHAPE, GTX_BYRON, GTX_PER_TX_OVERHEAD, GTX_NO_ROW = 5, 6, 4, 0xFFFFFFFF
+GTX_ITEM_FIELDS = (  # name, dtype (praos_gtx_items)
+    ("status", np.uint8), ("era", np.uint8), ("row", np.uint32), ("byron_kind", np.uint8),
+    ("payload_off", np.uint64), ("payload_len", np.uint32))
+GTX_TX_FIELDS = (  # name, dtype, record shape (praos_gtx_txs; wit_first has cap + 1 entries)
+    ("item", np.uint32, ()), ("era", np.uint8, ()), ("body_off", np.uint64, ()), ("body_len", np.uint32, ()),
+    ("wit_off", np.uint64, ()), ("wit_len", np.uint32, ()), ("aux_off", np.uint64, ()), ("aux_len", np.uint32, ()),
+    ("size", np.uint32, ()), ("in_block_size", np.uint32, ()), ("ex_mem", np.uint64, ()), ("ex_steps", np.uint64, ()),
+    ("is_valid", np.uint8, ()), ("tx_id", np.uint8, (32,)), ("wstatus", np.uint8, ()), ("n_vkey", np.uint32, ()),
+    ("n_boot", np.uint32, ()), ("n_bad", np.uint32, ()), ("wit_first", np.uint64, ()))
+
+
+class GtxCfg(ctypes.Structure):
+    _fields_ = [("n_eras", ctypes.c_uint32), ("dedup", ctypes.c_uint32), ("max_lanes", ctypes.c_uint32),
+                ("pad_", ctypes.c_uint32)]
+
+
+class GtxItems(ctypes.Structure):
+    _fields_ = [(name, _CT[dt]) for name, dt in GTX_ITEM_FIELDS]
+
+
+class GtxTxs(ctypes.Structure):
+    _fields_ = [("cap", ctypes.c_size_t), ("n_rows", ctypes.c_size_t)] + [(name, _CT[dt])
+                                                                          for name, dt, _ in GTX_TX_FIELDS]
+
+
 # Byron blocks: further PRAOS_BLK_* bits and the failing body comparisons (PRAOS_BYRON_W_*)
 BLK_PBFT_SIG, BLK_PM = 0x08, 0x10
 BYRON_W_DLG, BYRON_W_UPD, BYRON_W_NTX, BYRON_W_WIT, BYRON_W_ROOT = 0x01, 0x02, 0x04, 0x08, 0x10
@@ -469,6 +496,8 @@ SIGNATURES = {
     "praos_verify_tx_witnesses": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HeaderBytes), ctypes.POINTER(TxwCfg),
                                                  ctypes.POINTER(TxwBlocks), ctypes.POINTER(TxwTxs),
                                                  ctypes.POINTER(TxwWits)]),
+    "praos_verify_gen_txs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HeaderBytes), ctypes.POINTER(GtxCfg),
+                                            ctypes.POINTER(GtxItems), ctypes.POINTER(GtxTxs), ctypes.POINTER(TxwWits)]),
     "praos_block_batch_tx_witnesses": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(TxwCfg),
                                                       ctypes.POINTER(TxwBlocks), ctypes.POINTER(TxwTxs),
                                                       ctypes.POINTER(TxwWits)]),
@@ -982,6 +1011,65 @@ class Context:
         return self._tx_witnesses(lambda cfg, bs, ts, ws: self.L.praos_block_batch_tx_witnesses(
             self.h, b, ctypes.byref(cfg), ctypes.byref(bs) if bs is not None else None, ctypes.byref(ts),
             ctypes.byref(ws)), n, byron, max_lanes, rows, cap, out)
+
+    # ---- TxSubmission: wire transactions, each distinct one checked once (k_gentx.hip) ----
+    def gen_tx_buffers(self, n, tx_cap, wit_cap, rows=True):
+        """Output arrays for verify_gen_txs(..., out=...): (items, txs, wits) dicts of n items,
+        tx_cap rows (wit_first: tx_cap + 1) and wit_cap witnesses; rows=False: the per-item arrays
+        only."""
+        I = {name: np.zeros(n, dt) for name, dt in GTX_ITEM_FIELDS}
+        if not rows:
+            return I, {}, {}
+        T = {name: np.zeros((tx_cap + 1 if name == "wit_first" else tx_cap,) + shp, dt)
+             for name, dt, shp in GTX_TX_FIELDS}
+        W = {name: np.zeros((wit_cap,) + shp, dt) for name, dt, shp in TXW_WIT_FIELDS}
+        return I, T, W
+
+    def verify_gen_txs(self, arena, off, length, n_eras=7, dedup=True, max_lanes=0, rows=True, cap=None, out=None):
+        """The wire transactions arena[off[i]:off[i]+len[i]] (GenTxs in the node-to-node encoding)
+        unwrapped, the distinct ones indexed and their key witnesses checked over their txId
+        (praos_verify_gen_txs).  Returns (items, txs, wits, (n_rows, n_wits)): dicts of per-item
+        (GTX_ITEM_FIELDS), per-distinct-transaction (GTX_TX_FIELDS) and per-witness
+        (TXW_WIT_FIELDS, tx = the row) arrays; rows=False: the per-item arrays only.  dedup:
+        byte-identical transactions of the same era share a row.  cap: (row, witness) capacities
+        (default: sized by a first call); smaller ones raise PraosError with .needed and .items
+        set.  max_lanes: witnesses per launch (0: default).  out: gen_tx_buffers of the same n,
+        written again in place (a caller verifying batch after batch into its own arrays)."""
+        arena, off, length = self._chunk(arena, off, length)
+        hb = self.header_bytes_struct(arena, off, length)
+        n = len(off)
+        cfg = GtxCfg(n_eras, 1 if dedup else 0, max_lanes, 0)
+
+        def call(it, ts, ws):
+            return self.L.praos_verify_gen_txs(self.h, ctypes.byref(hb), ctypes.byref(cfg),
+                                               ctypes.byref(it) if it is not None else None, ctypes.byref(ts),
+                                               ctypes.byref(ws))
+        if out is None and rows and cap is None:
+            ts, ws = GtxTxs(), TxwWits()
+            self.check(call(None, ts, ws))
+            cap = (int(ts.n_rows), int(ws.n_wits))
+        I, T, W = out if out is not None else self.gen_tx_buffers(n, *(cap or (0, 0)), rows=rows)
+        it, ts, ws = GtxItems(), GtxTxs(), TxwWits()
+        for name, dt in GTX_ITEM_FIELDS:
+            setattr(it, name, ptr(I[name], _CT[dt]))
+        if T:
+            ts.cap = len(T["item"])
+            for name, dt, _ in GTX_TX_FIELDS:
+                setattr(ts, name, ptr(T[name], _CT[dt]))
+        if W:
+            ws.cap = len(W["tx"])
+            for name, dt, _ in TXW_WIT_FIELDS:
+                setattr(ws, name, ptr(W[name], _CT[dt]))
+        rc = call(it, ts, ws)
+        if rc == E_ARG and (T or W) and (ts.n_rows > ts.cap or ws.n_wits > ws.cap):
+            msg = self.L.praos_last_error(self.h)
+            err = PraosError(f"praos rc={rc}: {msg.decode() if msg else ''}")
+            err.needed, err.items = (int(ts.n_rows), int(ws.n_wits)), I
+            raise err
+        self.check(rc)
+        nt, nw = int(ts.n_rows), int(ws.n_wits)
+        return (I, {k: a[:nt + 1 if k == "wit_first" else nt] for k, a in T.items()},
+                {k: a[:nw] for k, a in W.items()}, (nt, nw))
 
     # ---- ImmutableDB chunk validation (k_crc32.hip, praos_validate_chunk) ----
     def crc32(self, arena, off, length):
