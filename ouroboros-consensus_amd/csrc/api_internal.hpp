@@ -1,9 +1,9 @@
 #pragma once
 // api_internal.hpp -- what the units of the host API share: the context and batch structs, the
 // staging pool, the allocation / error helpers and the functions that cross
-// unit boundaries (praos_impl).  Included by praos_api / praos_run / praos_fold / praos_debug /
-// praos_txindex / praos_txwit only; the other host modules (replay, group, candidates, pbft) go
-// through replay_internal.hpp.
+// unit boundaries (praos_impl).  Included by praos_api / praos_xfer / praos_blocks / praos_stream /
+// praos_run / praos_fold / praos_debug / praos_txindex / praos_txwit / praos_gentx only; the other
+// host modules (replay, group, candidates, pbft) go through replay_internal.hpp.
 #include "praos_hip.h"
 #include "launch.hpp"
 #include "host_util.hpp"
@@ -366,10 +366,7 @@ static constexpr uint32_t KC_MAX_ENTRIES = 1u << 20;   // a key used twice alrea
 
 #define HIPCHK(ctx, x)                                                                    \
   do {                                                                                    \
-    if ((ctx)->device < 0) {                                                              \
-      (ctx)->err = "host-only context: no HIP device";                                    \
-      return PRAOS_E_STATE;                                                               \
-    }                                                                                     \
+    if (praos_host_only_(ctx)) return PRAOS_E_STATE;                                      \
     hipError_t e_ = (x);                                                                  \
     if (e_ != hipSuccess) {                                                               \
       (ctx)->err = std::string(#x) + ": " + hipGetErrorString(e_);                        \
@@ -490,6 +487,85 @@ int txw_rows_down_wits(praos_ctx* c, praos_txw_wits* wits, const txw_rows& R);
 int ensure_bcomb16(praos_ctx* c);
 int batch_decode(praos_ctx* c, praos_batch* b);
 int32_t overlay_class(const praos_ctx* c, uint64_t slot);
+// k_decode_praos of headers [first, upto) into b's columns, from the device spans hoff / hlen into
+// arena, on st; the mode and the leader-certificate columns are the batch's
+void decode_launch(const praos_batch* b, hipStream_t st, const uint8_t* arena, size_t arena_len, const uint64_t* hoff,
+                   const uint32_t* hlen, size_t first, size_t upto);
+// device buffers of a from-bytes batch of n headers over an arena of bytes_len bytes
+// (owner == nullptr: fresh allocations, not taken from / given back to the spare list)
+praos_batch* bytes_batch_alloc(praos_ctx* c, size_t n, size_t bytes_len, bool tpraos, praos_ctx* owner);
+// arena upload of a from-bytes batch (zero padding for ld64u, then the bytes), on the ctx stream
+int arena_upload(praos_ctx* c, praos_batch* b, const uint8_t* bytes, size_t bytes_len);
+
+// praos_xfer.hip: the pinned staging buffers and the copies through them (h2d / d2h: on the ctx
+// stream; d2h_on and d2h return when the bytes are in dst)
+bool stage_init(praos_ctx* c);
+hipError_t zero_pad(praos_ctx* c, uint8_t* dst, size_t pad, hipStream_t st);
+hipError_t h2d_on(praos_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t st);
+hipError_t d2h_on(praos_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t st);
+hipError_t h2d(praos_ctx* c, void* dst, const void* src, size_t bytes);
+hipError_t d2h(praos_ctx* c, void* dst, const void* src, size_t bytes);
+hipError_t h2d_gather(praos_ctx* c, uint8_t* dst, const praos_span* sp, size_t ns, size_t total, hipStream_t st);
+
+// praos_stream.hip: what praos_close frees of the batches and calls the context keeps (the replay's
+// batches, the candidates' scratch, the pipeline's batches, events and pinned offsets)
+void stream_close(praos_ctx* c);
+
+// The columns a call downloads, each as f(host pointer, device pointer, bytes); a column the caller
+// left NULL is skipped, the first error ends the walk.  Outputs of a run:
+template <typename F>
+static hipError_t out_cols(const praos_out& o, const praos_batch& b, F&& f) {
+  const struct { void* h; const void* d; size_t w; } col[] = {
+      {o.bits, b.bits, 2}, {o.pool_idx, b.pool_idx, 4}, {o.beta, b.beta, 64}, {o.leader, b.leader, 32},
+      {o.nonce, b.nonce, 32}};
+  hipError_t e = hipSuccess;
+  for (const auto& x : col)
+    if (x.h && e == hipSuccess) e = f(x.h, x.d, x.w * b.n);
+  return e;
+}
+// ... and the decoded fields of a from-bytes batch:
+template <typename F>
+static hipError_t decoded_cols(const praos_decoded& d, const praos_batch& b, F&& f) {
+  const struct { void* h; const void* d; size_t w; } col[] = {
+      {d.status, b.dec_status, 2},   {d.block_no, b.block_no, 8},     {d.slot, b.slot, 8},
+      {d.prev_hash, b.prev_hash, 32}, {d.prev_is_genesis, b.prev_genesis, 1}, {d.cold_vk, b.cold_vk, 32},
+      {d.vrf_vk, b.vrf_vk, 32},      {d.vrf_out, b.vrf_out, 64},      {d.vrf_proof, b.vrf_proof, 80},
+      {d.body_size, b.body_size, 4}, {d.body_hash, b.body_hash, 32},  {d.hot_vk, b.hot_vk, 32},
+      {d.ocert_n, b.ocert_n, 8},     {d.ocert_c0, b.ocert_c0, 8},     {d.ocert_sig, b.ocert_sig, 64},
+      {d.prot_major, b.prot_major, 8}, {d.prot_minor, b.prot_minor, 8}, {d.kes_sig, b.kes_sig, 448},
+      {d.signed_len, b.body_len, 4}, {d.signed_body, b.body, b.signed_stride}, {d.header_hash, b.header_hash, 32}};
+  hipError_t e = hipSuccess;
+  for (const auto& x : col)
+    if (x.h && e == hipSuccess) e = f(x.h, x.d, x.w * b.n);
+  return e;
+}
+
+// A batch that a one-shot call borrows as the owner of its device allocations: on scope exit the
+// ctx stream is drained and the buffers go to the context's spare list (praos_batch_free).
+struct ScratchBatch {
+  praos_ctx* c;
+  praos_batch* b;
+  ScratchBatch(praos_ctx* c_, praos_batch* b_) : c(c_), b(b_) {}          // adopts an uploaded batch
+  ScratchBatch(praos_ctx* c_, size_t n) : c(c_), b(new praos_batch()) {
+    b->owner = c;
+    b->n = n;
+  }
+  ScratchBatch(const ScratchBatch&) = delete;
+  ScratchBatch& operator=(const ScratchBatch&) = delete;
+  ~ScratchBatch() {
+    (void)hipStreamSynchronize(c->stream);
+    praos_batch_free(c, b);
+  }
+};
+
+// the device's nonce table: 9 words per entry (nonce, neutral flag)
+static inline void pack_nonce_table(const praos_nonce* etas, uint32_t k, uint32_t* out36) {
+  std::memset(out36, 0, 36 * (size_t)k);
+  for (uint32_t e = 0; e < k; e++) {
+    if (!etas[e].neutral) std::memcpy(out36 + 9 * e, etas[e].hash, 32);
+    out36[9 * e + 8] = etas[e].neutral ? 1u : 0u;
+  }
+}
 
 // praos_run.hip: the key-cache prepass (hash set, entries, hit / miss lists), the entries' key
 // tables, and the crypto step's stream scheduler

@@ -3,7 +3,8 @@
 //     distribution (praos_apply_batch needs hashKey for the counter map,
 //     Praos.hs:595-606);
 //   * x = -(fromRational sigma * c) in Fixed E34 (checkLeaderNatValue's x,
-//     precomputed once per pool and epoch).
+//     precomputed once per pool and epoch);
+//   * the room and the zero pad of a device arena of stored bytes.
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -165,3 +166,15 @@ inline bool nonce_eq(const praos_nonce& a, const praos_nonce& b) {
 }
 
 }  // namespace praos_host
+
+// A device arena of `bytes` stored bytes: ld64u (arena.hpp) reads whole 64-bit words up to 16 bytes
+// past the last byte, so the allocation is the bytes rounded up to 8 plus 16, and the pad behind
+// the bytes is zeroed.
+inline size_t arena_room(size_t bytes) { return ((bytes + 7) & ~(size_t)7) + 16; }
+inline size_t arena_pad(size_t bytes) { return arena_room(bytes) - bytes; }
+// the first of n spans that does not lie inside an arena of bytes_len bytes (n: every span does)
+inline size_t first_bad_span(const uint64_t* off, const uint32_t* len, size_t n, uint64_t bytes_len) {
+  size_t i = 0;
+  while (i < n && off[i] <= bytes_len && len[i] <= bytes_len - off[i]) i++;
+  return i;
+}

@@ -121,7 +121,7 @@ bool frag_bounds_ok(const size_t* frag_first, size_t k, bool have_frags, size_t 
 // a device, an epoch where the call needs one, and no stored-bytes call in flight on the
 // context's streams
 int front_begin(praos_ctx* c, bool need_epoch) {
-  if (rp_device(c) < 0) { praos_set_error_(c, "host-only context: no HIP device"); return PRAOS_E_STATE; }
+  if (praos_host_only_(c)) return PRAOS_E_STATE;
   if (need_epoch && !rp_have_epoch(c)) { praos_set_error_(c, "candidates: no epoch installed (praos_set_epoch)"); return PRAOS_E_STATE; }
   return praos_verify_drain(c);
 }
@@ -149,7 +149,7 @@ int front_run(praos_ctx* c, const praos_header_bytes& items, uint32_t n_eras, ui
   const size_t nb = (N + NT_ITEMS - 1) / NT_ITEMS;
   // one device buffer, kept with the context between calls: the wire arena (with ld64u's pad), the
   // item buffers, the dedup's arrays and the rows' spans and kinds (at most N rows)
-  const size_t arena_sz = ((bytes + 7) & ~(size_t)7) + 16;
+  const size_t arena_sz = arena_room(bytes);
   Carve m;
   m.size = Carve::up(arena_sz) + ItemBufs::bytes(N) + 4 * Carve::up(4 * N) + Carve::up(4 * nb) + Carve::up(4) +
            2 * Carve::up(4 * (size_t)tab) + Carve::up(8 * N) + Carve::up(4 * N) + Carve::up(N);
@@ -203,12 +203,12 @@ extern "C" int praos_unwrap_wire_headers(praos_ctx* c, const praos_header_bytes*
     praos_set_error_(c, "unwrap: status, era, byron_kind, size_hint, off and len are required");
     return PRAOS_E_ARG;
   }
-  if (rp_device(c) < 0) { praos_set_error_(c, "host-only context: no HIP device"); return PRAOS_E_STATE; }
+  if (praos_host_only_(c)) return PRAOS_E_STATE;
   if (n == 0) return PRAOS_OK;
   CHIP(c, hipSetDevice(rp_device(c)));
   hipStream_t st = rp_copy_stream(c);
   Carve m;
-  const size_t arena_sz = ((bytes + 7) & ~(size_t)7) + 16;     // ld64u's pad (arena.hpp)
+  const size_t arena_sz = arena_room(bytes);     // ld64u's pad (arena.hpp)
   m.size = Carve::up(arena_sz) + ItemBufs::bytes(n);
   CHIP(c, hipMalloc((void**)&m.base, m.size));
   m.own = true;

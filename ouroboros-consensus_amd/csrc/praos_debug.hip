@@ -639,10 +639,10 @@ int praos_debug_hash_bytes(praos_ctx* c, int kind, size_t n, const uint8_t* aren
     for (size_t i = 0; i < n && kind == 2; i++)
       if (aux[i] > 4) return bad("more than 4 segments, block", i);
   }
-  if (c->device < 0) { c->err = "host-only context: no HIP device"; return PRAOS_E_STATE; }
+  if (praos_host_only_(c)) return PRAOS_E_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   // the arena as arena_upload leaves it: the bytes, then zeros to the next multiple of 8 and 16 more
-  const size_t padded = ((arena_len + 7) & ~(size_t)7) + 16;
+  const size_t padded = arena_room(arena_len);
   std::vector<uint8_t> host(padded, 0);
   if (arena_len) std::memcpy(host.data(), arena, arena_len);
   Scratch s(c);
@@ -680,7 +680,7 @@ int praos_debug_int(praos_ctx* c, int op, size_t n, const uint8_t* a, const uint
     std::memcpy(&k, b + 32 * i, 4);
     if (k < 2 || k >= 65536) return bad("divisor outside 2..65535, item " + std::to_string(i));
   }
-  if (c->device < 0) { c->err = "host-only context: no HIP device"; return PRAOS_E_STATE; }
+  if (praos_host_only_(c)) return PRAOS_E_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   Scratch s(c);
   auto da = s.up(a, 32 * n);

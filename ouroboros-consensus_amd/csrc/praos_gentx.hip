@@ -30,7 +30,7 @@ int gtx_run(praos_ctx* c, const praos_header_bytes* in, const praos_gtx_cfg* cfg
   uint32_t tab = 2;
   while (tab < 2 * n) tab <<= 1;
   const size_t nb = (n + NT - 1) / NT, ns = std::max<size_t>(tab, n);
-  const size_t arena_sz = ((bytes + 7) & ~(size_t)7) + 16;     // ld64u's pad (arena.hpp)
+  const size_t arena_sz = arena_room(bytes);     // ld64u's pad (arena.hpp)
   uint8_t* arena = nullptr;
   uint64_t* d_off = nullptr;
   uint32_t* d_len = nullptr;
@@ -198,7 +198,7 @@ extern "C" int praos_verify_gen_txs(praos_ctx* c, const praos_header_bytes* item
   if (cfg->n_eras < 1 || cfg->n_eras > 32) { c->err = "praos_verify_gen_txs: n_eras must be 1..32"; return PRAOS_E_ARG; }
   if (items->n && (!items->off || !items->len || (items->bytes_len && !items->bytes))) return PRAOS_E_ARG;
   if (items->n > 0x7fffffffull) { c->err = "praos_verify_gen_txs: too many items in one call"; return PRAOS_E_ARG; }
-  if (c->device < 0) { c->err = "host-only context: no HIP device"; return PRAOS_E_STATE; }
+  if (praos_host_only_(c)) return PRAOS_E_STATE;
   if (txs) txs->n_rows = 0;
   if (wits) wits->n_wits = 0;
   if (items->n == 0) {

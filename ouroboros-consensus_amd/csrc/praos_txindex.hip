@@ -238,7 +238,7 @@ int praos_block_batch_tx_index(praos_ctx* c, praos_batch* b, const praos_txi_cfg
 int praos_index_block_txs(praos_ctx* c, const praos_header_bytes* blocks, const praos_txi_cfg* cfg,
                           praos_txi_stats* stats, praos_txi_rows* rows) {
   if (!c || !blocks || !cfg) return PRAOS_E_ARG;
-  if (c->device < 0) { c->err = "host-only context: no HIP device"; return PRAOS_E_STATE; }
+  if (praos_host_only_(c)) return PRAOS_E_STATE;
   if (blocks->n == 0) {
     if (rows) rows->n_rows = 0;
     if (stats && stats->tx_first) stats->tx_first[0] = 0;

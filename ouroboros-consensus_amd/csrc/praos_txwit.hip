@@ -228,7 +228,7 @@ int praos_block_batch_tx_witnesses(praos_ctx* c, praos_batch* b, const praos_txw
 int praos_verify_tx_witnesses(praos_ctx* c, const praos_header_bytes* blocks, const praos_txw_cfg* cfg,
                               praos_txw_blocks* blocks_out, praos_txw_txs* txs, praos_txw_wits* wits) {
   if (!c || !blocks || !cfg) return PRAOS_E_ARG;
-  if (c->device < 0) { c->err = "host-only context: no HIP device"; return PRAOS_E_STATE; }
+  if (praos_host_only_(c)) return PRAOS_E_STATE;
   if (blocks->n == 0) {
     if (txs) txs->n_rows = 0;
     if (wits) wits->n_wits = 0;

@@ -9,11 +9,13 @@
 #include <string>
 #include <vector>
 
-// The context for the other host modules (praos_api.hip): its error text; the replay call scope
-// (first error kept, pool-key store on); the group's page-locked ranges (praos_group_host_register:
-// pinned once, known to every member); the staging copy threads onto the given CPUs (empty: back to
-// the process's own mask).
+// The context for the other host modules (praos_api.hip): its error text; the refusal of a call
+// that needs a device (true on a host-only context, with the error text set); the replay call scope
+// (first error kept, pool-key store on); and in praos_xfer.hip the group's page-locked ranges
+// (praos_group_host_register: pinned once, known to every member) and the staging copy threads onto
+// the given CPUs (empty: back to the process's own mask).
 void praos_set_error_(praos_ctx* c, const std::string& m);
+bool praos_host_only_(praos_ctx* c);
 void praos_replay_scope_(praos_ctx* c, bool on);
 int praos_ctx_note_registered_(praos_ctx* c, void* p, size_t len, bool add);
 void rp_copy_pin(praos_ctx* c, const std::vector<int>& cpus);
@@ -27,6 +29,7 @@ struct praos_span {           // a run of stored bytes in host memory (e.g. an m
   size_t len;
 };
 
+// (praos_stream.hip, down to rp_download_leader but for the ledger views)
 // A persistent from-bytes batch with room for n_cap headers over bytes_cap stored bytes, its
 // own events and pinned host buffers for the nonce table.
 praos_batch* rp_batch_alloc(praos_ctx* c, size_t n_cap, size_t bytes_cap, bool tpraos);
@@ -104,7 +107,7 @@ int rp_decode_rows(praos_ctx* c, praos_batch* b, const uint8_t* arena, size_t ar
 // after its run
 int rp_download_leader(praos_ctx* c, praos_batch* b, uint8_t* leader_out, uint8_t* leader_proof);
 // The Byron candidates call: praos_verify_pbft_headers' body over n > 0 rows already on the device
-// (praos_api.hip: spans into an arena with ld64u's pad behind it and two bytes in front of every
+// (praos_blocks.hip: spans into an arena with ld64u's pad behind it and two bytes in front of every
 // span, is_ebb flags; all final before the call), and the ChainSync client's mode of the PBFT fold
 // (praos_pbft.hip): item i reads row map[i] (PRAOS_NO_ROW: PRAOS_V_INPUT) of h and row_is_ebb,
 // PRAOS_V_DOESNT_FIT before the envelope, the fold ends at the first failure (*processed = items

@@ -271,6 +271,68 @@ def test_submitted_bytes_equal_blocking(ctx, c5_batch, chunk_v, monkeypatch):
             ctx.close()
 
 
+def test_staged_copies_reuse_pinned_buffers(ctx, c5_batch):
+    """Staged copies of more than two 16 MB pieces, so that both directions come back to a pinned
+    buffer they have used (piece 2 on buffer 0): c5_batch tiled four times is about 80,000 headers
+    over a 70 MB arena (five upload pieces) with 36 MB of decoded KES signatures (three download
+    pieces).  One span lies outside the arena and the last one is cut short with the arena, whose
+    length is then no multiple of 8.  The input runs as one blocking batch (h2d / d2h), as the
+    blocking pipeline in 3 chunks (h2d_on, d2h_on on the copy stream) and submitted then drained
+    (d2h_on on the download stream), from pageable buffers and with the arena and every output of
+    at least 1 MB page-locked (direct DMA): every output and decoded array is the same bit for bit,
+    and every decoded array is the tiling of what the untiled batch decodes to."""
+    from praos_hip import abi
+    cfg, H, pool_list, corrupted, p, arena, off, ln = c5_batch
+    T, A, n1, cut, bad = 4, len(arena), len(off), 5, 5000
+    end = int(off[-1]) + int(ln[-1])                 # the arena ends inside the last span
+
+    def damaged(k):                                   # k tiles; the damage is in the last one
+        a = np.tile(arena, k)[:(k - 1) * A + end - cut]
+        o = np.concatenate([off + np.uint64(t * A) for t in range(k)])
+        l_ = np.tile(ln, k)
+        o[(k - 1) * n1 + bad] = k * A + 100           # out of range
+        l_[-1] -= cut
+        return a, o, l_
+
+    arena_t, off_t, ln_t = damaged(T)
+    n = len(off_t)
+    assert arena_t.nbytes > 4 * (16 << 20) and 448 * n > 2 * (16 << 20)
+    ctx.set_epoch(cfg["eta0"], pool_list, p)
+    runs = []
+    try:
+        ctx.set_option(abi.OPT_PIPELINE, 1)
+        D_clean = ctx.verify_header_bytes(arena, off, ln, decoded=True)[1]
+        D_dmg = ctx.verify_header_bytes(*damaged(1), decoded=True)[1]
+        runs.append(ctx.verify_header_bytes(arena_t, off_t, ln_t, decoded=True))
+        ctx.set_option(abi.OPT_PIPELINE, 3)
+        runs.append(ctx.verify_header_bytes(arena_t, off_t, ln_t, decoded=True))
+        for locked in (False, True):
+            o, d = ctx.alloc_out(n), ctx.alloc_decoded(n)
+            bufs = [arena_t] + [v for v in list(o.values()) + list(d[0].values()) if v.nbytes >= (1 << 20)]
+            for b_ in bufs if locked else []:
+                ctx.host_register(b_)
+            try:
+                ctx.submit_header_bytes(arena_t, off_t, ln_t, out=o, decoded=d)
+                ctx.drain()
+            finally:
+                for b_ in bufs if locked else []:
+                    ctx.host_unregister(b_)
+            runs.append((o, d[0]))
+    finally:
+        ctx.drain()
+        ctx.set_option(abi.OPT_PIPELINE, 0)
+    o1, D1 = runs[0]
+    for j, (o, D) in enumerate(runs[1:], 1):
+        for k in o1:
+            assert np.array_equal(o1[k], o[k]), (j, k)
+        for k in D1:
+            assert np.array_equal(D1[k], D[k]), (j, k)
+    for k in D1:
+        assert np.array_equal(D1[k], np.concatenate([D_clean[k]] * (T - 1) + [D_dmg[k]])), k
+    assert D1["status"][(T - 1) * n1 + bad] & abi.DEC_RANGE and o1["bits"][(T - 1) * n1 + bad] & abi.BIT_INPUT
+    assert D1["status"][-1] & abi.DEC_FAILED
+
+
 @pytest.mark.parametrize("env,concurrent", [({"PRAOS_PRE_JOIN": "0"}, 1), ({"PRAOS_PRE_JOIN": "1"}, 1),
                                             ({"PRAOS_PRE_JOIN": "1"}, 0), ({"PRAOS_V_MAIN": "1"}, 1), ({"PRAOS_V_MAIN": "2"}, 1), ({"PRAOS_V_MAIN": "0"}, 1),
                                             ({"PRAOS_V_MAIN": "1", "PRAOS_PRE_JOIN": "0"}, 1),
