@@ -1,5 +1,7 @@
 // arena.hpp -- byte-arena loads and multi-block Blake2b-256 shared by the
-// stored-bytes kernels (k_decode.hip headers, k_block.hip block bodies).
+// stored-bytes kernels (k_decode.hip headers, k_block.hip block bodies, k_txindex.hip and
+// k_gentx.hip transaction bodies): per lane (b2b256_range) and staged through LDS by the
+// workgroup (b2b256_staged).
 // ld64u: 8 bytes at any offset as two aligned 8-byte loads + a funnel shift;
 // callers pad the arena by 16 bytes so the second load never leaves it.
 #pragma once
@@ -47,6 +49,17 @@ __device__ __forceinline__ void b2b_compress(uint64_t h[8], const uint64_t m[16]
   for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[i + 8];
 }
 
+__device__ __forceinline__ void b2b_init(uint64_t h[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) h[i] = B2B_IV[i];
+  h[0] ^= 0x01010000ULL ^ 32u;
+}
+// the 32-byte digest as little-endian words
+__device__ __forceinline__ void b2b_digest_words(uint32_t out[8], const uint64_t h[8]) {
+#pragma unroll
+  for (int i = 0; i < 4; i++) { out[2 * i] = (uint32_t)h[i]; out[2 * i + 1] = (uint32_t)(h[i] >> 32); }
+}
+
 // one 128-byte message block of p[pos, pos + len) starting at byte `base` (zero padded)
 __device__ __forceinline__ void b2b_load_block(uint64_t m[16], const uint8_t* __restrict__ p, uint64_t pos,
                                                uint64_t len, uint64_t base) {
@@ -67,7 +80,7 @@ __device__ __forceinline__ void b2b256_range(uint32_t out[8], const uint8_t* __r
                                              uint64_t len) {
   uint64_t h[8];
 #pragma unroll
-  for (int i = 0; i < 8; i++) h[i] = B2B_IV[i];
+  for (int i = 0; i < 8; i++) h[i] = B2B_IV[i];   // b2b_init, written out: see DESIGN section 34
   h[0] ^= 0x01010000ULL ^ 32u;
   const uint64_t nblk = len == 0 ? 1 : (len + 127) / 128;
   uint64_t nxt[16];
@@ -81,6 +94,71 @@ __device__ __forceinline__ void b2b256_range(uint32_t out[8], const uint8_t* __r
     const bool last = b + 1 == nblk;
     b2b_compress(h, m, last ? len : base + 128, last);
   }
+  b2b_digest_words(out, h);
+}
+
+// Blake2b-256 of arena[pos, pos + len) for every lane of a workgroup of NT lanes at once, with
+// the message blocks staged through LDS: a lane streaming its own bytes with per-lane 8-byte
+// loads touches 64 different cache lines per instruction and the L1 thrashes (each 128-byte
+// line is re-fetched from L2 for every word).  Here the workgroup loads the next 128-byte block
+// of all 256 messages cooperatively -- 8 lanes x 16 bytes per block, whole lines per
+// instruction -- into LDS (stride 17 words: 2-way bank conflicts at most), and each lane
+// compresses its own block from LDS.  The loop runs to the workgroup's longest message, so
+// callers put messages of similar length side by side.
+// Every lane of the workgroup must make the call (it holds barriers): a lane without a message
+// passes act = false and len = 0, so that it stages length 0, and gets no digest; a return ahead
+// of the call has to be uniform over the workgroup.  (The length is staged as passed: a select
+// on act here cost k_seg_hash 2.6 %)  At most one call per kernel (the LDS
+// tile is declared here).
+constexpr uint32_t B2B_STRIDE = 17;   // u64 words per staged block (16 + 1 pad)
+
+__device__ __forceinline__ void b2b256_staged(uint32_t out[8], const uint8_t* __restrict__ arena, bool act,
+                                              uint64_t pos, uint32_t len) {
+  __shared__ uint64_t sm[NT * B2B_STRIDE];
+  __shared__ uint64_t s_pos[NT];
+  __shared__ uint32_t s_len[NT];
+  __shared__ uint32_t s_max;
+  const uint32_t t = threadIdx.x;
+  const uint32_t nblk = act ? (len == 0 ? 1u : (len + 127u) / 128u) : 0u;
+  s_pos[t] = pos;
+  s_len[t] = len;
+  if (t == 0) s_max = 0;
+  __syncthreads();
+  if (nblk) atomicMax(&s_max, nblk);
+  __syncthreads();
+  const uint32_t nb = s_max;
+  uint64_t h[8];
+  b2b_init(h);
+  for (uint32_t b = 0; b < nb; b++) {
 #pragma unroll
-  for (int i = 0; i < 4; i++) { out[2 * i] = (uint32_t)h[i]; out[2 * i + 1] = (uint32_t)(h[i] >> 32); }
+    for (uint32_t r = 0; r < 8; r++) {
+      const uint32_t c = r * NT + t, owner = c >> 3, part = c & 7u;
+      const uint32_t olen = s_len[owner];
+      const uint64_t o = (uint64_t)b * 128 + 16 * part;
+      uint64_t w0 = 0, w1 = 0;
+      if (o < olen) {
+        const uint64_t opos = s_pos[owner];
+        w0 = ld64u(arena, opos + o);
+        if (o + 8 < olen) w1 = ld64u(arena, opos + o + 8);
+      }
+      sm[owner * B2B_STRIDE + 2 * part] = w0;
+      sm[owner * B2B_STRIDE + 2 * part + 1] = w1;
+    }
+    __syncthreads();
+    if (b < nblk) {
+      uint64_t m[16];
+      const uint64_t base = (uint64_t)b * 128;
+#pragma unroll
+      for (int k = 0; k < 16; k++) {
+        const uint64_t o = base + 8 * k;
+        uint64_t w = o < len ? sm[t * B2B_STRIDE + k] : 0;
+        if (o < len && len - o < 8) w &= (1ull << (8 * (len - o))) - 1;
+        m[k] = w;
+      }
+      const bool last = b + 1 == nblk;
+      b2b_compress(h, m, last ? (uint64_t)len : base + 128, last);
+    }
+    __syncthreads();
+  }
+  b2b_digest_words(out, h);
 }

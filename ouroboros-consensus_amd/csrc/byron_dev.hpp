@@ -1,40 +1,12 @@
 // byron_dev.hpp -- device helpers shared by the Byron kernels (k_byron.hip blocks, k_pbft.hip
-// headers): strict CBOR readers over a cursor, Blake2b-256 with a literal prefix, and the
-// 128-byte register streaming buffer of the SHA-512 / Blake2b-256 streams.
+// headers): Blake2b-256 with a literal prefix, and the 128-byte register streaming buffer of the
+// SHA-512 / Blake2b-256 streams.  The strict CBOR readers they parse with are cbor_dev.hpp's.
 #pragma once
 #include "kcommon.hpp"
 #include "arena.hpp"
 #include "cbor_dev.hpp"
 
 namespace {
-
-__device__ __forceinline__ bool rd_uint(Cur& c, uint64_t limit, uint64_t& v) {
-  uint32_t mt, ai;
-  bool indef;
-  return head(c, mt, ai, v, indef) && mt == 0 && v <= limit;
-}
-__device__ __forceinline__ bool rd_list(Cur& c, uint64_t n) {
-  uint32_t mt, ai;
-  uint64_t arg;
-  bool indef;
-  return head(c, mt, ai, arg, indef) && mt == 4 && !indef && arg == n;
-}
-// a definite byte string of exactly n bytes; at = offset of the raw bytes
-__device__ __forceinline__ bool rd_bytes(Cur& c, uint64_t n, uint64_t& at) {
-  uint32_t mt, ai;
-  uint64_t arg;
-  bool indef;
-  if (!(head(c, mt, ai, arg, indef) && mt == 2 && !indef && arg == n && n <= c.end - c.p)) return false;
-  at = c.p;
-  c.p += n;
-  return true;
-}
-
-__device__ __forceinline__ void b2b_init(uint64_t h[8]) {
-#pragma unroll
-  for (int i = 0; i < 8; i++) h[i] = B2B_IV[i];
-  h[0] ^= 0x01010000ULL ^ 32u;
-}
 
 // Blake2b-256 of (npre <= 2 literal bytes, the low bytes of pre) || a[pos, pos + len): the range
 // a[pos - npre, pos + len) with its first bytes replaced, so pos >= npre must hold (a Byron
@@ -52,8 +24,7 @@ __device__ void b2b256_pre(uint32_t out[8], const uint8_t* __restrict__ a, uint6
     const bool last = b + 1 == nblk;
     b2b_compress(h, m, last ? tot : 128 * b + 128, last);
   }
-#pragma unroll
-  for (int i = 0; i < 4; i++) { out[2 * i] = (uint32_t)h[i]; out[2 * i + 1] = (uint32_t)(h[i] >> 32); }
+  b2b_digest_words(out, h);
 }
 
 __device__ __forceinline__ void ld_bytes32(uint32_t w[8], const uint8_t* __restrict__ a, uint64_t pos) {

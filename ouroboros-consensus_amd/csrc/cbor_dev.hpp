@@ -1,7 +1,9 @@
-// cbor_dev.hpp -- the device-side CBOR item walk shared by the stored-block kernels
-// (k_block.hip, k_byron.hip): item heads and the skip over one well-formed item, the rules
-// of the oracle's block_integrity.cbor_skip.  Include inside the module's namespace-free
-// scope; everything here has internal linkage.
+// cbor_dev.hpp -- the device-side CBOR item walk shared by the stored-bytes kernels
+// (k_block.hip, k_byron.hip, k_pbft.hip, k_wire.hip, k_txindex.hip, k_txwit.hip, k_gentx.hip):
+// item heads and the skip over one well-formed item, the rules of the oracle's
+// block_integrity.cbor_skip; the strict readers of one item of a given form; and the walk of
+// one level of an array or a map, definite or indefinite (Lvl: open*, more, shut).  Include
+// inside the module's namespace-free scope; everything here has internal linkage.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -136,6 +138,86 @@ __device__ bool cbor_skip_regs(Cur& c) {
     }
   }
   return true;
+}
+
+// ---- strict readers: one item of exactly the given form
+__device__ __forceinline__ bool rd_uint(Cur& c, uint64_t limit, uint64_t& v) {
+  uint32_t mt, ai;
+  bool indef;
+  return head(c, mt, ai, v, indef) && mt == 0 && v <= limit;
+}
+__device__ __forceinline__ bool rd_list(Cur& c, uint64_t n) {
+  uint32_t mt, ai;
+  uint64_t arg;
+  bool indef;
+  return head(c, mt, ai, arg, indef) && mt == 4 && !indef && arg == n;
+}
+// a definite byte string of exactly n bytes; at = offset of the raw bytes
+__device__ __forceinline__ bool rd_bytes(Cur& c, uint64_t n, uint64_t& at) {
+  uint32_t mt, ai;
+  uint64_t arg;
+  bool indef;
+  if (!(head(c, mt, ai, arg, indef) && mt == 2 && !indef && arg == n && n <= c.end - c.p)) return false;
+  at = c.p;
+  c.p += n;
+  return true;
+}
+
+// ---- the level walker: an array or a map, definite or indefinite, item by item
+// one level of an array or a map: items (pairs) left, or indefinite
+struct Lvl {
+  uint64_t left;
+  bool indef;
+};
+
+__device__ __forceinline__ bool open_any(Cur& c, uint32_t& mt, Lvl& l) {
+  uint32_t ai;
+  uint64_t arg;
+  bool indef;
+  if (!head(c, mt, ai, arg, indef)) return false;
+  l.left = arg;
+  l.indef = indef;
+  return true;
+}
+__device__ __forceinline__ bool open(Cur& c, uint32_t want, Lvl& l) {
+  uint32_t mt;
+  return open_any(c, mt, l) && mt == want;
+}
+// an array of exactly k items (a definite head says so; an indefinite one is checked by shut)
+__device__ __forceinline__ bool open_k(Cur& c, uint64_t k, Lvl& l) {
+  return open(c, 4, l) && (l.indef || l.left == k);
+}
+__device__ __forceinline__ bool shut(Cur& c, const Lvl& l) {
+  if (!l.indef) return true;
+  if (c.p >= c.end || c.a[c.p] != 0xFF) return false;
+  c.p++;
+  return true;
+}
+// another item (pair) at this level?  Consumes the break of an indefinite level.
+__device__ __forceinline__ bool more(Cur& c, Lvl& l, bool& ok) {
+  if (l.indef) {
+    if (c.p >= c.end) { ok = false; return false; }
+    if (c.a[c.p] == 0xFF) { c.p++; return false; }
+    return true;
+  }
+  if (l.left == 0) return false;
+  l.left--;
+  return true;
+}
+
+// items of the array at c (count only; c is left inside a definite array)
+__device__ bool count_array(Cur& c, uint64_t& cnt) {
+  Lvl l;
+  if (!open(c, 4, l)) return false;
+  if (!l.indef) { cnt = l.left; return true; }
+  bool ok = true;
+  uint64_t k = 0;
+  while (more(c, l, ok)) {
+    if (!cbor_skip_regs(c)) return false;
+    k++;
+  }
+  cnt = k;
+  return ok;
 }
 
 }  // namespace

@@ -3,7 +3,7 @@
 // System.FS.CRC; parseChunkFile's checkEntries compares it per block).
 //
 // Spans run from ~800 B to ~90 KB, so one lane per span is out (serial,
-// uncoalesced, imbalanced; see the note above k_seg_hash).  Instead every span
+// uncoalesced, imbalanced; see the note above arena.hpp's b2b256_staged).  Instead every span
 // is cut into tiles of CRC_TILE bytes counted from its start; the host's prefix
 // sum of the tile counts (tile_first) maps a workgroup to (span, tile).
 //   k_crc32_tiles  one workgroup per tile.  A tile is CRC_ROWS rows of NT * 16

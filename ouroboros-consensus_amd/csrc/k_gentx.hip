@@ -11,7 +11,8 @@
 //   k_gtx_rep     row_item[row] = the representative item of each provisional row.
 //   k_gtx_rows    one lane per provisional row: the body is a map; for eras >= 4 the witness set's
 //                 first key 5 (ex_mem, ex_steps, both redeemer forms); tx_id = Blake2b-256 of the
-//                 body with the message blocks staged through LDS as k_txi_final stages them.
+//                 body with the message blocks staged through LDS (arena.hpp b2b256_staged, as
+//                 k_txi_final).
 //   k_gtx_final   one lane per index, in two roles: as a provisional row that stayed, its fields
 //                 gathered to its final row; as an item, its final row -- or PRAOS_GTX_SHAPE and no
 //                 row when k_gtx_rows refused its transaction.
@@ -19,53 +20,12 @@
 // are latency-bound and short beside the verifies.
 // CPU restatement: tests/gentx_model.py.
 #include "byron_dev.hpp"
+#include "tx_dev.hpp"
 #include "wire_scan.hpp"
 
 namespace {
 
 constexpr uint32_t NONE = 0xffffffffu;
-
-// one level of an array or a map, as k_txindex.hip walks them (its helpers are local to it)
-struct Lvl {
-  uint64_t left;
-  bool indef;
-};
-
-__device__ __forceinline__ bool open_any(Cur& c, uint32_t& mt, Lvl& l) {
-  uint32_t ai;
-  uint64_t arg;
-  bool indef;
-  if (!head(c, mt, ai, arg, indef)) return false;
-  l.left = arg;
-  l.indef = indef;
-  return true;
-}
-__device__ __forceinline__ bool open_k(Cur& c, uint64_t k, Lvl& l) {
-  uint32_t mt;
-  return open_any(c, mt, l) && mt == 4 && (l.indef || l.left == k);
-}
-__device__ __forceinline__ bool shut(Cur& c, const Lvl& l) {
-  if (!l.indef) return true;
-  if (c.p >= c.end || c.a[c.p] != 0xFF) return false;
-  c.p++;
-  return true;
-}
-// another item (pair) at this level?  Consumes the break of an indefinite level.
-__device__ __forceinline__ bool more(Cur& c, Lvl& l, bool& ok) {
-  if (l.indef) {
-    if (c.p >= c.end) { ok = false; return false; }
-    if (c.a[c.p] == 0xFF) { c.p++; return false; }
-    return true;
-  }
-  if (l.left == 0) return false;
-  l.left--;
-  return true;
-}
-__device__ __forceinline__ bool rd_u(Cur& c, uint64_t& v) {
-  uint32_t mt, ai;
-  bool indef;
-  return head(c, mt, ai, v, indef) && mt == 0;
-}
 
 __global__ void __launch_bounds__(NT) k_gtx_split(size_t n, const uint8_t* __restrict__ arena, uint64_t arena_len,
                                                   const uint64_t* __restrict__ off, const uint32_t* __restrict__ len,
@@ -147,78 +107,14 @@ __global__ void __launch_bounds__(NT) k_gtx_rep(size_t n, const uint32_t* __rest
   if (row < n) row_item[row] = (uint32_t)i;
 }
 
-// [mem, steps], both unsigned: the ExUnits of a redeemer
-__device__ __forceinline__ bool rd_exunits(Cur& c, uint64_t& mem, uint64_t& steps) {
-  Lvl x;
-  return open_k(c, 2, x) && rd_u(c, mem) && rd_u(c, steps) && shut(c, x);
-}
-
-// the value under key 5 of a witness set: [[tag, index, data, [mem, steps]], ...] or Conway's
-// {[tag, index]: [data, [mem, steps]], ...}; the sums mod 2^64 (k_txindex.hip's redeemer_steps
-// with the memory units kept)
-__device__ bool redeemer_units(Cur& c, uint64_t& mem_sum, uint64_t& steps_sum) {
-  uint32_t mt;
-  Lvl l;
-  if (!open_any(c, mt, l) || (mt != 4 && mt != 5)) return false;
-  bool ok = true;
-  uint64_t sm = 0, ss = 0;
-  while (ok && more(c, l, ok)) {
-    Lvl e;
-    uint64_t mem = 0, steps = 0;
-    if (mt == 4) {
-      ok = open_k(c, 4, e) && cbor_skip_regs(c) && cbor_skip_regs(c) && cbor_skip_regs(c) &&
-           rd_exunits(c, mem, steps) && shut(c, e);
-    } else {
-      ok = cbor_skip_regs(c) && open_k(c, 2, e) && cbor_skip_regs(c) && rd_exunits(c, mem, steps) && shut(c, e);
-    }
-    if (ok) { sm += mem; ss += steps; }
-  }
-  mem_sum = sm;
-  steps_sum = ss;
-  return ok;
-}
-
-// the value under the first unsigned key `want` of the map at c: found = false when there is
-// none or c is no map; c is left at the value
-__device__ bool find_key(Cur& c, uint64_t want, bool& found) {
-  found = false;
-  uint32_t mt;
-  Lvl m;
-  if (!open_any(c, mt, m)) return false;
-  if (mt != 5) return true;
-  bool ok = true;
-  while (ok && more(c, m, ok)) {
-    const uint64_t ks = c.p;
-    uint32_t kmt, ai;
-    uint64_t arg;
-    bool indef;
-    if (!head(c, kmt, ai, arg, indef)) return false;
-    if (kmt == 0 && arg == want) { found = true; return true; }
-    if (kmt > 1) {   // not an integer: the head alone is not the whole key
-      c.p = ks;
-      ok = cbor_skip_regs(c);
-    }
-    ok = ok && cbor_skip_regs(c);
-  }
-  return ok;
-}
-
-constexpr uint32_t GTX_STRIDE = 17;   // u64 words per staged message block (16 + 1 pad), as k_txi_final
-
-// Provisional rows [0, *total).  tx_id: the workgroup loads the next 128-byte block of its 256
-// bodies cooperatively (8 lanes x 16 bytes per body) into LDS and each lane compresses its own;
-// the loop runs to the workgroup's longest body.
+// Provisional rows [0, *total).  tx_id: the workgroup hashes its 256 bodies together
+// (b2b256_staged); its loop runs to the workgroup's longest body.
 __global__ void __launch_bounds__(NT) k_gtx_rows(size_t n, const uint32_t* __restrict__ total,
                                                  const uint8_t* __restrict__ arena,
                                                  const uint32_t* __restrict__ row_item, praos_gtx_dev_items d,
                                                  uint8_t* __restrict__ row_ok, uint64_t* __restrict__ ex_mem,
                                                  uint64_t* __restrict__ ex_steps, uint8_t* __restrict__ tx_id) {
-  __shared__ uint64_t sm[NT * GTX_STRIDE];
-  __shared__ uint64_t s_pos[NT];
-  __shared__ uint32_t s_len[NT];
-  __shared__ uint32_t s_max;
-  const uint32_t t = threadIdx.x;
-  const size_t p = (size_t)blockIdx.x * NT + t;
+  const size_t p = (size_t)blockIdx.x * NT + threadIdx.x;
   const size_t P = min((size_t)*total, n);
   bool act = false;
   uint64_t pos = 0;
@@ -235,7 +131,7 @@ __global__ void __launch_bounds__(NT) k_gtx_rows(size_t n, const uint32_t* __res
         const uint64_t wo = d.wit_off[i];
         Cur w{arena, wo, wo + d.wit_len[i], true};
         bool found;
-        ok = find_key(w, 5, found);
+        ok = find_key(w, 5, false, found);
         if (ok && found) ok = redeemer_units(w, mem, steps);
       }
       row_ok[p] = ok ? 1 : 0;
@@ -247,53 +143,9 @@ __global__ void __launch_bounds__(NT) k_gtx_rows(size_t n, const uint32_t* __res
       ex_steps[p] = 0;
     }
   }
-  const uint32_t nblk = act ? (len == 0 ? 1u : (len + 127u) / 128u) : 0u;
-  s_pos[t] = pos;
-  s_len[t] = act ? len : 0u;
-  if (t == 0) s_max = 0;
-  __syncthreads();
-  if (nblk) atomicMax(&s_max, nblk);
-  __syncthreads();
-  const uint32_t nb = s_max;
-  uint64_t h[8];
-#pragma unroll
-  for (int w = 0; w < 8; w++) h[w] = B2B_IV[w];
-  h[0] ^= 0x01010000ULL ^ 32u;
-  for (uint32_t b = 0; b < nb; b++) {
-#pragma unroll
-    for (uint32_t rr = 0; rr < 8; rr++) {
-      const uint32_t c = rr * NT + t, owner = c >> 3, part = c & 7u;
-      const uint32_t olen = s_len[owner];
-      const uint64_t off = (uint64_t)b * 128 + 16 * part;
-      uint64_t w0 = 0, w1 = 0;
-      if (off < olen) {
-        const uint64_t opos = s_pos[owner];
-        w0 = ld64u(arena, opos + off);
-        if (off + 8 < olen) w1 = ld64u(arena, opos + off + 8);
-      }
-      sm[owner * GTX_STRIDE + 2 * part] = w0;
-      sm[owner * GTX_STRIDE + 2 * part + 1] = w1;
-    }
-    __syncthreads();
-    if (b < nblk) {
-      uint64_t m[16];
-      const uint64_t base = (uint64_t)b * 128;
-#pragma unroll
-      for (int k = 0; k < 16; k++) {
-        const uint64_t off = base + 8 * k;
-        uint64_t w = off < len ? sm[t * GTX_STRIDE + k] : 0;
-        if (off < len && len - off < 8) w &= (1ull << (8 * (len - off))) - 1;
-        m[k] = w;
-      }
-      const bool last = b + 1 == nblk;
-      b2b_compress(h, m, last ? (uint64_t)len : base + 128, last);
-    }
-    __syncthreads();
-  }
-  if (!act) return;
   uint32_t out[8];
-#pragma unroll
-  for (int w = 0; w < 4; w++) { out[2 * w] = (uint32_t)h[w]; out[2 * w + 1] = (uint32_t)(h[w] >> 32); }
+  b2b256_staged(out, arena, act, pos, len);   // every lane: it holds barriers
+  if (!act) return;
   store_words(tx_id + 32 * p, out, 8);
 }
 

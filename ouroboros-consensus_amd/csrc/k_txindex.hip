@@ -22,7 +22,8 @@
 //                 row values are summed (u64).
 //   k_txi_final   one lane per provisional row: its place among the rows of the blocks that
 //                 stayed OK, the row's fields copied there, and tx_id = Blake2b-256 of the stored
-//                 body bytes with the message blocks staged through LDS as k_seg_hash stages them.
+//                 body bytes with the message blocks staged through LDS (arena.hpp
+//                 b2b256_staged, which k_seg_hash calls too).
 // The walks read item heads with byte loads, one lane per item sequence: neighbouring lanes
 // are in different blocks (count, emit) or different transactions (rows), so their loads do not
 // coalesce and their loops diverge; they are latency-bound and hidden by occupancy, as
@@ -33,72 +34,9 @@
 // CPU restatement: tests/tx_index_model.py.
 #include "kcommon.hpp"
 #include "arena.hpp"
-#include "cbor_dev.hpp"
+#include "tx_dev.hpp"
 
 namespace {
-
-enum : uint8_t { TXK_NONE = 0, TXK_SHELLEY3 = 1, TXK_SHELLEY4 = 2, TXK_BYRON = 3, TXK_EBB = 4 };
-
-// one level of an array or a map: items (pairs) left, or indefinite
-struct Lvl {
-  uint64_t left;
-  bool indef;
-};
-
-__device__ __forceinline__ bool open_any(Cur& c, uint32_t& mt, Lvl& l) {
-  uint32_t ai;
-  uint64_t arg;
-  bool indef;
-  if (!head(c, mt, ai, arg, indef)) return false;
-  l.left = arg;
-  l.indef = indef;
-  return true;
-}
-__device__ __forceinline__ bool open(Cur& c, uint32_t want, Lvl& l) {
-  uint32_t mt;
-  return open_any(c, mt, l) && mt == want;
-}
-// an array of exactly k items (a definite head says so; an indefinite one is checked by shut)
-__device__ __forceinline__ bool open_k(Cur& c, uint64_t k, Lvl& l) {
-  return open(c, 4, l) && (l.indef || l.left == k);
-}
-__device__ __forceinline__ bool shut(Cur& c, const Lvl& l) {
-  if (!l.indef) return true;
-  if (c.p >= c.end || c.a[c.p] != 0xFF) return false;
-  c.p++;
-  return true;
-}
-// another item (pair) at this level?  Consumes the break of an indefinite level.
-__device__ __forceinline__ bool more(Cur& c, Lvl& l, bool& ok) {
-  if (l.indef) {
-    if (c.p >= c.end) { ok = false; return false; }
-    if (c.a[c.p] == 0xFF) { c.p++; return false; }
-    return true;
-  }
-  if (l.left == 0) return false;
-  l.left--;
-  return true;
-}
-__device__ __forceinline__ bool rd_u(Cur& c, uint64_t& v) {
-  uint32_t mt, ai;
-  bool indef;
-  return head(c, mt, ai, v, indef) && mt == 0;
-}
-
-// items of the array at c (count only; c is left inside a definite array)
-__device__ bool count_array(Cur& c, uint64_t& cnt) {
-  Lvl l;
-  if (!open(c, 4, l)) return false;
-  if (!l.indef) { cnt = l.left; return true; }
-  bool ok = true;
-  uint64_t k = 0;
-  while (more(c, l, ok)) {
-    if (!cbor_skip_regs(c)) return false;
-    k++;
-  }
-  cnt = k;
-  return ok;
-}
 
 __global__ void __launch_bounds__(NT) k_txi_count(size_t n, const uint8_t* __restrict__ arena, uint64_t arena_len,
                                                   const uint64_t* __restrict__ blk_off,
@@ -149,14 +87,14 @@ __global__ void __launch_bounds__(NT) k_txi_count(size_t n, const uint8_t* __res
       ok = ok && open(s3, 5, l);
       while (ok && more(s3, l, ok)) {
         uint64_t key;
-        ok = rd_u(s3, key) && key < nt && cbor_skip_regs(s3);
+        ok = rd_uint(s3, ~0ull, key) && key < nt && cbor_skip_regs(s3);
       }
       if (ok && ns == 4) {
         Cur s4 = seg(3);
         ok = open(s4, 4, l);
         while (ok && more(s4, l, ok)) {
           uint64_t idx;
-          ok = rd_u(s4, idx) && idx < nt;
+          ok = rd_uint(s4, ~0ull, idx) && idx < nt;
         }
       }
       st = ok ? PRAOS_TXI_OK : PRAOS_TXI_SHAPE;
@@ -225,7 +163,7 @@ __device__ void emit_part(uint32_t k, size_t i, size_t n, const uint8_t* __restr
     ok = open(c, 5, l);
     while (ok && more(c, l, ok)) {
       uint64_t key;
-      if (!rd_u(c, key)) break;
+      if (!rd_uint(c, ~0ull, key)) break;
       const uint64_t s = c.p;
       if (!cbor_skip_regs(c)) break;
       if (key < nt) {   // a repeated key: the later entry stands
@@ -237,7 +175,7 @@ __device__ void emit_part(uint32_t k, size_t i, size_t n, const uint8_t* __restr
     ok = open(c, 4, l);
     while (ok && more(c, l, ok)) {
       uint64_t idx;
-      if (!rd_u(c, idx)) break;
+      if (!rd_uint(c, ~0ull, idx)) break;
       if (idx < nt) r.is_valid[base + idx] = 0;
     }
   }
@@ -261,61 +199,6 @@ __global__ void __launch_bounds__(NT) k_txi_emit(size_t n, const uint8_t* __rest
   emit_part((uint32_t)k0, i, n, arena, blk_off, seg_off, seg_len, txp_o, txp_l, kd, base, nt, r);
 }
 
-// [mem, steps], both unsigned: the ExUnits of a redeemer
-__device__ __forceinline__ bool rd_exunits(Cur& c, uint64_t& steps) {
-  Lvl x;
-  uint64_t mem;
-  return open_k(c, 2, x) && rd_u(c, mem) && rd_u(c, steps) && shut(c, x);
-}
-
-// the value under key 5 of a witness set: [[tag, index, data, [mem, steps]], ...] or Conway's
-// {[tag, index]: [data, [mem, steps]], ...}; the sum of the steps mod 2^64
-__device__ bool redeemer_steps(Cur& c, uint64_t& sum) {
-  uint32_t mt;
-  Lvl l;
-  if (!open_any(c, mt, l) || (mt != 4 && mt != 5)) return false;
-  bool ok = true;
-  uint64_t s = 0;
-  while (ok && more(c, l, ok)) {
-    Lvl e;
-    uint64_t steps = 0;
-    if (mt == 4) {
-      ok = open_k(c, 4, e) && cbor_skip_regs(c) && cbor_skip_regs(c) && cbor_skip_regs(c) && rd_exunits(c, steps) &&
-           shut(c, e);
-    } else {
-      ok = cbor_skip_regs(c) && open_k(c, 2, e) && cbor_skip_regs(c) && rd_exunits(c, steps) && shut(c, e);
-    }
-    s += steps;
-  }
-  sum = s;
-  return ok;
-}
-
-// the value under the first unsigned key `want` of the map at c: found = false when there is
-// none (or c is no map and need_map is off); c is left at the value
-__device__ bool find_key(Cur& c, uint64_t want, bool need_map, bool& found) {
-  found = false;
-  uint32_t mt;
-  Lvl m;
-  if (!open_any(c, mt, m)) return false;
-  if (mt != 5) return !need_map;
-  bool ok = true;
-  while (ok && more(c, m, ok)) {
-    const uint64_t ks = c.p;
-    uint32_t kmt, ai;
-    uint64_t arg;
-    bool indef;
-    if (!head(c, kmt, ai, arg, indef)) return false;
-    if (kmt == 0 && arg == want) { found = true; return true; }
-    if (kmt > 1) {   // not an integer: the head alone is not the whole key
-      c.p = ks;
-      ok = cbor_skip_regs(c);
-    }
-    ok = ok && cbor_skip_regs(c);
-  }
-  return ok;
-}
-
 __global__ void __launch_bounds__(NT) k_txi_rows(size_t nrows, const uint8_t* __restrict__ arena,
                                                  const uint8_t* __restrict__ kind, TxRows r,
                                                  uint32_t* __restrict__ bad) {
@@ -325,7 +208,7 @@ __global__ void __launch_bounds__(NT) k_txi_rows(size_t nrows, const uint8_t* __
   const uint32_t bl = r.body_len[p], wl = r.wit_len[p], al = r.aux_len[p];
   Cur b{arena, r.body_off[p], r.body_off[p] + bl, true};
   bool ok = bl != 0 && wl != 0;   // a row the emit pass did not reach
-  uint64_t nout = 0, steps = 0;
+  uint64_t nout = 0, mem = 0, steps = 0;   // the index keeps no memory units
   if (ok && kd == TXK_BYRON) {
     // tx = [inputs, outputs, attributes]: the items of tx[1]
     Lvl t;
@@ -339,7 +222,7 @@ __global__ void __launch_bounds__(NT) k_txi_rows(size_t nrows, const uint8_t* __
     if (ok && kd == TXK_SHELLEY4) {
       Cur w{arena, r.wit_off[p], r.wit_off[p] + wl, true};
       ok = find_key(w, 5, false, found);
-      if (ok && found) ok = redeemer_steps(w, steps);
+      if (ok && found) ok = redeemer_units(w, mem, steps);
     }
     r.size[p] = 1u + bl + wl + (al ? al : 1u);   // sizeTxF: [body, wits, aux or null]
   }
@@ -375,22 +258,14 @@ __global__ void __launch_bounds__(NT) k_txi_reduce(size_t n, const uint32_t* __r
   ex_steps[i] = ex;
 }
 
-constexpr uint32_t TXI_STRIDE = 17;   // u64 words per staged message block (16 + 1 pad), as k_seg_hash
-
 // Provisional row p of a block that stayed OK lands at tfirst[i] + (p - first[i]).  tx_id: the
-// workgroup loads the next 128-byte block of its 256 bodies cooperatively (8 lanes x 16 bytes per
-// body, whole lines per instruction) into LDS and each lane compresses its own; rows neighbouring
-// in a block are of similar size, and the loop runs to the workgroup's longest body.
+// workgroup hashes its 256 bodies together (b2b256_staged); rows neighbouring in a block are of
+// similar size, and its loop runs to the workgroup's longest body.
 __global__ void __launch_bounds__(NT) k_txi_final(size_t nrows, const uint8_t* __restrict__ arena,
                                                   const uint8_t* __restrict__ status,
                                                   const uint32_t* __restrict__ first,
                                                   const uint32_t* __restrict__ tfirst, TxRows r, TxRows o) {
-  __shared__ uint64_t sm[NT * TXI_STRIDE];
-  __shared__ uint64_t s_pos[NT];
-  __shared__ uint32_t s_len[NT];
-  __shared__ uint32_t s_max;
-  const uint32_t t = threadIdx.x;
-  const size_t p = (size_t)blockIdx.x * NT + t;
+  const size_t p = (size_t)blockIdx.x * NT + threadIdx.x;
   bool act = false;
   uint64_t pos = 0;
   uint32_t len = 0;
@@ -416,53 +291,9 @@ __global__ void __launch_bounds__(NT) k_txi_final(size_t nrows, const uint8_t* _
     }
   }
   if (!o.tx_id) return;   // the same for every lane
-  const uint32_t nblk = act ? (len == 0 ? 1u : (len + 127u) / 128u) : 0u;
-  s_pos[t] = pos;
-  s_len[t] = act ? len : 0u;
-  if (t == 0) s_max = 0;
-  __syncthreads();
-  if (nblk) atomicMax(&s_max, nblk);
-  __syncthreads();
-  const uint32_t nb = s_max;
-  uint64_t h[8];
-#pragma unroll
-  for (int w = 0; w < 8; w++) h[w] = B2B_IV[w];
-  h[0] ^= 0x01010000ULL ^ 32u;
-  for (uint32_t b = 0; b < nb; b++) {
-#pragma unroll
-    for (uint32_t rr = 0; rr < 8; rr++) {
-      const uint32_t c = rr * NT + t, owner = c >> 3, part = c & 7u;
-      const uint32_t olen = s_len[owner];
-      const uint64_t off = (uint64_t)b * 128 + 16 * part;
-      uint64_t w0 = 0, w1 = 0;
-      if (off < olen) {
-        const uint64_t opos = s_pos[owner];
-        w0 = ld64u(arena, opos + off);
-        if (off + 8 < olen) w1 = ld64u(arena, opos + off + 8);
-      }
-      sm[owner * TXI_STRIDE + 2 * part] = w0;
-      sm[owner * TXI_STRIDE + 2 * part + 1] = w1;
-    }
-    __syncthreads();
-    if (b < nblk) {
-      uint64_t m[16];
-      const uint64_t base = (uint64_t)b * 128;
-#pragma unroll
-      for (int k = 0; k < 16; k++) {
-        const uint64_t off = base + 8 * k;
-        uint64_t w = off < len ? sm[t * TXI_STRIDE + k] : 0;
-        if (off < len && len - off < 8) w &= (1ull << (8 * (len - off))) - 1;
-        m[k] = w;
-      }
-      const bool last = b + 1 == nblk;
-      b2b_compress(h, m, last ? (uint64_t)len : base + 128, last);
-    }
-    __syncthreads();
-  }
-  if (!act) return;
   uint32_t out[8];
-#pragma unroll
-  for (int w = 0; w < 4; w++) { out[2 * w] = (uint32_t)h[w]; out[2 * w + 1] = (uint32_t)(h[w] >> 32); }
+  b2b256_staged(out, arena, act, pos, len);   // every lane: it holds barriers
+  if (!act) return;
   store_words(o.tx_id + 32 * q, out, 8);
 }
 

@@ -24,28 +24,9 @@
 // are latency-bound and short beside the verifies.
 // CPU restatement: tests/tx_witness_model.py.
 #include "byron_dev.hpp"
+#include "tx_dev.hpp"
 
 namespace {
-
-constexpr uint8_t TXK_BYRON = 3;   // k_txindex.hip's kind of a Byron main block
-
-// one level of an array or a map, as k_txindex.hip walks them (its helpers are local to it)
-struct Lvl {
-  uint64_t left;
-  bool indef;
-};
-
-// another item (pair) at this level?  Consumes the break of an indefinite level.
-__device__ __forceinline__ bool more(Cur& c, Lvl& l, bool& ok) {
-  if (l.indef) {
-    if (c.p >= c.end) { ok = false; return false; }
-    if (c.a[c.p] == 0xFF) { c.p++; return false; }
-    return true;
-  }
-  if (l.left == 0) return false;
-  l.left--;
-  return true;
-}
 
 // Where the witness records of one row go (emit pass; count pass: tx = null)
 struct WitOut {
@@ -73,15 +54,12 @@ __device__ bool walk_wits(Cur& c, uint32_t arity, uint64_t& cnt, const WitOut& o
   bool ok = true;
   uint64_t k = 0;
   while (ok && more(c, l, ok)) {
-    uint64_t n, key_at = 0, sig_at = 0;
-    bool ind;
-    if (!(head(c, mt, ai, n, ind) && mt == 4 && (ind || n == arity))) return false;
+    uint64_t key_at = 0, sig_at = 0;
+    Lvl e;
+    if (!open_k(c, arity, e)) return false;
     if (!(rd_bytes(c, 32, key_at) && rd_bytes(c, 64, sig_at))) return false;
     if (arity == 4 && !(cbor_skip_regs(c) && cbor_skip_regs(c))) return false;
-    if (ind) {
-      if (c.p >= c.end || c.a[c.p] != 0xFF) return false;
-      c.p++;
-    }
+    if (!shut(c, e)) return false;
     if (o.tx && k < lim) {
       o.tx[base + k] = row;
       o.kind[base + k] = kd;
@@ -144,11 +122,7 @@ __global__ void __launch_bounds__(NT) k_txw_count(size_t nrows, TxwCount a) {
           at2 = c.p;
           ok = walk_wits(c, 4, nb, none, 0, 0, 0, 0);
         } else {
-          if (kmt > 1) {   // not an integer: the head alone is not the whole key
-            c.p = ks;
-            ok = cbor_skip_regs(c);
-          }
-          ok = ok && cbor_skip_regs(c);
+          skip_pair(c, ks, kmt, ok);
         }
       }
     }
