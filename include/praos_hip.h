@@ -740,6 +740,126 @@ typedef struct {                  /* per distinct transaction; caller buffers of
 int praos_verify_gen_txs(praos_ctx* ctx, const praos_header_bytes* items, const praos_gtx_cfg* cfg,
                          praos_gtx_items* per_item, praos_gtx_txs* txs, praos_txw_wits* wits);
 
+/* ---- BlockFetch blocks: wire blocks, each checked once (additive: ABI version unchanged) ----
+ * The checks the BlockFetch client makes on every block it receives, and the key-witness check
+ * above for those blocks -- the blocks that ChainSel applies (ApplyVal) rather than reapplies:
+ * mkBlockFetchConsensusInterface (MiniProtocol/BlockFetch/ClientInterface.hs:157-176) tests that
+ * the block is the one asked for and blockMatchesHeader (Shelley/Ledger/Block.hs:150-158,
+ * Byron/Ledger/Block.hs:161-162).  In deadline mode the decision logic "does not avoid requesting
+ * a block that is already in-flight from other peers" (ClientInterface.hs:208-221), so the same
+ * block arrives from several peers.
+ * items: wire block spans in one arena.  A wire block is #6.24(bytes) around the stored block
+ * [diskTag, ...] as praos_verify_block_integrity, praos_verify_byron_integrity and
+ * praos_index_block_txs take it (wrapCBORinCBOR (encodeDiskHfcBlock ccfg),
+ * HardFork/Combinator/Serialisation/SerialiseNodeToNode.hs:113): disk tag 0 an EBB, 1 a Byron main
+ * block, 2..7 Shelley to Conway; no era list around it.  The tag's and the byte string's heads are
+ * taken at any width; the tag is 24, the byte string definite; the inner bytes start with a
+ * definite array head of length 2 and an unsigned integer, at any width (PRAOS_WIRE_SYNTAX
+ * otherwise), a disk tag above cfg->n_eras is PRAOS_WIRE_ERA, bytes after the byte string are
+ * PRAOS_WIRE_TRAILING; bytes after the block inside the byte string fail the split.
+ * ranges: range r holds items [item_first[r], item_first[r + 1]) -- one peer's answer to one
+ * request, in arrival order -- and expects the points [exp_first[r], exp_first[r + 1]) of
+ * exp_slot / exp_hash, the points of the requested headers in order: item j of the range is
+ * held against point j.  item_first[0] = 0 and item_first[k] = items->n, both arrays ascending.
+ * Per item: the split of the stored-block calls (k_block_split for tags >= 2, k_byron_split for 0
+ * and 1), slot, block number and prev hash from their decoders, and the header hash (Blake2b-256
+ * of the header item; of 82 0k || header for Byron).
+ * Rows: one per distinct block.  With cfg->dedup the items that split and decode are classed by
+ * (disk tag, header hash, inner length); the representative of a class is its lowest item, and
+ * every other member is compared byte for byte with it: equal, it shares the representative's
+ * row; not equal, it gets a row of its own (such deviants are not classed among themselves).
+ * Different bytes never share a row, and a body is hashed once per row.  Rows are numbered in
+ * order of first appearance of their lowest item.  Without dedup every item that splits and
+ * decodes is its own row.
+ * Per row: bits = PRAOS_BLK_BODY_HASH when blockMatchesHeader fails, else 0.  No KES, PBFT
+ * signature or protocol-magic check: ChainSync validated the header and the hash carries that
+ * over.  Tags >= 2: body_hash = hashTxSeq as computed.  Tags 0 / 1: praos_verify_byron_integrity's
+ * body half with its PRAOS_BYRON_W_* in which; an EBB passes; body_hash is zeros.
+ * With cfg->witnesses: praos_verify_tx_witnesses over the rows' inner bytes (byron = Byron on),
+ * word for word; blocks_out, txs and wits are its outputs with "block" meaning row, and a row
+ * whose body check failed is indexed all the same.
+ * Verdict per item, the first that applies:
+ *   PRAOS_BF_WIRE          status != PRAOS_WIRE_OK
+ *   PRAOS_BF_TOO_MANY      its index in the range >= the range's expected points
+ *   PRAOS_BF_UNSUPPORTED   a Byron item with byron_epoch_slots = 0; or a Byron main block of
+ *                          n /= 1 transactions whose txRoot is the only failing comparison
+ *   PRAOS_BF_DECODE        the envelope or the header does not split or decode: no row
+ *   PRAOS_BF_WRONG_BLOCK   slot or header hash differs from the expected point (an EBB's slot:
+ *                          epoch * byron_epoch_slots)
+ *   PRAOS_BF_INVALID_BODY  the row's bits != 0
+ *   PRAOS_BF_OK
+ * Per range, folded on the host: stop = the index in the range of its first item that is not
+ * PRAOS_BF_OK (the item count when there is none); the items after it read
+ * PRAOS_BF_NOT_REACHED (their rows stay); accepted = stop; status COMPLETE, FAILED (an item is
+ * not OK) or TOO_FEW (no failure, fewer items than points).
+ * Host round trips: one for the row count, praos_verify_tx_witnesses' three with cfg->witnesses,
+ * and the final wait for the downloads. */
+#define PRAOS_BF_OK            0
+#define PRAOS_BF_WIRE          1
+#define PRAOS_BF_DECODE        2
+#define PRAOS_BF_WRONG_BLOCK   3
+#define PRAOS_BF_INVALID_BODY  4
+#define PRAOS_BF_TOO_MANY      5
+#define PRAOS_BF_UNSUPPORTED   6
+#define PRAOS_BF_NOT_REACHED   255
+#define PRAOS_BF_RANGE_COMPLETE 0
+#define PRAOS_BF_RANGE_FAILED   1
+#define PRAOS_BF_RANGE_TOO_FEW  2
+#define PRAOS_BF_NO_ROW 0xffffffffu
+typedef struct {
+  size_t k;                       /* ranges */
+  const uint64_t* item_first;     /* k + 1 */
+  const uint64_t* exp_first;      /* k + 1 */
+  const uint64_t* exp_slot;       /* exp_first[k] */
+  const uint8_t* exp_hash;        /* exp_first[k] * 32 */
+} praos_bf_ranges;
+typedef struct {
+  uint32_t n_eras;                /* the highest disk tag (7 for the reference's CardanoBlock); 1..31 */
+  uint32_t dedup;                 /* non-zero: byte-identical blocks share a row */
+  uint32_t witnesses;             /* 0: stop after the body check */
+  uint32_t max_lanes;             /* as praos_txw_cfg */
+  uint64_t byron_epoch_slots;     /* 0: Byron off */
+} praos_bf_cfg;
+typedef struct {                  /* per item (n entries); every pointer may be NULL = not returned */
+  uint8_t* status;                /* PRAOS_WIRE_* */
+  uint8_t* tag;                   /* the disk tag (0xff until it is read) */
+  uint8_t* verdict;               /* PRAOS_BF_* */
+  uint32_t* row;                  /* the item's distinct-block row, PRAOS_BF_NO_ROW: none */
+} praos_bf_items;
+typedef struct {                  /* per range (k entries); every pointer may be NULL */
+  uint64_t* stop;
+  uint64_t* accepted;
+  uint8_t* status;                /* PRAOS_BF_RANGE_* */
+} praos_bf_range_out;
+typedef struct {                  /* per distinct block; caller buffers of cap rows, every pointer may be NULL */
+  size_t cap;
+  size_t n_rows;                  /* out: the rows of the call */
+  uint32_t* item;                 /* the lowest item index of the row */
+  uint8_t* tag;
+  uint8_t* is_ebb;
+  uint64_t* slot;
+  uint64_t* block_no;
+  uint8_t* header_hash;           /* cap * 32 */
+  uint8_t* prev_hash;             /* cap * 32; zeros for Genesis */
+  uint64_t* hdr_off;              /* the header item, into items->bytes */
+  uint32_t* hdr_len;
+  uint64_t* blk_off;              /* the inner bytes: the stored block */
+  uint32_t* blk_len;
+  uint8_t* body_hash;             /* cap * 32: as computed (tags >= 2) */
+  uint8_t* bits;                  /* 0 or PRAOS_BLK_BODY_HASH */
+  uint8_t* which;                 /* PRAOS_BYRON_W_* (tags 0 / 1) */
+} praos_bf_rows;
+/* per_item, per_range, rows, blocks_out, txs and wits may be NULL.  When an array of rows, txs or
+ * wits is given and its cap is below the count: PRAOS_E_ARG with n_rows / n_wits = the counts
+ * needed and the per-item and per-range arrays filled; with no array given cap is not looked at
+ * (the sizing call).  blocks_out has a row per entry and no cap of its own: its arrays hold
+ * rows->cap entries (tx_first rows->cap + 1), and they are written only when rows is given and
+ * rows->cap >= n_rows -- never with rows NULL, never on a call whose rows do not fit.  At most
+ * 2^30 items in one call.  n = 0 is PRAOS_OK (every range TOO_FEW or COMPLETE). */
+int praos_verify_fetched_blocks(praos_ctx* ctx, const praos_header_bytes* items, const praos_bf_ranges* ranges,
+                                const praos_bf_cfg* cfg, praos_bf_items* per_item, praos_bf_range_out* per_range,
+                                praos_bf_rows* rows, praos_txw_blocks* blocks_out, praos_txw_txs* txs,
+                                praos_txw_wits* wits);
 /* ---- Byron header validation: PBFT (additive as the two sections above: ABI version unchanged) ----
  * validateHeader for Byron = validateEnvelope (HeaderValidation.hs:297-344 with the Byron
  * instance, Byron/Ledger/HeaderValidation.hs:39-75) + PBFT updateChainDepState
@@ -1593,6 +1713,18 @@ int praos_debug_hash_bytes(praos_ctx* ctx, int kind, size_t n, const uint8_t* ar
  * outside 2 .. 65535 (op 8).  n = 0 is PRAOS_OK.  PRAOS_E_STATE on a host-only context. */
 int praos_debug_int(praos_ctx* ctx, int op, size_t n, const uint8_t* a, const uint8_t* b, const uint8_t* c,
                     uint8_t* out);
+
+/* ---- addition (ABI stays 15): self test of the BlockFetch dedup's compare kernel (k_blockfetch.hip).
+ * out[i] = 1 iff arena[a_off[i], + len[i]) and
+ * arena[b_off[i], + len[i]) hold the same bytes.  One wave per pair: the bytes up to the first
+ * 16-byte boundary of a, then PRAOS_SPAN_EQ_VEC-byte vectors, PRAOS_SPAN_EQ_WAVE bytes per wave
+ * step and PRAOS_SPAN_EQ_TILE bytes between two any-difference votes, then the bytes left.  Reads
+ * the two spans only.  PRAOS_E_ARG, with nothing launched, for a span outside [0, arena_len). */
+#define PRAOS_SPAN_EQ_VEC  16u
+#define PRAOS_SPAN_EQ_WAVE 1024u
+#define PRAOS_SPAN_EQ_TILE 4096u
+int praos_debug_span_equal(praos_ctx* ctx, size_t n, const uint8_t* arena, size_t arena_len, const uint64_t* a_off,
+                           const uint64_t* b_off, const uint32_t* len, uint8_t* out);
 
 #ifdef __cplusplus
 }

@@ -68,6 +68,8 @@ module Ouroboros.Consensus.Protocol.Praos.Batch
   , praosVerifyTxWitnesses
   , GenTxResults (..)
   , praosVerifyGenTxs
+  , FetchedBlockResults (..)
+  , praosVerifyFetchedBlocks
   , BlockWitnessStats (..)
     -- * Byron header validation (PBFT)
   , PBftParamsC (..)
@@ -239,6 +241,16 @@ foreign import ccall safe "praos_verify_tx_witnesses" c_verify_tx_witnesses
 -- layout-gtx praos_gtx_txs (168 bytes): cap@0 n_rows@8 item@16 era@24 body_off@32 body_len@40 wit_off@48 wit_len@56 aux_off@64 aux_len@72 size@80 in_block_size@88 ex_mem@96 ex_steps@104 is_valid@112 tx_id@120 wstatus@128 n_vkey@136 n_boot@144 n_bad@152 wit_first@160
 foreign import ccall safe "praos_verify_gen_txs" c_verify_gen_txs
   :: Ptr PraosCtx -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> IO CInt
+-- additive as well (ABI version unchanged): wire blocks of the BlockFetch client.  Its structs
+-- (checked against the C compiler by tests/test_blockfetch_abi.py, which owns the "layout-bf"
+-- lines; the praos_txw_* structs are those above):
+-- layout-bf praos_bf_ranges (40 bytes): k@0 item_first@8 exp_first@16 exp_slot@24 exp_hash@32
+-- layout-bf praos_bf_cfg (24 bytes): n_eras@0 dedup@4 witnesses@8 max_lanes@12 byron_epoch_slots@16
+-- layout-bf praos_bf_items (32 bytes): status@0 tag@8 verdict@16 row@24
+-- layout-bf praos_bf_range_out (24 bytes): stop@0 accepted@8 status@16
+-- layout-bf praos_bf_rows (128 bytes): cap@0 n_rows@8 item@16 tag@24 is_ebb@32 slot@40 block_no@48 header_hash@56 prev_hash@64 hdr_off@72 hdr_len@80 blk_off@88 blk_len@96 body_hash@104 bits@112 which@120
+foreign import ccall safe "praos_verify_fetched_blocks" c_verify_fetched_blocks
+  :: Ptr PraosCtx -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> Ptr () -> IO CInt
 -- additive as well (ABI version unchanged): Byron header validation.  The structs
 -- validatePBftHeaderBatch pokes and peeks (checked against the C compiler by tests/test_pbft_abi.py;
 -- "layout-pbft": the other layout lines belong to the tests named above):
@@ -1066,6 +1078,89 @@ praosVerifyTxWitnesses ctx byron arena offs lens = do
       check ctx $ c_verify_tx_witnesses p (castPtr hb) (castPtr wcfg) (castPtr blks) (castPtr txs) (castPtr wits)
   BlockWitnessStats <$> VS.unsafeFreeze st <*> VS.unsafeFreeze ntx <*> VS.unsafeFreeze nwit <*> VS.unsafeFreeze nbad
                     <*> VS.unsafeFreeze nshape
+
+-- | What the BlockFetch client learns about the blocks its peers sent, before ChainSel: per wire
+-- item its verdict (0 OK, 1 the wire wrapper, 2 does not decode, 3 not the block asked for, 4 the
+-- body does not match the header, 5 more blocks than points, 6 unsupported, 255 after the range's
+-- first failure) and the row of its block (0xffffffff: none); per range how many blocks were
+-- accepted and its status (0 complete, 1 failed, 2 too few); per distinct block its point and the
+-- outcome of the key-witness signature check 'applyBlockLedgerResult' makes under ValidateAll
+-- (Shelley/Ledger/Ledger.hs:335-352): @fbrBad@ witnesses fail, @fbrShape@ transactions have a
+-- witness set outside the shapes read.
+data FetchedBlockResults = FetchedBlockResults
+  { fbrVerdict  :: !(VS.Vector Word8)
+  , fbrRow      :: !(VS.Vector Word32)
+  , fbrAccepted :: !(VS.Vector Word64)
+  , fbrStatus   :: !(VS.Vector Word8)
+  , fbrSlot     :: !(VS.Vector Word64)
+  , fbrBlockNo  :: !(VS.Vector Word64)
+  , fbrHash     :: !(VS.Vector Word8)     -- ^ rows x 32
+  , fbrNumTxs   :: !(VS.Vector Word32)
+  , fbrWits     :: !(VS.Vector Word32)
+  , fbrBad      :: !(VS.Vector Word32)
+  , fbrShape    :: !(VS.Vector Word32)
+  }
+
+-- | praos_verify_fetched_blocks over the wire blocks @arena[off_i .. off_i + len_i)@ (blocks in the
+-- node-to-node encoding, as the peers sent them; MiniProtocol/BlockFetch/ClientInterface.hs:157-176),
+-- byte-identical blocks sharing a row.  Range r holds the items @[itemFirst_r, itemFirst_(r+1))@
+-- and expects the points @[expFirst_r, expFirst_(r+1))@ of @expSlot@ / @expHash@ (32 bytes each).
+-- Two calls: the first, without row arrays, gives the number of distinct blocks; it costs a whole
+-- run, witness verifies included (a caller that bounds the rows by the item count can skip it).
+praosVerifyFetchedBlocks :: PraosBatchCtx -> Word32 -> Word64 -> BS.ByteString -> VS.Vector Word64 -> VS.Vector Word32
+                         -> VS.Vector Word64 -> VS.Vector Word64 -> VS.Vector Word64 -> BS.ByteString
+                         -> IO FetchedBlockResults
+praosVerifyFetchedBlocks ctx nEras byronEpochSlots arena offs lens itemFirst expFirst expSlot expHash = do
+  let n = VS.length offs
+      k = VS.length itemFirst - 1
+  when (VS.length lens /= n || k < 0 || VS.length expFirst /= k + 1 || BS.length expHash /= 32 * VS.length expSlot) $
+    throwIO (PraosBatchError (-1) "praosVerifyFetchedBlocks: vector lengths differ")
+  let p = ctxPtr ctx                           -- a group's first member: the check has no group form
+  vd <- VSM.new n
+  row <- VSM.new n
+  acc <- VSM.new k
+  rst <- VSM.new k
+  BSU.unsafeUseAsCStringLen arena $ \(ap, alen) -> BSU.unsafeUseAsCStringLen expHash $ \(ehp, _) ->
+    VS.unsafeWith offs $ \offp -> VS.unsafeWith lens $ \lenp -> VS.unsafeWith itemFirst $ \ifp ->
+    VS.unsafeWith expFirst $ \efp -> VS.unsafeWith expSlot $ \esp ->
+    VSM.unsafeWith vd $ \vdp -> VSM.unsafeWith row $ \rowp -> VSM.unsafeWith acc $ \accp -> VSM.unsafeWith rst $ \rstp ->
+    allocaBytes 40 $ \hb -> allocaBytes 40 $ \rgs -> allocaBytes 24 $ \bcfg -> allocaBytes 32 $ \its ->
+    allocaBytes 24 $ \rout -> allocaBytes 128 $ \rws -> allocaBytes 48 $ \blks -> allocaBytes 72 $ \txs ->
+    allocaBytes 64 $ \wits -> do
+      pokeByteOff hb 0 (fromIntegral n :: CSize) >> pokeByteOff hb 8 ap
+      pokeByteOff hb 16 (fromIntegral alen :: CSize)
+      pokeByteOff hb 24 offp >> pokeByteOff hb 32 lenp
+      pokeByteOff rgs 0 (fromIntegral k :: CSize) >> pokeByteOff rgs 8 ifp >> pokeByteOff rgs 16 efp
+      pokeByteOff rgs 24 esp >> pokeByteOff rgs 32 ehp
+      pokeByteOff bcfg 0 nEras >> pokeByteOff bcfg 4 (1 :: Word32) >> pokeByteOff bcfg 8 (1 :: Word32)
+      pokeByteOff bcfg 12 (0 :: Word32) >> pokeByteOff bcfg 16 byronEpochSlots
+      fillBytes its 0 32
+      pokeByteOff its 16 vdp >> pokeByteOff its 24 rowp
+      fillBytes rout 0 24
+      pokeByteOff rout 8 accp >> pokeByteOff rout 16 rstp
+      fillBytes rws 0 128 >> fillBytes blks 0 48     -- no row arrays: the caps are not looked at
+      fillBytes txs 0 72 >> fillBytes wits 0 64
+      let call = check ctx $ c_verify_fetched_blocks p (castPtr hb) (castPtr rgs) (castPtr bcfg) (castPtr its)
+                   (castPtr rout) (castPtr rws) (castPtr blks) (castPtr txs) (castPtr wits)
+      call
+      rows <- fromIntegral <$> (peekByteOff rws 8 :: IO CSize)
+      slot <- VSM.new rows
+      bno <- VSM.new rows
+      hh <- VSM.new (32 * rows)
+      ntx <- VSM.new rows
+      nwit <- VSM.new rows
+      nbad <- VSM.new rows
+      nshape <- VSM.new rows
+      VSM.unsafeWith slot $ \slotp -> VSM.unsafeWith bno $ \bnop -> VSM.unsafeWith hh $ \hhp ->
+        VSM.unsafeWith ntx $ \ntxp -> VSM.unsafeWith nwit $ \nwitp -> VSM.unsafeWith nbad $ \nbadp ->
+        VSM.unsafeWith nshape $ \nshapep -> do
+          pokeByteOff rws 0 (fromIntegral rows :: CSize)
+          pokeByteOff rws 40 slotp >> pokeByteOff rws 48 bnop >> pokeByteOff rws 56 hhp
+          pokeByteOff blks 8 ntxp >> pokeByteOff blks 16 nwitp >> pokeByteOff blks 24 nbadp >> pokeByteOff blks 32 nshapep
+          call
+      FetchedBlockResults <$> VS.unsafeFreeze vd <*> VS.unsafeFreeze row <*> VS.unsafeFreeze acc <*> VS.unsafeFreeze rst
+                          <*> VS.unsafeFreeze slot <*> VS.unsafeFreeze bno <*> VS.unsafeFreeze hh <*> VS.unsafeFreeze ntx
+                          <*> VS.unsafeFreeze nwit <*> VS.unsafeFreeze nbad <*> VS.unsafeFreeze nshape
 
 -- | What the TxSubmission inbound side learns about the transactions its peers offered, before
 -- 'addTx': per wire item its status (0 OK, 1..4 the wire wrapper's, 5 not the shape of a

@@ -2,7 +2,7 @@
 // api_internal.hpp -- what the units of the host API share: the context and batch structs, the
 // staging pool, the allocation / error helpers and the functions that cross
 // unit boundaries (praos_impl).  Included by praos_api / praos_xfer / praos_blocks / praos_stream /
-// praos_run / praos_fold / praos_debug / praos_txindex / praos_txwit / praos_gentx only; the other
+// praos_run / praos_fold / praos_debug / praos_txindex / praos_txwit / praos_gentx / praos_blockfetch only; the other
 // host modules (replay, group, candidates, pbft) go through replay_internal.hpp.
 #include "praos_hip.h"
 #include "launch.hpp"
@@ -481,6 +481,12 @@ int txw_rows_run(praos_ctx* c, const char* who, const uint8_t* arena, uint64_t a
                  const uint8_t* blk_kind, const uint32_t* row_block, const uint64_t* wit_off, const uint32_t* wit_len,
                  const uint8_t* tx_id, uint32_t max_lanes, txw_rows& R);
 int txw_rows_down_wits(praos_ctx* c, praos_txw_wits* wits, const txw_rows& R);
+// the context's Ed25519 lane tables (txw_tabs) grown to at least `lanes` lanes
+int txw_lane_tables(praos_ctx* c, size_t lanes);
+// praos_verify_tx_witnesses over a batch of which only n, arena, arena_len, blk_off and blk_len
+// are read (praos_blockfetch.hip: the rows of distinct wire blocks as blocks)
+int txw_run(praos_ctx* c, praos_batch* b, const praos_txw_cfg* cfg, praos_txw_blocks* bo, praos_txw_txs* txs,
+            praos_txw_wits* wits);
 
 // praos_api.hip: the radix-2^16 comb, k_decode_praos over a from-bytes batch, the overlay class
 // of a slot

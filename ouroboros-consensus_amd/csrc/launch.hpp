@@ -411,3 +411,60 @@ void launch_gtx_final(hipStream_t stream, size_t n, const uint32_t* total, const
                       const uint8_t* row_ok, const uint32_t* row_final, const uint64_t* ex_mem, const uint64_t* ex_steps,
                       const uint8_t* tx_id, const praos_gtx_dev_items* items, uint32_t* item_row,
                       const praos_gtx_dev_rows* rows);
+// wire blocks (k_blockfetch.hip).  unwrap: status, disk tag and inner span of n wire items; hoff /
+// hlen: the inner span again, launch_block_split's in / out columns.  key: elig[i] = 0 for an item
+// that splits and decodes (1 otherwise) and, key != NULL, the hash set's key (header hash with the
+// inner length folded in); *any_byron = 1 when such an item has disk tag 0 or 1.  class: one wave per item over launch_hdr_dedup's item_slot / item_rep:
+// slot2 / min2 for launch_hdr_number, a member that differs from its representative in a byte a
+// class of its own.  rows: the representatives' columns at rep_row (R rows; seg_off / seg_len
+// segment-major over R).  bits: a Byron row's bits, which and zero body hash from
+// launch_byron_integrity's results (NULL: Byron off).  verdict: PRAOS_BF_* per item, then which[]
+// loses its host-internal flag.  span_equal: out[i] = the spans a and b of len[i] bytes are equal.
+struct praos_bf_dev_items {
+  const uint8_t* tag;
+  const uint8_t* kind;            // launch_byron_split's (zeros with Byron off)
+  const uint64_t* slot;
+  const uint64_t* block_no;
+  const uint64_t* hoff;
+  const uint32_t* hlen;
+  const uint8_t* header_hash;
+  const uint8_t* prev_hash;
+  const uint8_t* body_hash;       // the header's
+  const uint8_t* nseg;
+  const uint64_t* seg_off;
+  const uint32_t* seg_len;
+};
+struct praos_bf_dev_rows {
+  uint32_t* item;
+  uint8_t* tag;
+  uint8_t* is_ebb;
+  uint64_t* slot;
+  uint64_t* block_no;
+  uint64_t* hdr_off;
+  uint32_t* hdr_len;
+  uint8_t* header_hash;
+  uint8_t* prev_hash;
+  uint8_t* claimed;               // the header's body hash
+  uint8_t* nseg;
+  uint64_t* seg_off;
+  uint32_t* seg_len;
+};
+void launch_span_equal(hipStream_t stream, size_t n, const uint8_t* arena, uint64_t arena_len, const uint64_t* a_off,
+                       const uint64_t* b_off, const uint32_t* len, uint8_t* out);
+void launch_bf_unwrap(hipStream_t stream, size_t n, const uint8_t* arena, uint64_t arena_len, const uint64_t* off,
+                      const uint32_t* len, uint32_t n_eras, uint8_t* status, uint8_t* tag, uint64_t* ioff,
+                      uint32_t* ilen, uint64_t* hoff, uint32_t* hlen);
+void launch_bf_key(hipStream_t stream, size_t n, const uint8_t* status, const uint8_t* split_status,
+                   const uint16_t* dec_status, const uint8_t* tag, const uint32_t* ilen, const uint8_t* header_hash,
+                   uint8_t* elig, uint8_t* key, uint32_t* any_byron);
+void launch_bf_class(hipStream_t stream, size_t n, const uint8_t* arena, const uint32_t* item_slot,
+                     const uint32_t* item_rep, const uint64_t* ioff, const uint32_t* ilen, uint32_t* slot2,
+                     uint32_t* min2);
+void launch_bf_rows(hipStream_t stream, size_t n, size_t R, const uint32_t* slot2, const uint32_t* rep_row,
+                    const praos_bf_dev_items* items, const praos_bf_dev_rows* rows);
+void launch_bf_bits(hipStream_t stream, size_t R, const uint8_t* tag, const uint8_t* byr_result,
+                    const uint8_t* byr_which, uint8_t* bits, uint8_t* which, uint8_t* body_hash);
+void launch_bf_verdict(hipStream_t stream, size_t n, size_t R, int byron_on, const uint8_t* status, const uint8_t* tag,
+                       const uint32_t* item_row, const uint32_t* exp_idx, const uint64_t* exp_slot,
+                       const uint8_t* exp_hash, const uint64_t* slot, const uint8_t* header_hash, const uint8_t* bits,
+                       uint8_t* which, uint8_t* verdict);

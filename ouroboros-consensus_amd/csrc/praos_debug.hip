@@ -695,4 +695,31 @@ int praos_debug_int(praos_ctx* c, int op, size_t n, const uint8_t* a, const uint
   return PRAOS_OK;
 }
 
+int praos_debug_span_equal(praos_ctx* c, size_t n, const uint8_t* arena, size_t arena_len, const uint64_t* a_off,
+                           const uint64_t* b_off, const uint32_t* len, uint8_t* out) {
+  if (!c || (!arena && arena_len) || n > (1u << 24)) return PRAOS_E_ARG;
+  if (n == 0) return PRAOS_OK;
+  if (!a_off || !b_off || !len || !out) return PRAOS_E_ARG;
+  for (size_t i = 0; i < n; i++)
+    for (const uint64_t o : {a_off[i], b_off[i]})
+      if (o > arena_len || len[i] > arena_len - o) {
+        c->err = "praos_debug_span_equal: span outside the arena, pair " + std::to_string(i);
+        return PRAOS_E_ARG;
+      }
+  if (praos_host_only_(c)) return PRAOS_E_STATE;
+  HIPCHK(c, hipSetDevice(c->device));
+  Scratch s(c);
+  auto da = s.up(arena, arena_len);          // the bytes alone: the kernel reads nothing past them
+  auto d_a = s.up(a_off, 8 * n);
+  auto d_b = s.up(b_off, 8 * n);
+  auto dlen = s.up(len, 4 * n);
+  auto dout = s.zeros<uint8_t>(n);
+  if (!s.ok) return PRAOS_E_OOM;
+  launch_span_equal(c->stream, n, da, arena_len, d_a, d_b, dlen, dout);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, dout, n, hipMemcpyDeviceToHost));
+  return PRAOS_OK;
+}
+
 }  // extern "C"

@@ -33,6 +33,23 @@ bool any_wit_array(const praos_txw_wits* w) {
 
 namespace praos_impl {
 
+// the context's lane tables hold at least `lanes` lanes (grown, never shrunk; the stream is drained
+// before they are replaced)
+int txw_lane_tables(praos_ctx* c, size_t lanes) {
+  if (c->txw_lanes >= lanes) return PRAOS_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  (void)hipFree(c->txw_tabs);
+  c->txw_tabs = nullptr;
+  c->txw_lanes = 0;
+  if (hipMalloc(&c->txw_tabs, lanes * LT_ED_B) != hipSuccess) {
+    c->txw_tabs = nullptr;
+    c->err = "device allocation failed";
+    return PRAOS_E_OOM;
+  }
+  c->txw_lanes = lanes;
+  return PRAOS_OK;
+}
+
 // count, the counts down and their prefix sum up, emit, the verify slices, the per-row reduction:
 // everything is enqueued on the context's stream; R owns the buffers and holds wit_first and W
 int txw_rows_run(praos_ctx* c, const char* who, const uint8_t* arena, uint64_t arena_len, size_t T,
@@ -81,18 +98,8 @@ int txw_rows_run(praos_ctx* c, const char* who, const uint8_t* arena, uint64_t a
       return PRAOS_E_OOM;
     }
     const size_t lanes = std::min<size_t>((size_t)W, max_lanes ? max_lanes : TXW_LANES);
-    if (c->txw_lanes < lanes) {
-      HIPCHK(c, hipStreamSynchronize(s));
-      (void)hipFree(c->txw_tabs);
-      c->txw_tabs = nullptr;
-      c->txw_lanes = 0;
-      if (hipMalloc(&c->txw_tabs, lanes * LT_ED_B) != hipSuccess) {
-        c->txw_tabs = nullptr;
-        c->err = "device allocation failed";
-        return PRAOS_E_OOM;
-      }
-      c->txw_lanes = lanes;
-    }
+    const int rt = txw_lane_tables(c, lanes);
+    if (rt != PRAOS_OK) return rt;
     launch_txw_emit(s, T, arena, wit_off, wit_len, R.nv, R.nb, R.v0, R.v2, R.d_wfirst, W, R.tx, R.kind, R.koff, R.soff);
     HIPCHK(c, hipGetLastError());
     for (size_t w0 = 0; w0 < W; w0 += lanes) {
@@ -123,10 +130,8 @@ int txw_rows_down_wits(praos_ctx* c, praos_txw_wits* wits, const txw_rows& R) {
   return PRAOS_OK;
 }
 
-}  // namespace praos_impl
-
-namespace {
-
+// the whole call over a block batch: b's n, arena and block spans are all it reads of the batch
+// (praos_blockfetch.hip passes one whose blocks are the rows of distinct wire blocks)
 int txw_run(praos_ctx* c, praos_batch* b, const praos_txw_cfg* cfg, praos_txw_blocks* bo, praos_txw_txs* txs,
             praos_txw_wits* wits) {
   const size_t n = b->n;
@@ -212,7 +217,7 @@ int txw_run(praos_ctx* c, praos_batch* b, const praos_txw_cfg* cfg, praos_txw_bl
   return PRAOS_OK;
 }
 
-}  // namespace
+}  // namespace praos_impl
 
 extern "C" {
 
@@ -220,7 +225,7 @@ int praos_block_batch_tx_witnesses(praos_ctx* c, praos_batch* b, const praos_txw
                                    praos_txw_txs* txs, praos_txw_wits* wits) {
   if (!c || !b || !b->is_block || !cfg) return PRAOS_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  const int r = txw_run(c, b, cfg, blocks_out, txs, wits);
+  const int r = praos_impl::txw_run(c, b, cfg, blocks_out, txs, wits);
   (void)hipStreamSynchronize(c->stream);   // the call's buffers are freed on return
   return r;
 }

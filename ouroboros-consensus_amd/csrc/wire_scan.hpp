@@ -11,7 +11,8 @@
 // decodeListLen / decodeWord8 / decodeTag accept non-shortest forms); lists and the byte string
 // must be definite; the tag must be 24.  Plain integers only: k_wire.hip includes the file for
 // the device and g++ compiles it for the host tests (tests/test_wire_host.py).
-// gen_tx_unwrap, below it, is the same for a transaction (k_gentx.hip, tests/test_gentx_host.py).
+// gen_tx_unwrap, below it, is the same for a transaction (k_gentx.hip, tests/test_gentx_host.py),
+// wire_block_unwrap for a block (k_blockfetch.hip, tests/test_blockfetch_host.py).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -121,6 +122,33 @@ WIRE_HD Item gen_tx_unwrap(const uint8_t* a, uint64_t arena_len, uint64_t pos, u
   r.off = c.p;
   r.len = (uint32_t)v;
   r.status = c.p + v == c.end ? OK : TRAILING;
+  return r;
+}
+
+// The node-to-node wrapper of a block, as the BlockFetch client receives it: #6.24(bytes) around
+// the stored block [diskTag, ...] (wrapCBORinCBOR (encodeDiskHfcBlock ccfg),
+// HardFork/Combinator/Serialisation/SerialiseNodeToNode.hs:113) -- no era list around it.  The
+// same rules as wire_unwrap for the tag and the byte string.  Bytes after the byte string are
+// TRAILING, whatever it holds.  The inner bytes must start with a definite array head of length 2
+// and an unsigned integer, both of any width (SYNTAX otherwise): the disk tag, 0 an EBB, 1 a Byron
+// main block, 2.. the Shelley-based eras; a tag above n_eras (7 for the reference's CardanoBlock)
+// is ERA.  era = the disk tag (0xff until it is read; a tag above 0xfe reads 0xfe), (off, len) the
+// inner bytes of an OK or ERA item (0, 0 otherwise).  byron_kind and size_hint are not used.
+WIRE_HD Item wire_block_unwrap(const uint8_t* a, uint64_t arena_len, uint64_t pos, uint64_t len, uint32_t n_eras) {
+  Item r{SYNTAX, 0xff, NOT_BYRON, 0u, 0ull, 0u};
+  if (pos > arena_len || len > arena_len - pos) { r.status = RANGE; return r; }
+  Cur c{a, pos, pos + len};
+  uint64_t v;
+  if (!head(c, 6, v) || v != 24) return r;
+  if (!head(c, 2, v) || v > c.end - c.p || v > 0xffffffffull) return r;
+  if (c.p + v != c.end) { r.status = TRAILING; return r; }
+  const uint64_t at = c.p;
+  uint64_t tag;
+  if (!head(c, 4, v) || v != 2 || !head(c, 0, tag)) return r;
+  r.off = at;
+  r.len = (uint32_t)(c.end - at);
+  r.era = tag > 0xfe ? (uint8_t)0xfe : (uint8_t)tag;
+  r.status = tag > n_eras ? ERA : OK;
   return r;
 }
 

@@ -283,6 +283,43 @@ class GtxTxs(ctypes.Structure):
                                                                           for name, dt, _ in GTX_TX_FIELDS]
 
 
+# BlockFetch blocks: wire blocks, each checked once (praos_verify_fetched_blocks)
+(BF_OK, BF_WIRE, BF_DECODE, BF_WRONG_BLOCK, BF_INVALID_BODY, BF_TOO_MANY, BF_UNSUPPORTED,
+ BF_NOT_REACHED) = 0, 1, 2, 3, 4, 5, 6, 255
+BF_RANGE_COMPLETE, BF_RANGE_FAILED, BF_RANGE_TOO_FEW, BF_NO_ROW = 0, 1, 2, 0xFFFFFFFF
+SPAN_EQ_VEC, SPAN_EQ_WAVE, SPAN_EQ_TILE = 16, 1024, 4096   # praos_debug_span_equal's geometry
+BF_ITEM_FIELDS = (("status", np.uint8), ("tag", np.uint8), ("verdict", np.uint8), ("row", np.uint32))   # praos_bf_items
+BF_RANGE_FIELDS = (("stop", np.uint64), ("accepted", np.uint64), ("status", np.uint8))   # praos_bf_range_out
+BF_ROW_FIELDS = (  # name, dtype, record shape (praos_bf_rows)
+    ("item", np.uint32, ()), ("tag", np.uint8, ()), ("is_ebb", np.uint8, ()), ("slot", np.uint64, ()),
+    ("block_no", np.uint64, ()), ("header_hash", np.uint8, (32,)), ("prev_hash", np.uint8, (32,)),
+    ("hdr_off", np.uint64, ()), ("hdr_len", np.uint32, ()), ("blk_off", np.uint64, ()), ("blk_len", np.uint32, ()),
+    ("body_hash", np.uint8, (32,)), ("bits", np.uint8, ()), ("which", np.uint8, ()))
+
+
+class BfRanges(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_size_t), ("item_first", u64p), ("exp_first", u64p), ("exp_slot", u64p),
+                ("exp_hash", u8p)]
+
+
+class BfCfg(ctypes.Structure):
+    _fields_ = [("n_eras", ctypes.c_uint32), ("dedup", ctypes.c_uint32), ("witnesses", ctypes.c_uint32),
+                ("max_lanes", ctypes.c_uint32), ("byron_epoch_slots", ctypes.c_uint64)]
+
+
+class BfItems(ctypes.Structure):
+    _fields_ = [(name, _CT[dt]) for name, dt in BF_ITEM_FIELDS]
+
+
+class BfRangeOut(ctypes.Structure):
+    _fields_ = [(name, _CT[dt]) for name, dt in BF_RANGE_FIELDS]
+
+
+class BfRows(ctypes.Structure):
+    _fields_ = [("cap", ctypes.c_size_t), ("n_rows", ctypes.c_size_t)] + [(name, _CT[dt])
+                                                                          for name, dt, _ in BF_ROW_FIELDS]
+
+
 # Byron blocks: further PRAOS_BLK_* bits and the failing body comparisons (PRAOS_BYRON_W_*)
 BLK_PBFT_SIG, BLK_PM = 0x08, 0x10
 BYRON_W_DLG, BYRON_W_UPD, BYRON_W_NTX, BYRON_W_WIT, BYRON_W_ROOT = 0x01, 0x02, 0x04, 0x08, 0x10
@@ -498,6 +535,13 @@ SIGNATURES = {
                                                  ctypes.POINTER(TxwWits)]),
     "praos_verify_gen_txs": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HeaderBytes), ctypes.POINTER(GtxCfg),
                                             ctypes.POINTER(GtxItems), ctypes.POINTER(GtxTxs), ctypes.POINTER(TxwWits)]),
+    "praos_verify_fetched_blocks": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HeaderBytes),
+                                                   ctypes.POINTER(BfRanges), ctypes.POINTER(BfCfg),
+                                                   ctypes.POINTER(BfItems), ctypes.POINTER(BfRangeOut),
+                                                   ctypes.POINTER(BfRows), ctypes.POINTER(TxwBlocks),
+                                                   ctypes.POINTER(TxwTxs), ctypes.POINTER(TxwWits)]),
+    "praos_debug_span_equal": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, u8p, ctypes.c_size_t, u64p, u64p, u32p,
+                                              u8p]),
     "praos_block_batch_tx_witnesses": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(TxwCfg),
                                                       ctypes.POINTER(TxwBlocks), ctypes.POINTER(TxwTxs),
                                                       ctypes.POINTER(TxwWits)]),
@@ -1070,6 +1114,93 @@ class Context:
         nt, nw = int(ts.n_rows), int(ws.n_wits)
         return (I, {k: a[:nt + 1 if k == "wit_first" else nt] for k, a in T.items()},
                 {k: a[:nw] for k, a in W.items()}, (nt, nw))
+
+    # ---- BlockFetch: wire blocks, each distinct one checked once (k_blockfetch.hip) ----
+    def fetched_block_buffers(self, n, k, row_cap, tx_cap, wit_cap, rows=True):
+        """Output arrays for verify_fetched_blocks(..., out=...): (items, ranges, rows, blocks, txs,
+        wits) dicts of n items, k ranges, row_cap rows (the witness call's per-block arrays hold a
+        row each), tx_cap transactions and wit_cap witnesses; rows=False: the per-item and
+        per-range arrays only."""
+        I = {name: np.zeros(n, dt) for name, dt in BF_ITEM_FIELDS}
+        G = {name: np.zeros(k, dt) for name, dt in BF_RANGE_FIELDS}
+        if not rows:
+            return I, G, {}, {}, {}, {}
+        R = {name: np.zeros((row_cap,) + shp, dt) for name, dt, shp in BF_ROW_FIELDS}
+        B, T, W = self.tx_witness_buffers(row_cap, tx_cap, wit_cap)
+        return I, G, R, B, T, W
+
+    def verify_fetched_blocks(self, arena, off, length, item_first, exp_first, exp_slot, exp_hash, n_eras=7,
+                              byron_epoch_slots=0, dedup=True, witnesses=True, max_lanes=0, rows=True, cap=None,
+                              out=None):
+        """The wire blocks arena[off[i]:off[i]+len[i]] (blocks in the node-to-node encoding, as the
+        BlockFetch client receives them) held against the requested points, the distinct ones
+        checked once: blockMatchesHeader and, with witnesses, their transactions' key witnesses
+        (praos_verify_fetched_blocks).  item_first / exp_first (k + 1 each): range r holds items
+        [item_first[r], item_first[r+1]) and expects the points [exp_first[r], exp_first[r+1]) of
+        exp_slot / exp_hash (u8[., 32]).  Returns (items, ranges, rows, blocks, txs, wits, (n_rows,
+        n_txs, n_wits)): dicts of per-item (BF_ITEM_FIELDS), per-range (BF_RANGE_FIELDS), per-row
+        (BF_ROW_FIELDS) arrays and verify_tx_witnesses' three with "block" meaning row (empty
+        without witnesses); rows=False: the per-item and per-range arrays only.  cap: (row,
+        transaction, witness) capacities (default: sized by a first call, which costs a whole run
+        of the pipeline, witness verifies included: a caller that knows bounds passes cap or
+        out); smaller ones raise PraosError with .needed, .items and .ranges set, and the
+        per-row witness counts are then not written.  out: fetched_block_buffers of the same n
+        and k, written again in place."""
+        arena, off, length = self._chunk(arena, off, length)
+        hb = self.header_bytes_struct(arena, off, length)
+        n = len(off)
+        item_first = np.ascontiguousarray(item_first, np.uint64)
+        exp_first = np.ascontiguousarray(exp_first, np.uint64)
+        exp_slot = np.ascontiguousarray(exp_slot, np.uint64)
+        exp_hash = np.ascontiguousarray(exp_hash, np.uint8).reshape(-1, 32)
+        k = len(item_first) - 1
+        rg = BfRanges(k, ptr(item_first, u64p), ptr(exp_first, u64p), ptr(exp_slot, u64p) if len(exp_slot) else None,
+                      ptr(exp_hash) if len(exp_hash) else None)
+        cfg = BfCfg(n_eras, 1 if dedup else 0, 1 if witnesses else 0, max_lanes, byron_epoch_slots)
+
+        def call(it, ro, rs, bs, ts, ws):
+            ref = lambda x: ctypes.byref(x) if x is not None else None
+            return self.L.praos_verify_fetched_blocks(self.h, ctypes.byref(hb), ctypes.byref(rg), ctypes.byref(cfg),
+                                                      ref(it), ref(ro), ref(rs), ref(bs), ref(ts), ref(ws))
+        if out is None and rows and cap is None:
+            rs, ts, ws = BfRows(), TxwTxs(), TxwWits()
+            self.check(call(None, None, rs, None, ts, ws))
+            cap = (int(rs.n_rows), int(ts.n_rows), int(ws.n_wits))
+        I, G, R, B, T, W = out if out is not None else self.fetched_block_buffers(n, k, *(cap or (0, 0, 0)), rows=rows)
+        if not witnesses:
+            B, T, W = {}, {}, {}
+        it, ro, rs, bs, ts, ws = BfItems(), BfRangeOut(), BfRows(), TxwBlocks(), TxwTxs(), TxwWits()
+        for name, dt in BF_ITEM_FIELDS:
+            setattr(it, name, ptr(I[name], _CT[dt]))
+        for name, dt in BF_RANGE_FIELDS:
+            setattr(ro, name, ptr(G[name], _CT[dt]))
+        if R:
+            rs.cap = len(R["item"])
+            for name, dt, _ in BF_ROW_FIELDS:
+                setattr(rs, name, ptr(R[name], _CT[dt]))
+        if B:
+            for name, dt in TXW_BLOCK_FIELDS:
+                setattr(bs, name, ptr(B[name], _CT[dt]))
+        if T:
+            ts.cap = len(T["block"])
+            for name, dt, _ in TXW_TX_FIELDS:
+                setattr(ts, name, ptr(T[name], _CT[dt]))
+        if W:
+            ws.cap = len(W["tx"])
+            for name, dt, _ in TXW_WIT_FIELDS:
+                setattr(ws, name, ptr(W[name], _CT[dt]))
+        rc = call(it, ro, rs, bs if B else None, ts, ws)
+        if rc == E_ARG and (R or T or W) and (rs.n_rows > rs.cap or ts.n_rows > ts.cap or ws.n_wits > ws.cap):
+            msg = self.L.praos_last_error(self.h)
+            err = PraosError(f"praos rc={rc}: {msg.decode() if msg else ''}")
+            err.needed, err.items, err.ranges = (int(rs.n_rows), int(ts.n_rows), int(ws.n_wits)), I, G
+            raise err
+        self.check(rc)
+        nr, nt, nw = int(rs.n_rows), int(ts.n_rows), int(ws.n_wits)
+        return (I, G, {k_: a[:nr] for k_, a in R.items()},
+                {k_: a[:nr + 1 if k_ == "tx_first" else nr] for k_, a in B.items()},
+                {k_: a[:nt + 1 if k_ == "wit_first" else nt] for k_, a in T.items()},
+                {k_: a[:nw] for k_, a in W.items()}, (nr, nt, nw))
 
     # ---- ImmutableDB chunk validation (k_crc32.hip, praos_validate_chunk) ----
     def crc32(self, arena, off, length):
@@ -1720,6 +1851,18 @@ class Context:
         self.check(self.L.praos_debug_int(self.h, op, len(a), ptr(a), ptr(b), ptr(c), ptr(out)))
         return out
 
+
+    def debug_span_equal(self, arena, a_off, b_off, length):
+        """The BlockFetch dedup's compare kernel alone: u8[n], 1 where arena[a_off[i]:+len[i]] ==
+        arena[b_off[i]:+len[i]] (praos_debug_span_equal; one wave per pair)."""
+        a = np.frombuffer(bytes(arena), np.uint8)
+        a_off = np.ascontiguousarray(a_off, np.uint64)
+        b_off = np.ascontiguousarray(b_off, np.uint64)
+        length = np.ascontiguousarray(length, np.uint32)
+        out = np.zeros(len(a_off), np.uint8)
+        self.check(self.L.praos_debug_span_equal(self.h, len(a_off), ptr(a) if len(a) else None, len(a),
+                                                 ptr(a_off, u64p), ptr(b_off, u64p), ptr(length, u32p), ptr(out)))
+        return out
 
 class Group:
     """praos_group: one context per listed device (repeats allowed), batches split into
