@@ -1726,6 +1726,17 @@ int praos_debug_int(praos_ctx* ctx, int op, size_t n, const uint8_t* a, const ui
 int praos_debug_span_equal(praos_ctx* ctx, size_t n, const uint8_t* arena, size_t arena_len, const uint64_t* a_off,
                            const uint64_t* b_off, const uint32_t* len, uint8_t* out);
 
+/* ---- addition (ABI stays 15): self test of the row set of the wire calls (k_wire.hip's k_hdr_*
+ * kernels, as praos_validate_candidates*, praos_verify_gen_txs and praos_verify_fetched_blocks run
+ * them).  dedup != 0: the items with flag[i] == 0 and tag[i] < 32 in tag_mask are classed by
+ * (tag[i], key32[32 i, + 32)); limit is ignored.  dedup == 0: every item with flag[i] == 0 and
+ * i < *limit (limit NULL: n) is a class of its own; tag, key32 and tag_mask are not read.  The
+ * classes are numbered in order of first appearance: item_row[i] = the row of item i's class
+ * (PRAOS_NO_ROW: in no class), *n_rows = the classes.  n < 2^24; n = 0 is PRAOS_OK with
+ * *n_rows = 0.  PRAOS_E_STATE on a host-only context. */
+int praos_debug_row_set(praos_ctx* ctx, size_t n, const uint8_t* flag, const uint8_t* tag, const uint8_t* key32,
+                        uint32_t tag_mask, int dedup, const uint32_t* limit, uint32_t* item_row, uint32_t* n_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,9 +1,9 @@
 #pragma once
 // api_internal.hpp -- what the units of the host API share: the context and batch structs, the
-// staging pool, the allocation / error helpers and the functions that cross
+// staging pool, the allocation / error helpers, the wire calls' row set and the functions that cross
 // unit boundaries (praos_impl).  Included by praos_api / praos_xfer / praos_blocks / praos_stream /
-// praos_run / praos_fold / praos_debug / praos_txindex / praos_txwit / praos_gentx / praos_blockfetch only; the other
-// host modules (replay, group, candidates, pbft) go through replay_internal.hpp.
+// praos_run / praos_fold / praos_debug / praos_txindex / praos_txwit / praos_gentx / praos_blockfetch /
+// praos_candidates only; the other host modules (replay, group, pbft) go through replay_internal.hpp.
 #include "praos_hip.h"
 #include "launch.hpp"
 #include "host_util.hpp"
@@ -437,6 +437,83 @@ static hipError_t carve_alloc(DevBuf& buf, F&& layout) {
   layout(c);
   return hipSuccess;
 }
+// the same over the buffer the context keeps for the candidates calls (rp_scratch: the parts stay
+// valid until the next call that carves it); false: no memory
+template <typename F>
+static bool carve_kept(praos_ctx* c, F&& layout) {
+  Carve m;
+  layout(m);
+  Carve k;
+  k.base = rp_scratch(c, m.off);
+  if (!k.base) return false;
+  layout(k);
+  return true;
+}
+
+// ---- what the wire calls share (candidates, GenTxs, BlockFetch blocks)
+// the items of a call: spans where there are items, bytes where there is a length
+static inline bool items_ok(const praos_header_bytes* s) {
+  return s && (s->n == 0 || (s->off && s->len)) && (s->bytes_len == 0 || s->bytes);
+}
+// zeros in the pad behind an arena's bytes (ld64u, arena.hpp), on s: before the bytes go up
+static inline hipError_t pad_zero(uint8_t* arena, size_t bytes, hipStream_t s) {
+  return hipMemsetAsync(arena + bytes, 0, arena_pad(bytes), s);
+}
+// the items' offsets and lengths, on s: after the bytes
+static inline hipError_t items_upload(const praos_header_bytes& in, uint64_t* d_off, uint32_t* d_len, hipStream_t s) {
+  const hipError_t e = hipMemcpyAsync(d_off, in.off, 8 * in.n, hipMemcpyHostToDevice, s);
+  return e != hipSuccess ? e : hipMemcpyAsync(d_len, in.len, 4 * in.n, hipMemcpyHostToDevice, s);
+}
+// the download of an output array the caller may have left NULL
+struct Down {
+  hipStream_t s;
+  hipError_t operator()(void* dst, const void* src, size_t bytes) const {
+    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+  }
+};
+
+// The row set: which of n items are the same (tag, 32-byte key), and the row of each distinct one
+// in order of first appearance (k_wire.hip's k_hdr_* kernels).  A call lays it out in its Carve,
+// then runs reset + set (dedup) or ident, and number.  A copy with other arrays put in numbers
+// other classes (BlockFetch: the ones k_bf_class refined) or into other rows (GenTxs' second pass).
+struct RowSet {
+  size_t n = 0, nb = 0, tab = 0;                 // items, blocks of NT items, the table's slots
+  uint32_t *item_slot = nullptr, *item_rep = nullptr, *rep_row = nullptr, *item_row = nullptr, *blk = nullptr,
+           *slot_item = nullptr, *slot_min = nullptr;
+  void layout(Carve& m, size_t items) {
+    n = items;
+    nb = (n + NT - 1) / NT;
+    for (tab = 2; tab < 2 * n;) tab <<= 1;       // a power of two >= 2n: probing always ends, and
+    item_slot = m.take<uint32_t>(4 * n);         // ident's n entries of slot_min fit
+    item_rep = m.take<uint32_t>(4 * n);
+    rep_row = m.take<uint32_t>(4 * n);
+    item_row = m.take<uint32_t>(4 * n);
+    blk = m.take<uint32_t>(4 * nb);
+    slot_item = m.take<uint32_t>(4 * tab);
+    slot_min = m.take<uint32_t>(4 * tab);
+  }
+  hipError_t reset(hipStream_t s) const {
+    const hipError_t e = hipMemsetAsync(slot_item, 0, 4 * tab, s);
+    return e != hipSuccess ? e : hipMemsetAsync(slot_min, 0xff, 4 * tab, s);
+  }
+  // the classes: items with flag 0 and a tag below 32 in tag_mask, by (tag, key)
+  void set(hipStream_t s, const uint8_t* flag, const uint8_t* tag, const uint8_t* key, uint32_t tag_mask) const {
+    launch_hdr_set(s, n, flag, tag, key, tag_mask, (uint32_t)(tab - 1), slot_item, slot_min, item_slot);
+  }
+  // ... or every index below *limit (a device word; NULL: n) with flag[i] == flag_ok its own class
+  void ident(hipStream_t s, const uint32_t* limit, const uint8_t* flag, uint8_t flag_ok) const {
+    launch_hdr_ident(s, n, limit, flag, flag_ok, item_slot, slot_min);
+  }
+  // item_rep alone: for a caller that refines the classes before it numbers them
+  void count(hipStream_t s) const { launch_hdr_count(s, n, item_slot, slot_min, item_rep, blk); }
+  // rows in order of first appearance: *total (a device word), rep_row, item_row, and the
+  // representatives' spans ioff / ilen compacted into row_off / row_len (n entries)
+  void number(hipStream_t s, uint32_t* total, const uint64_t* ioff, const uint32_t* ilen, uint64_t* row_off,
+              uint32_t* row_len) const {
+    launch_hdr_number(s, n, item_slot, slot_min, item_rep, blk, total, ioff, ilen, (uint32_t)n, row_off, row_len,
+                      rep_row, item_row);
+  }
+};
 
 // The transaction index's device results kept for a pass that follows it (praos_txwit.hip): the
 // call's allocations, owned here, and what that pass reads in them.

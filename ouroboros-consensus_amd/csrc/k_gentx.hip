@@ -5,10 +5,8 @@
 //                 inner bytes -- one array [body, wits, (isValid,) aux / null], definite or
 //                 indefinite, nothing after it -- with cbor_skip_regs (spans, is_valid, size), and
 //                 Blake2b-256 of the inner bytes (b2b256_range), the key of the dedup.
-//   k_gtx_ident   the hash set's arrays for a numbering without a hash set: every flagged index
-//                 its own class (dedup off; the second numbering that drops the rows k_gtx_rows
-//                 refused).  k_wire.hip's count / scan / rows / map kernels number both.
-//   k_gtx_rep     row_item[row] = the representative item of each provisional row.
+//   (the provisional and the final rows are numbered by k_wire.hip's row set kernels: the hash
+//   set or k_hdr_ident, the count / scan / rows / map kernels, k_hdr_rep.)
 //   k_gtx_rows    one lane per provisional row: the body is a map; for eras >= 4 the witness set's
 //                 first key 5 (ex_mem, ex_steps, both redeemer forms); tx_id = Blake2b-256 of the
 //                 body with the message blocks staged through LDS (arena.hpp b2b256_staged, as
@@ -83,28 +81,6 @@ __global__ void __launch_bounds__(NT) k_gtx_split(size_t n, const uint8_t* __res
     if (ok) b2b256_range(w, arena, r.off, r.len);
     store_words(d.hash + 32 * i, w, 8);
   }
-}
-
-// item_slot[i] = i and slot_min[i] = i for a flagged index below *limit (limit NULL: n), NONE
-// otherwise: k_hdr_count then finds every flagged index to be its own representative.  flag_ok:
-// the value of flag[i] that counts.
-__global__ void __launch_bounds__(NT) k_gtx_ident(size_t n, const uint32_t* __restrict__ limit,
-                                                  const uint8_t* __restrict__ flag, uint8_t flag_ok,
-                                                  uint32_t* __restrict__ item_slot, uint32_t* __restrict__ slot_min) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const bool in = (!limit || i < *limit) && flag[i] == flag_ok;
-  item_slot[i] = in ? (uint32_t)i : NONE;
-  slot_min[i] = (uint32_t)i;
-}
-
-__global__ void __launch_bounds__(NT) k_gtx_rep(size_t n, const uint32_t* __restrict__ item_slot,
-                                                const uint32_t* __restrict__ item_rep,
-                                                const uint32_t* __restrict__ rep_row, uint32_t* __restrict__ row_item) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || item_slot[i] == NONE || item_rep[i] != (uint32_t)i) return;
-  const uint32_t row = rep_row[i];
-  if (row < n) row_item[row] = (uint32_t)i;
 }
 
 // Provisional rows [0, *total).  tx_id: the workgroup hashes its 256 bodies together
@@ -201,18 +177,6 @@ void launch_gtx_split(hipStream_t stream, size_t n, const uint8_t* arena, uint64
                       const uint32_t* len, uint32_t n_eras, const praos_gtx_dev_items* items) {
   hipLaunchKernelGGL(k_gtx_split, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, stream, n, arena, arena_len, off,
                      len, n_eras, *items);
-}
-
-void launch_gtx_ident(hipStream_t stream, size_t n, const uint32_t* limit, const uint8_t* flag, uint8_t flag_ok,
-                      uint32_t* item_slot, uint32_t* slot_min) {
-  hipLaunchKernelGGL(k_gtx_ident, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, stream, n, limit, flag, flag_ok,
-                     item_slot, slot_min);
-}
-
-void launch_gtx_rep(hipStream_t stream, size_t n, const uint32_t* item_slot, const uint32_t* item_rep,
-                    const uint32_t* rep_row, uint32_t* row_item) {
-  hipLaunchKernelGGL(k_gtx_rep, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, stream, n, item_slot, item_rep,
-                     rep_row, row_item);
 }
 
 void launch_gtx_rows(hipStream_t stream, size_t n, const uint32_t* total, const uint8_t* arena, const uint32_t* row_item,

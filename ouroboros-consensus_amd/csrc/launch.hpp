@@ -338,31 +338,37 @@ void launch_selftest4_msm(hipStream_t stream, int variant, size_t n, const uint8
 // 0, 1, 3, 4 (kind 2 is launch_seg_hash); the tables are praos_hip.h's
 void launch_selftest_hash(hipStream_t stream, int kind, size_t n, const uint8_t* arena, const uint64_t* off,
                           const uint32_t* len, const uint8_t* aux, const uint64_t* parts, uint8_t* out);
-// wire headers (k_wire.hip): unwrap + header hash of n wire items (hash may be NULL), and the
-// header dedup of praos_validate_candidates -- slot_item / slot_min: (mask + 1) words each, zeroed
-// / set to 0xff by the caller; blk: one word per block of NT items; *total = distinct headers;
-// row_off / row_len: the representatives' inner spans in order of first appearance (rows <
-// rows_cap); item_row: each item's row (0xffffffff: none)
+// wire headers (k_wire.hip): unwrap + header hash of n wire items (hash may be NULL)
 void launch_wire_split(hipStream_t stream, size_t n, const uint8_t* arena, uint64_t arena_len, const uint64_t* off,
                        const uint32_t* len, uint32_t n_eras, uint8_t* status, uint8_t* era, uint8_t* kind,
                        uint32_t* hint, uint64_t* ioff, uint32_t* ilen, uint8_t* hash);
-void launch_hdr_dedup(hipStream_t stream, size_t n, const uint8_t* status, const uint8_t* era, const uint8_t* hash,
-                      uint32_t era_mask, uint32_t mask, uint32_t* slot_item, uint32_t* slot_min, uint32_t* item_slot,
-                      uint32_t* item_rep, uint32_t* blk, uint32_t* total, const uint64_t* ioff, const uint32_t* ilen,
-                      uint32_t rows_cap, uint64_t* row_off, uint32_t* row_len, uint32_t* rep_row, uint32_t* item_row);
-void launch_hdr_row_kind(hipStream_t stream, size_t n, const uint32_t* item_slot, const uint32_t* item_rep,
-                         const uint32_t* rep_row, const uint8_t* kind, uint32_t rows_cap, uint8_t* row_is_ebb);
-// launch_hdr_dedup without its hash set: the count / scan / rows / map kernels over item_slot and
-// slot_min as a caller filled them
+// the row set of the wire calls (k_wire.hip; api_internal.hpp RowSet holds the arrays): per-item
+// arrays of n entries, item_slot / slot_min say which class an item is in.  set: the hash set over
+// (tag, 32-byte key) of the items with flag[i] == 0 and tag[i] < 32 in tag_mask; slot_item /
+// slot_min: mask + 1 words each, a power of two >= 2n, zeroed / set to 0xff by the caller.  ident:
+// no set, every index below *limit (NULL: n) with flag[i] == flag_ok a class of its own; slot_min:
+// n words.  count: item_rep[i] = the lowest item of i's class; blk: one word per block of NT items.
+// number: count, then the rows in order of first appearance: *total = the rows; row_off / row_len:
+// the representatives' spans ioff / ilen (rows < rows_cap); rep_row: each representative's row;
+// item_row: each item's row (0xffffffff: none).  rep: row_item[row] = the row's representative
+// (row_item set to 0xff by the caller).  row_kind: row_is_ebb[row] = its kind is 0 (rows < rows_cap).
+void launch_hdr_set(hipStream_t stream, size_t n, const uint8_t* flag, const uint8_t* tag, const uint8_t* key,
+                    uint32_t tag_mask, uint32_t mask, uint32_t* slot_item, uint32_t* slot_min, uint32_t* item_slot);
+void launch_hdr_ident(hipStream_t stream, size_t n, const uint32_t* limit, const uint8_t* flag, uint8_t flag_ok,
+                      uint32_t* item_slot, uint32_t* slot_min);
+void launch_hdr_count(hipStream_t stream, size_t n, const uint32_t* item_slot, const uint32_t* slot_min,
+                      uint32_t* item_rep, uint32_t* blk);
 void launch_hdr_number(hipStream_t stream, size_t n, const uint32_t* item_slot, const uint32_t* slot_min,
                        uint32_t* item_rep, uint32_t* blk, uint32_t* total, const uint64_t* ioff, const uint32_t* ilen,
                        uint32_t rows_cap, uint64_t* row_off, uint32_t* row_len, uint32_t* rep_row, uint32_t* item_row);
+void launch_hdr_rep(hipStream_t stream, size_t n, const uint32_t* item_slot, const uint32_t* item_rep,
+                    const uint32_t* rep_row, uint32_t* row_item);
+void launch_hdr_row_kind(hipStream_t stream, size_t n, const uint32_t* item_slot, const uint32_t* item_rep,
+                         const uint32_t* rep_row, const uint8_t* kind, uint32_t rows_cap, uint8_t* row_is_ebb);
 // wire transactions (k_gentx.hip).  Per-item arrays of n entries (hash may be NULL) and the final
 // rows' arrays (n entries each: a call has at most n rows; block: zeros, the row_block of
 // launch_txw_count under a one-entry kind table).  split: unwrap, top-level walk, dedup hash.
-// ident: item_slot / slot_min for launch_hdr_number, every index below *limit (NULL: n) with
-// flag[i] == flag_ok a class of its own.  rep: row_item[row] = the row's representative (row_item
-// set to 0xff by the caller).  rows: provisional rows [0, *total): row_ok, the ExUnits sums, tx_id.
+// rows: provisional rows [0, *total): row_ok, the ExUnits sums, tx_id.
 // final: the kept rows' fields at row_final[row]; item_row from provisional to final rows, the
 // items of refused rows PRAOS_GTX_SHAPE.
 struct praos_gtx_dev_items {
@@ -400,10 +406,6 @@ struct praos_gtx_dev_rows {
 };
 void launch_gtx_split(hipStream_t stream, size_t n, const uint8_t* arena, uint64_t arena_len, const uint64_t* off,
                       const uint32_t* len, uint32_t n_eras, const praos_gtx_dev_items* items);
-void launch_gtx_ident(hipStream_t stream, size_t n, const uint32_t* limit, const uint8_t* flag, uint8_t flag_ok,
-                      uint32_t* item_slot, uint32_t* slot_min);
-void launch_gtx_rep(hipStream_t stream, size_t n, const uint32_t* item_slot, const uint32_t* item_rep,
-                    const uint32_t* rep_row, uint32_t* row_item);
 void launch_gtx_rows(hipStream_t stream, size_t n, const uint32_t* total, const uint8_t* arena, const uint32_t* row_item,
                      const praos_gtx_dev_items* items, uint8_t* row_ok, uint64_t* ex_mem, uint64_t* ex_steps,
                      uint8_t* tx_id);
@@ -414,9 +416,10 @@ void launch_gtx_final(hipStream_t stream, size_t n, const uint32_t* total, const
 // wire blocks (k_blockfetch.hip).  unwrap: status, disk tag and inner span of n wire items; hoff /
 // hlen: the inner span again, launch_block_split's in / out columns.  key: elig[i] = 0 for an item
 // that splits and decodes (1 otherwise) and, key != NULL, the hash set's key (header hash with the
-// inner length folded in); *any_byron = 1 when such an item has disk tag 0 or 1.  class: one wave per item over launch_hdr_dedup's item_slot / item_rep:
-// slot2 / min2 for launch_hdr_number, a member that differs from its representative in a byte a
-// class of its own.  rows: the representatives' columns at rep_row (R rows; seg_off / seg_len
+// inner length folded in); *any_byron = 1 when such an item has disk tag 0 or 1.  class: one wave
+// per item over launch_hdr_set's item_slot and launch_hdr_count's item_rep: slot2 / min2 for
+// launch_hdr_number, a member that differs from its representative in a byte a class of its own.
+// rows: the representatives' columns at rep_row (R rows; seg_off / seg_len
 // segment-major over R).  bits: a Byron row's bits, which and zero body hash from
 // launch_byron_integrity's results (NULL: Byron off).  verdict: PRAOS_BF_* per item, then which[]
 // loses its host-internal flag.  span_equal: out[i] = the spans a and b of len[i] bytes are equal.

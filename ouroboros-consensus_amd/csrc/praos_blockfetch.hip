@@ -3,9 +3,10 @@
 //
 // One call: the arena, the spans and the expected points up; k_bf_unwrap; the stored-block splits
 // and header decoders over the inner spans (k_block_split + k_decode_praos, k_byron_split with
-// Byron on); k_bf_key; with dedup k_wire.hip's hash set over (tag, header hash, length) and
-// k_bf_class, which compares every other member of a class with its representative, without it
-// k_gtx_ident; k_wire.hip's numbering gives the rows in order of first appearance.  The host
+// Byron on); k_bf_key; the row set of api_internal.hpp: with dedup its hash set over (tag, header
+// hash, length), the representatives (count) and k_bf_class, which compares every other member of a
+// class with its representative and writes the classes that are numbered; without it ident.  The
+// numbering gives the rows in order of first appearance.  The host
 // waits for the row count (it sizes the row arrays: the first round trip).  Then k_bf_rows, the
 // segment hashes and the join over the rows with no KES launch, the Byron body proof of the
 // Byron rows, k_bf_bits, k_bf_verdict, the downloads and the fold per range on the host.  With
@@ -50,18 +51,14 @@ int bf_run(praos_ctx* c, const praos_header_bytes* in, const praos_bf_ranges* rg
     for (uint64_t j = 0; i0 + j < rg->item_first[r + 1]; j++)
       h_exp[i0 + j] = j < points ? (uint32_t)(rg->exp_first[r] + j) : 0xffffffffu;
   }
-  uint32_t tab = 2;
-  while (tab < 2 * n) tab <<= 1;
-  const size_t nb = (n + NT - 1) / NT, ns = std::max<size_t>(tab, n);
   const size_t arena_sz = arena_room(bytes);
   uint8_t* arena = nullptr;
   uint64_t *d_off = nullptr, *ioff = nullptr, *hoff = nullptr, *seg_off = nullptr, *slot = nullptr, *block_no = nullptr,
            *ocert_n = nullptr, *ocert_c0 = nullptr, *body_off = nullptr, *pmaj = nullptr, *pmin = nullptr,
-           *b_epoch = nullptr, *row_off = nullptr, *off_scratch = nullptr, *exp_slot = nullptr;
+           *b_epoch = nullptr, *row_off = nullptr, *exp_slot = nullptr;
   uint32_t *d_len = nullptr, *ilen = nullptr, *hlen = nullptr, *seg_len = nullptr, *body_len = nullptr, *body_size = nullptr,
-           *row_len = nullptr, *len_scratch = nullptr, *item_slot = nullptr, *item_rep = nullptr, *rep_row = nullptr,
-           *item_row = nullptr, *slot2 = nullptr, *min2 = nullptr, *bcnt = nullptr, *total = nullptr, *slot_item = nullptr,
-           *slot_min = nullptr, *exp_idx = nullptr, *row_scratch = nullptr;
+           *row_len = nullptr, *slot2 = nullptr, *min2 = nullptr, *total = nullptr, *exp_idx = nullptr;
+  RowSet rs;
   uint8_t *status = nullptr, *tag = nullptr, *nseg = nullptr, *split = nullptr, *kind = nullptr, *elig = nullptr,
           *key = nullptr, *cold = nullptr, *vrf_vk = nullptr, *vrf_out = nullptr, *vrf_proof = nullptr, *hot = nullptr,
           *ocert_sig = nullptr, *kes_sig = nullptr, *signed_body = nullptr, *prev = nullptr, *gen = nullptr,
@@ -111,21 +108,12 @@ int bf_run(praos_ctx* c, const praos_header_bytes* in, const praos_bf_ranges* rg
         // classes and rows
         elig = m.take<uint8_t>(n);
         key = m.take<uint8_t>(32 * n);
-        item_slot = m.take<uint32_t>(4 * n);
-        item_rep = m.take<uint32_t>(4 * n);
-        rep_row = m.take<uint32_t>(4 * n);
-        item_row = m.take<uint32_t>(4 * n);
-        row_scratch = m.take<uint32_t>(4 * n);
+        rs.layout(m, n);
         slot2 = m.take<uint32_t>(4 * n);
         min2 = m.take<uint32_t>(4 * n);
         row_off = m.take<uint64_t>(8 * n);
         row_len = m.take<uint32_t>(4 * n);
-        off_scratch = m.take<uint64_t>(8 * n);
-        len_scratch = m.take<uint32_t>(4 * n);
-        bcnt = m.take<uint32_t>(4 * nb);
-        total = m.take<uint32_t>(16);                            // rows, the hash set's own count, any Byron item with a row
-        slot_item = m.take<uint32_t>(4 * (size_t)tab);
-        slot_min = m.take<uint32_t>(4 * ns);
+        total = m.take<uint32_t>(16);                            // [0] rows, [2] any Byron item with a row
         exp_idx = m.take<uint32_t>(4 * n);
         exp_slot = m.take<uint64_t>(8 * E);
         exp_hash = m.take<uint8_t>(32 * E);
@@ -135,10 +123,9 @@ int bf_run(praos_ctx* c, const praos_header_bytes* in, const praos_bf_ranges* rg
     return PRAOS_E_OOM;
   }
   (void)hipGetLastError();
-  HIPCHK(c, hipMemsetAsync(arena + bytes, 0, arena_sz - bytes, s));
+  HIPCHK(c, pad_zero(arena, bytes, s));
   if (bytes) HIPCHK(c, praos_impl::h2d(c, arena, in->bytes, bytes));
-  HIPCHK(c, hipMemcpyAsync(d_off, in->off, 8 * n, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(d_len, in->len, 4 * n, hipMemcpyHostToDevice, s));
+  HIPCHK(c, items_upload(*in, d_off, d_len, s));
   HIPCHK(c, hipMemcpyAsync(exp_idx, h_exp.data(), 4 * n, hipMemcpyHostToDevice, s));
   if (E) {
     HIPCHK(c, hipMemcpyAsync(exp_slot, rg->exp_slot, 8 * E, hipMemcpyHostToDevice, s));
@@ -158,20 +145,20 @@ int bf_run(praos_ctx* c, const praos_header_bytes* in, const praos_bf_ranges* rg
   HIPCHK(c, hipGetLastError());
   // ---- rows: one per distinct block, in order of first appearance
   launch_bf_key(s, n, status, split, dec, tag, ilen, hh, elig, cfg->dedup ? key : nullptr, total + 2);
+  // (the classes that are numbered are slot2 / min2: the hash set's with the deviants k_bf_class
+  // found taken out, each a class of its own)
+  RowSet cls = rs;
+  cls.item_slot = slot2;
+  cls.slot_min = min2;
   if (cfg->dedup) {
-    // launch_hdr_dedup is used for its hash set alone (item_slot, item_rep): its own numbering --
-    // total[1], off_scratch, len_scratch, rep_row, row_scratch -- is discarded, because the rows
-    // are known only after k_bf_class has taken the deviants out; launch_hdr_number numbers them
-    HIPCHK(c, hipMemsetAsync(slot_item, 0, 4 * (size_t)tab, s));
-    HIPCHK(c, hipMemsetAsync(slot_min, 0xff, 4 * (size_t)tab, s));
-    launch_hdr_dedup(s, n, elig, tag, key, 0xffffffffu, tab - 1, slot_item, slot_min, item_slot, item_rep, bcnt, total + 1,
-                     ioff, ilen, (uint32_t)n, off_scratch, len_scratch, rep_row, row_scratch);
-    launch_bf_class(s, n, arena, item_slot, item_rep, ioff, ilen, slot2, min2);
+    HIPCHK(c, rs.reset(s));
+    rs.set(s, elig, tag, key, 0xffffffffu);
+    rs.count(s);
+    launch_bf_class(s, n, arena, rs.item_slot, rs.item_rep, ioff, ilen, slot2, min2);
   } else {
-    launch_gtx_ident(s, n, nullptr, elig, 0, slot2, min2);
+    cls.ident(s, nullptr, elig, 0);
   }
-  launch_hdr_number(s, n, slot2, min2, item_rep, bcnt, total, ioff, ilen, (uint32_t)n, row_off, row_len, rep_row,
-                    item_row);
+  cls.number(s, total, ioff, ilen, row_off, row_len);
   HIPCHK(c, hipGetLastError());
   uint32_t h_total[3] = {0, 0, 0};
   HIPCHK(c, hipMemcpyAsync(h_total, total, 12, hipMemcpyDeviceToHost, s));
@@ -224,7 +211,7 @@ int bf_run(praos_ctx* c, const praos_header_bytes* in, const praos_bf_ranges* rg
     (void)hipGetLastError();
     HIPCHK(c, hipMemsetAsync(r_zero, 0, 2 * R, s));
     const praos_bf_dev_items d{tag, kind, slot, block_no, hoff, hlen, hh, prev, claimed, nseg, seg_off, seg_len};
-    launch_bf_rows(s, n, R, slot2, rep_row, &d, &o);
+    launch_bf_rows(s, n, R, slot2, rs.rep_row, &d, &o);
     const dim3 gr(nblocks(R, NT));
     launch_seg_hash(dim3(nblocks(4 * R, NT)), blk, s, R, arena, o.seg_off, o.seg_len, o.nseg, r_seg_hash);
     launch_block_join(gr, blk, s, R, o.nseg, r_zero, (const uint16_t*)r_zero, (const uint16_t*)r_zero, r_seg_hash,
@@ -243,19 +230,17 @@ int bf_run(praos_ctx* c, const praos_header_bytes* in, const praos_bf_ranges* rg
     }
     launch_bf_bits(s, R, o.tag, r_bres, r_bwhich, r_bits, r_which, r_calc);
   }
-  launch_bf_verdict(s, n, R, byron ? 1 : 0, status, tag, item_row, exp_idx, exp_slot, exp_hash, slot, hh, r_bits, r_which,
+  launch_bf_verdict(s, n, R, byron ? 1 : 0, status, tag, rs.item_row, exp_idx, exp_slot, exp_hash, slot, hh, r_bits, r_which,
                     verdict);
   HIPCHK(c, hipGetLastError());
   // ---- the downloads and the fold
-  auto down = [&](void* dst, const void* src, size_t b) {
-    return dst && b ? hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, s) : hipSuccess;
-  };
+  const Down down{s};
   std::vector<uint8_t> h_verdict(n);
   HIPCHK(c, down(h_verdict.data(), verdict, n));
   if (po) {
     HIPCHK(c, down(po->status, status, n));
     HIPCHK(c, down(po->tag, tag, n));
-    HIPCHK(c, down(po->row, item_row, 4 * n));
+    HIPCHK(c, down(po->row, rs.item_row, 4 * n));
   }
   const bool short_r = any_row_array(rows) && rows->cap < R;
   if (any_row_array(rows) && !short_r && R) {
@@ -311,7 +296,7 @@ extern "C" int praos_verify_fetched_blocks(praos_ctx* c, const praos_header_byte
     return PRAOS_E_ARG;
   }
   const size_t n = items->n;
-  if (n && (!items->off || !items->len || (items->bytes_len && !items->bytes))) return PRAOS_E_ARG;
+  if (n && !items_ok(items)) return PRAOS_E_ARG;
   if (n > (1ull << 30)) { c->err = "praos_verify_fetched_blocks: too many items in one call"; return PRAOS_E_ARG; }
   if (!rg->item_first || !rg->exp_first || rg->item_first[0] != 0 || rg->item_first[rg->k] != n ||
       rg->exp_first[0] != 0 || rg->exp_first[rg->k] > 0x7fffffffull ||

@@ -1,13 +1,13 @@
 // praos_candidates.hip -- headers as the ChainSync client receives them (call
-// stack 3): host C++ on top of the wire kernels (k_wire.hip) and the internal from-bytes batch of
-// replay_internal.hpp.
+// stack 3): host C++ on top of the wire kernels (k_wire.hip), the row set of api_internal.hpp and
+// the internal from-bytes batch of replay_internal.hpp.
 //
 //   praos_unwrap_wire_headers   every era: the inner header span and the header hash of each
 //                               wire item (k_wire_split).
 //   praos_validate_candidates   K candidate fragments of Praos wire headers, each from its own
 //                               HeaderState (MiniProtocol/ChainSync/Client.hs:794-812):
-//     device   k_wire_split, k_hdr_dedup (+ the scan that numbers the distinct headers in order of
-//              first appearance and writes their spans into the batch's span arrays),
+//     device   k_wire_split, the row set (its hash set, then the numbering of the distinct headers
+//              in order of first appearance, which writes their spans into the row span arrays),
 //              k_decode_praos and k_vrf_nonce over those rows only;
 //     host     the speculative nonce chain of each fragment from its own state (the replay's
 //              chain thread: tick, candidate freeze, epoch nonce per header), which gives every
@@ -25,64 +25,22 @@
 //                               praos_verify_pbft_headers' kernels over the distinct headers read
 //                               from the wire arena, and the PBFT fold in the client's mode.
 // All three share the front half (front_begin / front_run): only the era mask differs.
-#include <hip/hip_runtime.h>
+#include "api_internal.hpp"
 
-#include "praos_hip.h"
-#include "launch.hpp"
-#include "host_util.hpp"
-#include "replay_internal.hpp"
-
-#include <algorithm>
 #include <atomic>
-#include <cstring>
-#include <functional>
-#include <mutex>
-#include <string>
-#include <thread>
 #include <unordered_map>
-#include <vector>
 
 namespace {
 
-constexpr size_t NT_ITEMS = 256;               // items per block of the k_hdr_* kernels (kcommon.hpp NT)
 constexpr uint32_t NONE = PRAOS_NO_ROW;
 constexpr unsigned MAX_FOLD_THREADS = 16;
-
-#define CHIP(c, x)                                                              \
-  do {                                                                          \
-    hipError_t e_ = (x);                                                        \
-    if (e_ != hipSuccess) {                                                     \
-      praos_set_error_((c), std::string(#x) + ": " + hipGetErrorString(e_));    \
-      return PRAOS_E_HIP;                                                       \
-    }                                                                           \
-  } while (0)
-
-// one device allocation carved into 256-byte aligned pieces (own: freed with the Carve)
-struct Carve {
-  uint8_t* base = nullptr;
-  size_t size = 0, used = 0;
-  bool own = false;
-  ~Carve() {
-    if (base && own) (void)hipFree(base);
-  }
-  static size_t up(size_t b) { return (b + 255) & ~(size_t)255; }
-  template <typename T>
-  T* take(size_t bytes) {
-    T* p = (T*)(base + used);
-    used += up(bytes);
-    return p;
-  }
-};
 
 // the item-side buffers of both entry points
 struct ItemBufs {
   uint64_t *off, *ioff;
   uint32_t *len, *hint, *ilen;
   uint8_t *status, *era, *kind, *hash;
-  static size_t bytes(size_t n) {
-    return 2 * Carve::up(8 * n) + 3 * Carve::up(4 * n) + 3 * Carve::up(n) + Carve::up(32 * n);
-  }
-  void carve(Carve& m, size_t n) {
+  void layout(Carve& m, size_t n) {
     off = m.take<uint64_t>(8 * n); ioff = m.take<uint64_t>(8 * n);
     len = m.take<uint32_t>(4 * n); hint = m.take<uint32_t>(4 * n); ilen = m.take<uint32_t>(4 * n);
     status = m.take<uint8_t>(n); era = m.take<uint8_t>(n); kind = m.take<uint8_t>(n);
@@ -90,9 +48,8 @@ struct ItemBufs {
   }
 };
 
-bool items_ok(const praos_header_bytes* s) {
-  return s && (s->n == 0 || (s->off && s->len)) && (s->bytes_len == 0 || s->bytes) && s->n < (1ull << 30);
-}
+// a call takes fewer than 2^30 items
+bool cand_items_ok(const praos_header_bytes* s) { return items_ok(s) && s->n < (1ull << 30); }
 
 // runs f(j) for j in [0, k) on at most min(k, 16) threads (never sized by the machine's cores)
 void par_for(size_t k, const std::function<void(size_t)>& f) {
@@ -111,9 +68,9 @@ void par_for(size_t k, const std::function<void(size_t)>& f) {
 }
 
 // ---- the front half of every candidates call: the wire items go up once, are unwrapped and hashed
-// (k_wire_split), byte-identical headers of the eras in era_mask are found (k_hdr_dedup) and
-// numbered in order of first appearance (the scan kernels), and wire_status, the item-to-row map
-// and the row count come back.  The era mask is all that differs between the calls.
+// (k_wire_split), byte-identical headers of the eras in era_mask are found and numbered in order
+// of first appearance (the row set), and wire_status, the item-to-row map and the row count come
+// back.  The era mask is all that differs between the calls.
 bool frag_bounds_ok(const size_t* frag_first, size_t k, bool have_frags, size_t n) {
   return frag_first && (k == 0 || have_frags) && frag_first[0] == 0 && frag_first[k] == n;
 }
@@ -122,7 +79,7 @@ bool frag_bounds_ok(const size_t* frag_first, size_t k, bool have_frags, size_t 
 // context's streams
 int front_begin(praos_ctx* c, bool need_epoch) {
   if (praos_host_only_(c)) return PRAOS_E_STATE;
-  if (need_epoch && !rp_have_epoch(c)) { praos_set_error_(c, "candidates: no epoch installed (praos_set_epoch)"); return PRAOS_E_STATE; }
+  if (need_epoch && !c->have_epoch) { praos_set_error_(c, "candidates: no epoch installed (praos_set_epoch)"); return PRAOS_E_STATE; }
   return praos_verify_drain(c);
 }
 
@@ -141,34 +98,26 @@ struct Front {
 int front_run(praos_ctx* c, const praos_header_bytes& items, uint32_t n_eras, uint32_t era_mask, bool row_kind,
               uint8_t* wire_status, Front& f) {
   const size_t N = items.n, bytes = items.bytes_len;
-  CHIP(c, hipSetDevice(rp_device(c)));
-  hipStream_t st = rp_copy_stream(c);
-  // the hash set: a power of two, at least 2N slots
-  uint32_t tab = 2;
-  while (tab < 2 * N) tab <<= 1;
-  const size_t nb = (N + NT_ITEMS - 1) / NT_ITEMS;
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t st = c->cstream;
   // one device buffer, kept with the context between calls: the wire arena (with ld64u's pad), the
-  // item buffers, the dedup's arrays and the rows' spans and kinds (at most N rows)
-  const size_t arena_sz = arena_room(bytes);
-  Carve m;
-  m.size = Carve::up(arena_sz) + ItemBufs::bytes(N) + 4 * Carve::up(4 * N) + Carve::up(4 * nb) + Carve::up(4) +
-           2 * Carve::up(4 * (size_t)tab) + Carve::up(8 * N) + Carve::up(4 * N) + Carve::up(N);
-  m.base = rp_scratch(c, m.size);
-  if (!m.base) { praos_set_error_(c, "candidates: device allocation failed"); return PRAOS_E_OOM; }
-  f.arena = m.take<uint8_t>(arena_sz);
+  // item buffers, the row set and the rows' spans and kinds (room for N: the extra (header, nonce)
+  // rows of the Praos calls are written behind the R distinct ones, R2 <= N in all)
   ItemBufs& d = f.d;
-  d.carve(m, N);
-  uint32_t* item_slot = m.take<uint32_t>(4 * N);
-  uint32_t* item_rep = m.take<uint32_t>(4 * N);
-  uint32_t* rep_row = m.take<uint32_t>(4 * N);
-  uint32_t* item_row = m.take<uint32_t>(4 * N);
-  uint32_t* blk = m.take<uint32_t>(4 * nb);
-  uint32_t* total = m.take<uint32_t>(4);
-  uint32_t* slot_item = m.take<uint32_t>(4 * (size_t)tab);
-  uint32_t* slot_min = m.take<uint32_t>(4 * (size_t)tab);
-  f.d_row_off = m.take<uint64_t>(8 * N);
-  f.d_row_len = m.take<uint32_t>(4 * N);
-  f.d_row_ebb = m.take<uint8_t>(N);
+  RowSet rs;
+  uint32_t* total = nullptr;
+  if (!carve_kept(c, [&](Carve& m) {
+        f.arena = m.take<uint8_t>(arena_room(bytes));
+        d.layout(m, N);
+        rs.layout(m, N);
+        total = m.take<uint32_t>(4);
+        f.d_row_off = m.take<uint64_t>(8 * N);
+        f.d_row_len = m.take<uint32_t>(4 * N);
+        f.d_row_ebb = m.take<uint8_t>(N);
+      })) {
+    praos_set_error_(c, "candidates: device allocation failed");
+    return PRAOS_E_OOM;
+  }
 
   const praos_span whole{items.bytes, bytes};
   f.R = 0;
@@ -177,19 +126,17 @@ int front_run(praos_ctx* c, const praos_header_bytes& items, uint32_t n_eras, ui
     const int rc = rp_upload_bytes(c, f.arena, &whole, bytes ? 1 : 0);
     if (rc != PRAOS_OK) return rc;
   }
-  CHIP(c, hipMemcpyAsync(d.off, items.off, 8 * N, hipMemcpyHostToDevice, st));
-  CHIP(c, hipMemcpyAsync(d.len, items.len, 4 * N, hipMemcpyHostToDevice, st));
-  CHIP(c, hipMemsetAsync(slot_item, 0, 4 * (size_t)tab, st));
-  CHIP(c, hipMemsetAsync(slot_min, 0xff, 4 * (size_t)tab, st));
+  HIPCHK(c, items_upload(items, d.off, d.len, st));
+  HIPCHK(c, rs.reset(st));
   launch_wire_split(st, N, f.arena, bytes, d.off, d.len, n_eras, d.status, d.era, d.kind, d.hint, d.ioff, d.ilen, d.hash);
-  launch_hdr_dedup(st, N, d.status, d.era, d.hash, era_mask, tab - 1, slot_item, slot_min, item_slot, item_rep, blk, total,
-                   d.ioff, d.ilen, (uint32_t)N, f.d_row_off, f.d_row_len, rep_row, item_row);
-  if (row_kind) launch_hdr_row_kind(st, N, item_slot, item_rep, rep_row, d.kind, (uint32_t)N, f.d_row_ebb);
-  CHIP(c, hipGetLastError());
-  CHIP(c, hipMemcpyAsync(&f.R, total, 4, hipMemcpyDeviceToHost, st));
-  CHIP(c, hipMemcpyAsync(wire_status, d.status, N, hipMemcpyDeviceToHost, st));
-  CHIP(c, hipMemcpyAsync(f.base_row.data(), item_row, 4 * N, hipMemcpyDeviceToHost, st));
-  CHIP(c, hipStreamSynchronize(st));
+  rs.set(st, d.status, d.era, d.hash, era_mask);
+  rs.number(st, total, d.ioff, d.ilen, f.d_row_off, f.d_row_len);
+  if (row_kind) launch_hdr_row_kind(st, N, rs.item_slot, rs.item_rep, rs.rep_row, d.kind, (uint32_t)N, f.d_row_ebb);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(&f.R, total, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(wire_status, d.status, N, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(f.base_row.data(), rs.item_row, 4 * N, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
   return PRAOS_OK;
 }
 
@@ -197,7 +144,7 @@ int front_run(praos_ctx* c, const praos_header_bytes& items, uint32_t n_eras, ui
 
 extern "C" int praos_unwrap_wire_headers(praos_ctx* c, const praos_header_bytes* items, uint32_t n_eras,
                                          praos_wire_out* out) {
-  if (!c || !items_ok(items) || !out) return PRAOS_E_ARG;
+  if (!c || !cand_items_ok(items) || !out) return PRAOS_E_ARG;
   const size_t n = items->n, bytes = items->bytes_len;
   if (n && (!out->status || !out->era || !out->byron_kind || !out->size_hint || !out->off || !out->len)) {
     praos_set_error_(c, "unwrap: status, era, byron_kind, size_hint, off and len are required");
@@ -205,31 +152,30 @@ extern "C" int praos_unwrap_wire_headers(praos_ctx* c, const praos_header_bytes*
   }
   if (praos_host_only_(c)) return PRAOS_E_STATE;
   if (n == 0) return PRAOS_OK;
-  CHIP(c, hipSetDevice(rp_device(c)));
-  hipStream_t st = rp_copy_stream(c);
-  Carve m;
-  const size_t arena_sz = arena_room(bytes);     // ld64u's pad (arena.hpp)
-  m.size = Carve::up(arena_sz) + ItemBufs::bytes(n);
-  CHIP(c, hipMalloc((void**)&m.base, m.size));
-  m.own = true;
-  uint8_t* arena = m.take<uint8_t>(arena_sz);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t st = c->cstream;
+  uint8_t* arena = nullptr;
   ItemBufs d;
-  d.carve(m, n);
-  CHIP(c, hipMemsetAsync(arena + bytes, 0, arena_sz - bytes, st));
-  if (bytes) CHIP(c, hipMemcpyAsync(arena, items->bytes, bytes, hipMemcpyHostToDevice, st));
-  CHIP(c, hipMemcpyAsync(d.off, items->off, 8 * n, hipMemcpyHostToDevice, st));
-  CHIP(c, hipMemcpyAsync(d.len, items->len, 4 * n, hipMemcpyHostToDevice, st));
+  DevBuf buf;
+  const hipError_t device_allocation = carve_alloc(buf, [&](Carve& m) {
+    arena = m.take<uint8_t>(arena_room(bytes));     // ld64u's pad (arena.hpp)
+    d.layout(m, n);
+  });
+  HIPCHK(c, device_allocation);
+  HIPCHK(c, pad_zero(arena, bytes, st));
+  if (bytes) HIPCHK(c, hipMemcpyAsync(arena, items->bytes, bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(c, items_upload(*items, d.off, d.len, st));
   launch_wire_split(st, n, arena, bytes, d.off, d.len, n_eras, d.status, d.era, d.kind, d.hint, d.ioff, d.ilen,
                     out->header_hash ? d.hash : nullptr);
-  CHIP(c, hipGetLastError());
-  CHIP(c, hipMemcpyAsync(out->status, d.status, n, hipMemcpyDeviceToHost, st));
-  CHIP(c, hipMemcpyAsync(out->era, d.era, n, hipMemcpyDeviceToHost, st));
-  CHIP(c, hipMemcpyAsync(out->byron_kind, d.kind, n, hipMemcpyDeviceToHost, st));
-  CHIP(c, hipMemcpyAsync(out->size_hint, d.hint, 4 * n, hipMemcpyDeviceToHost, st));
-  CHIP(c, hipMemcpyAsync(out->off, d.ioff, 8 * n, hipMemcpyDeviceToHost, st));
-  CHIP(c, hipMemcpyAsync(out->len, d.ilen, 4 * n, hipMemcpyDeviceToHost, st));
-  if (out->header_hash) CHIP(c, hipMemcpyAsync(out->header_hash, d.hash, 32 * n, hipMemcpyDeviceToHost, st));
-  CHIP(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out->status, d.status, n, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out->era, d.era, n, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out->byron_kind, d.kind, n, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out->size_hint, d.hint, 4 * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out->off, d.ioff, 8 * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out->len, d.ilen, 4 * n, hipMemcpyDeviceToHost, st));
+  if (out->header_hash) HIPCHK(c, hipMemcpyAsync(out->header_hash, d.hash, 32 * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
   return PRAOS_OK;
 }
 
@@ -350,7 +296,7 @@ int candidates_impl(praos_ctx* c, const praos_candidates_in* in, bool tpraos, co
     const int rc = front_run(c, in->items, in->n_eras, era_mask, false, out->wire_status, f);
     if (rc != PRAOS_OK) return rc;
   }
-  hipStream_t st = rp_copy_stream(c);
+  hipStream_t st = c->cstream;
   uint8_t* const arena = f.arena;
   uint64_t* const d_row_off = f.d_row_off;
   uint32_t* const d_row_len = f.d_row_len;
@@ -376,8 +322,8 @@ int candidates_impl(praos_ctx* c, const praos_candidates_in* in, bool tpraos, co
     int rc = rp_decode_rows(c, b, arena, bytes, d_row_off, d_row_len, 0, R);
     if (rc != PRAOS_OK) return rc;
     if (R) {
-      CHIP(c, hipMemcpyAsync(row_off.data(), d_row_off, 8 * (size_t)R, hipMemcpyDeviceToHost, st));
-      CHIP(c, hipMemcpyAsync(row_len.data(), d_row_len, 4 * (size_t)R, hipMemcpyDeviceToHost, st));
+      HIPCHK(c, hipMemcpyAsync(row_off.data(), d_row_off, 8 * (size_t)R, hipMemcpyDeviceToHost, st));
+      HIPCHK(c, hipMemcpyAsync(row_len.data(), d_row_len, 4 * (size_t)R, hipMemcpyDeviceToHost, st));
     }
     rc = rp_download_decoded(c, b, &dec, &nonce_h);            // (synchronises the copy stream)
     if (rc != PRAOS_OK) return rc;
@@ -459,8 +405,8 @@ int candidates_impl(praos_ctx* c, const praos_candidates_in* in, bool tpraos, co
   {
     for (size_t x = 0; x < extra_base.size(); x++) { xoff[x] = row_off[extra_base[x]]; xlen[x] = row_len[extra_base[x]]; }
     if (!xoff.empty()) {                         // (R2 <= N: the span arrays have room)
-      CHIP(c, hipMemcpyAsync(d_row_off + R, xoff.data(), 8 * xoff.size(), hipMemcpyHostToDevice, st));
-      CHIP(c, hipMemcpyAsync(d_row_len + R, xlen.data(), 4 * xlen.size(), hipMemcpyHostToDevice, st));
+      HIPCHK(c, hipMemcpyAsync(d_row_off + R, xoff.data(), 8 * xoff.size(), hipMemcpyHostToDevice, st));
+      HIPCHK(c, hipMemcpyAsync(d_row_len + R, xlen.data(), 4 * xlen.size(), hipMemcpyHostToDevice, st));
     }
     int rc;
     if (rp_batch_fits(b, R2, 0)) {
@@ -616,7 +562,7 @@ int candidates_impl(praos_ctx* c, const praos_candidates_in* in, bool tpraos, co
 
 extern "C" int praos_validate_candidates(praos_ctx* c, const praos_candidates_in* in, praos_fragments* frags,
                                          praos_candidates_out* out) {
-  if (!c || !in || !frags || !out || !items_ok(&in->items)) return PRAOS_E_ARG;
+  if (!c || !in || !frags || !out || !cand_items_ok(&in->items)) return PRAOS_E_ARG;
   praos_candidates_in a = *in;
   if (!a.praos_eras) a.praos_eras = (1u << 5) | (1u << 6);
   const CandOut o{out->wire_status, out->row, out->verdict, nullptr, out->rows_cap, &out->n_rows, out->eta_idx, out->etas,
@@ -630,7 +576,7 @@ extern "C" int praos_validate_candidates(praos_ctx* c, const praos_candidates_in
 // The overlay installed with praos_set_overlay applies as in every TPraos batch.
 extern "C" int praos_validate_candidates_tpraos(praos_ctx* c, const praos_tpraos_candidates_in* in,
                                                 praos_fragments* frags, praos_tpraos_candidates_out* out) {
-  if (!c || !in || !frags || !out || !items_ok(&in->items)) return PRAOS_E_ARG;
+  if (!c || !in || !frags || !out || !cand_items_ok(&in->items)) return PRAOS_E_ARG;
   praos_candidates_in a{};
   a.items = in->items;
   a.n_eras = in->n_eras;
@@ -652,7 +598,7 @@ extern "C" int praos_validate_candidates_tpraos(praos_ctx* c, const praos_tpraos
 //     host     the PBFT fold per fragment in the client's mode, through the item-to-row map.
 extern "C" int praos_validate_candidates_pbft(praos_ctx* c, const praos_pbft_candidates_in* in,
                                               praos_pbft_fragments* frags, praos_pbft_candidates_out* out) {
-  if (!c || !in || !frags || !out || !items_ok(&in->items)) return PRAOS_E_ARG;
+  if (!c || !in || !frags || !out || !cand_items_ok(&in->items)) return PRAOS_E_ARG;
   const size_t N = in->items.n, K = frags->k, bytes = in->items.bytes_len;
   const praos_pbft_params& p = in->params;
   if (!frag_bounds_ok(frags->frag_first, K, frags->frag != nullptr, N) || p.epoch_slots == 0 || p.window_size == 0 ||
@@ -715,7 +661,7 @@ extern "C" int praos_validate_candidates_pbft(praos_ctx* c, const praos_pbft_can
   praos_pbft_out rows{r_bits.data(), r_gk.data(), r_slot.data(), r_bno.data(), r_prev.data(), r_gen.data(), r_hh.data(),
                       out->rows.delegate_hash ? r_dh.data() : nullptr};
   if (R) {
-    CHIP(c, hipMemcpy(r_ebb.data(), f.d_row_ebb, R, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(r_ebb.data(), f.d_row_ebb, R, hipMemcpyDeviceToHost));
     const int rc = rp_pbft_verify_rows(c, R, f.arena, bytes, f.d_row_off, f.d_row_len, f.d_row_ebb, &p, in->delegs,
                                        in->n_delegs, &rows);
     if (rc != PRAOS_OK) return rc;

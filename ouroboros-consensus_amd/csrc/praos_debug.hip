@@ -722,4 +722,56 @@ int praos_debug_span_equal(praos_ctx* c, size_t n, const uint8_t* arena, size_t 
   return PRAOS_OK;
 }
 
+int praos_debug_row_set(praos_ctx* c, size_t n, const uint8_t* flag, const uint8_t* tag, const uint8_t* key32,
+                        uint32_t tag_mask, int dedup, const uint32_t* limit, uint32_t* item_row, uint32_t* n_rows) {
+  if (!c || !n_rows || n >= (1u << 24)) return PRAOS_E_ARG;
+  *n_rows = 0;
+  if (n == 0) return PRAOS_OK;
+  if (!flag || !item_row || (dedup && (!tag || !key32))) return PRAOS_E_ARG;
+  if (praos_host_only_(c)) return PRAOS_E_STATE;
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  RowSet rs;
+  uint8_t *d_flag = nullptr, *d_tag = nullptr, *d_key = nullptr;
+  uint64_t *ioff = nullptr, *row_off = nullptr;          // the spans the numbering compacts: zeros here
+  uint32_t *ilen = nullptr, *row_len = nullptr, *total = nullptr, *d_limit = nullptr;
+  size_t spans_at = 0, spans_end = 0;
+  DevBuf buf;
+  if (carve_alloc(buf, [&](Carve& m) {
+        rs.layout(m, n);
+        d_flag = m.take<uint8_t>(n);
+        d_tag = m.take<uint8_t>(n);
+        d_key = m.take<uint8_t>(32 * n);
+        total = m.take<uint32_t>(4);
+        d_limit = m.take<uint32_t>(4);
+        spans_at = m.off;
+        ioff = m.take<uint64_t>(8 * n);
+        ilen = m.take<uint32_t>(4 * n);
+        row_off = m.take<uint64_t>(8 * n);
+        row_len = m.take<uint32_t>(4 * n);
+        spans_end = m.off;
+      }) != hipSuccess) {
+    c->err = "device allocation failed";
+    return PRAOS_E_OOM;
+  }
+  HIPCHK(c, hipMemsetAsync((uint8_t*)buf.p + spans_at, 0, spans_end - spans_at, s));
+  HIPCHK(c, hipMemsetAsync(total, 0, 4, s));
+  HIPCHK(c, hipMemcpyAsync(d_flag, flag, n, hipMemcpyHostToDevice, s));
+  if (dedup) {
+    HIPCHK(c, hipMemcpyAsync(d_tag, tag, n, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_key, key32, 32 * n, hipMemcpyHostToDevice, s));
+    HIPCHK(c, rs.reset(s));
+    rs.set(s, d_flag, d_tag, d_key, tag_mask);
+  } else {
+    if (limit) HIPCHK(c, hipMemcpyAsync(d_limit, limit, 4, hipMemcpyHostToDevice, s));
+    rs.ident(s, limit ? d_limit : nullptr, d_flag, 0);
+  }
+  rs.number(s, total, ioff, ilen, row_off, row_len);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(item_row, rs.item_row, 4 * n, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(n_rows, total, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  return PRAOS_OK;
+}
+
 }  // extern "C"

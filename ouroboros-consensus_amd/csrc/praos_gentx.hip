@@ -1,9 +1,10 @@
 // praos_gentx.hip -- host side of praos_verify_gen_txs (k_gentx.hip): wire
 // transactions of several peers, each distinct one checked once.
 //
-// One call: the arena and the spans up; k_gtx_split; the first numbering (k_wire.hip's hash set
-// with dedup, k_gtx_ident without) gives provisional rows in order of first appearance;
-// k_gtx_rows over them; the second numbering drops the rows it refused; k_gtx_final gathers the
+// One call: the arena and the spans up; k_gtx_split; the first numbering (the row set of
+// api_internal.hpp: its hash set with dedup, ident without) gives provisional rows in order of
+// first appearance; k_gtx_rows over them; the second numbering (ident over the rows it kept, into
+// row arrays of its own) drops the rows it refused; k_gtx_final gathers the
 // final rows and maps every item to its row.  Both numberings and the kernels between them read
 // the provisional row count on the device, so the host first waits for the final count (it
 // sizes the witness step's row arrays); then praos_txwit.hip's txw_rows_run (the witness counts
@@ -27,18 +28,14 @@ int gtx_run(praos_ctx* c, const praos_header_bytes* in, const praos_gtx_cfg* cfg
             praos_gtx_txs* txs, praos_txw_wits* wits) {
   const size_t n = in->n, bytes = in->bytes_len;
   hipStream_t s = c->stream;
-  uint32_t tab = 2;
-  while (tab < 2 * n) tab <<= 1;
-  const size_t nb = (n + NT - 1) / NT, ns = std::max<size_t>(tab, n);
   const size_t arena_sz = arena_room(bytes);     // ld64u's pad (arena.hpp)
   uint8_t* arena = nullptr;
   uint64_t* d_off = nullptr;
   uint32_t* d_len = nullptr;
   praos_gtx_dev_items d{};
   praos_gtx_dev_rows o{};
-  uint32_t *item_slot = nullptr, *item_rep = nullptr, *rep_row = nullptr, *item_row = nullptr, *blk = nullptr,
-           *total = nullptr, *slot_item = nullptr, *slot_min = nullptr, *row_item = nullptr, *row_final = nullptr,
-           *row_scratch = nullptr, *len_scratch = nullptr;
+  RowSet rs;
+  uint32_t *total = nullptr, *row_item = nullptr, *row_final = nullptr, *row_scratch = nullptr, *len_scratch = nullptr;
   uint64_t *off_scratch = nullptr, *ex_mem = nullptr, *ex_steps = nullptr;
   uint8_t *row_ok = nullptr, *p_txid = nullptr, *kind1 = nullptr;
   DevBuf buf;
@@ -75,19 +72,13 @@ int gtx_run(praos_ctx* c, const praos_header_bytes* in, const praos_gtx_cfg* cfg
         o.is_valid = m.take<uint8_t>(n);
         o.tx_id = m.take<uint8_t>(32 * n);
         o.block = m.take<uint32_t>(4 * n);
-        item_slot = m.take<uint32_t>(4 * n);
-        item_rep = m.take<uint32_t>(4 * n);
-        rep_row = m.take<uint32_t>(4 * n);
-        item_row = m.take<uint32_t>(4 * n);
+        rs.layout(m, n);
         row_item = m.take<uint32_t>(4 * n);
         row_final = m.take<uint32_t>(4 * n);
         row_scratch = m.take<uint32_t>(4 * n);
         off_scratch = m.take<uint64_t>(8 * n);
         len_scratch = m.take<uint32_t>(4 * n);
-        blk = m.take<uint32_t>(4 * nb);
         total = m.take<uint32_t>(8);                             // [0] provisional rows, [1] final rows
-        slot_item = m.take<uint32_t>(4 * (size_t)tab);
-        slot_min = m.take<uint32_t>(4 * ns);
         row_ok = m.take<uint8_t>(n);
         ex_mem = m.take<uint64_t>(8 * n);
         ex_steps = m.take<uint64_t>(8 * n);
@@ -98,43 +89,40 @@ int gtx_run(praos_ctx* c, const praos_header_bytes* in, const praos_gtx_cfg* cfg
     return PRAOS_E_OOM;
   }
   (void)hipGetLastError();
-  HIPCHK(c, hipMemsetAsync(arena + bytes, 0, arena_sz - bytes, s));
+  HIPCHK(c, pad_zero(arena, bytes, s));
   if (bytes) HIPCHK(c, hipMemcpyAsync(arena, in->bytes, bytes, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(d_off, in->off, 8 * n, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(d_len, in->len, 4 * n, hipMemcpyHostToDevice, s));
+  HIPCHK(c, items_upload(*in, d_off, d_len, s));
   HIPCHK(c, hipMemsetAsync(row_item, 0xff, 4 * n, s));
   HIPCHK(c, hipMemsetAsync(kind1, TXK_SHELLEY, 1, s));
   if (!cfg->dedup) d.hash = nullptr;
   launch_gtx_split(s, n, arena, bytes, d_off, d_len, cfg->n_eras, &d);
   // ---- provisional rows: the distinct items in order of first appearance
   if (cfg->dedup) {
-    HIPCHK(c, hipMemsetAsync(slot_item, 0, 4 * (size_t)tab, s));
-    HIPCHK(c, hipMemsetAsync(slot_min, 0xff, 4 * (size_t)tab, s));
-    launch_hdr_dedup(s, n, d.status, d.era, d.hash, 0xfffffffeu, tab - 1, slot_item, slot_min, item_slot, item_rep, blk,
-                     total, d.ioff, d.ilen, (uint32_t)n, off_scratch, len_scratch, rep_row, item_row);
+    HIPCHK(c, rs.reset(s));
+    rs.set(s, d.status, d.era, d.hash, 0xfffffffeu);           // every era but Byron
   } else {
-    launch_gtx_ident(s, n, nullptr, d.status, PRAOS_WIRE_OK, item_slot, slot_min);
-    launch_hdr_number(s, n, item_slot, slot_min, item_rep, blk, total, d.ioff, d.ilen, (uint32_t)n, off_scratch,
-                      len_scratch, rep_row, item_row);
+    rs.ident(s, nullptr, d.status, PRAOS_WIRE_OK);
   }
-  launch_gtx_rep(s, n, item_slot, item_rep, rep_row, row_item);
+  rs.number(s, total, d.ioff, d.ilen, off_scratch, len_scratch);
+  launch_hdr_rep(s, n, rs.item_slot, rs.item_rep, rs.rep_row, row_item);
   launch_gtx_rows(s, n, total, arena, row_item, &d, row_ok, ex_mem, ex_steps, p_txid);
-  // ---- final rows: the provisional rows k_gtx_rows kept, in the same order
-  launch_gtx_ident(s, n, total, row_ok, 1, item_slot, slot_min);
-  launch_hdr_number(s, n, item_slot, slot_min, item_rep, blk, total + 1, d.ioff, d.ilen, (uint32_t)n, off_scratch,
-                    len_scratch, row_final, row_scratch);
+  // ---- final rows: the provisional rows k_gtx_rows kept, in the same order.  The same arrays but
+  // for the rows: k_gtx_final reads the first numbering's item_row beside the second's row_final.
+  RowSet fin = rs;
+  fin.rep_row = row_final;
+  fin.item_row = row_scratch;
+  fin.ident(s, total, row_ok, 1);
+  fin.number(s, total + 1, d.ioff, d.ilen, off_scratch, len_scratch);
   HIPCHK(c, hipMemsetAsync(o.block, 0, 4 * n, s));
-  launch_gtx_final(s, n, total, row_item, row_ok, row_final, ex_mem, ex_steps, p_txid, &d, item_row, &o);
+  launch_gtx_final(s, n, total, row_item, row_ok, row_final, ex_mem, ex_steps, p_txid, &d, rs.item_row, &o);
   HIPCHK(c, hipGetLastError());
   uint32_t h_total[2] = {0, 0};
   HIPCHK(c, hipMemcpyAsync(h_total, total, 8, hipMemcpyDeviceToHost, s));
-  auto down = [&](void* dst, const void* src, size_t b) {
-    return dst && b ? hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, s) : hipSuccess;
-  };
+  const Down down{s};
   if (po) {
     HIPCHK(c, down(po->status, d.status, n));
     HIPCHK(c, down(po->era, d.era, n));
-    HIPCHK(c, down(po->row, item_row, 4 * n));
+    HIPCHK(c, down(po->row, rs.item_row, 4 * n));
     HIPCHK(c, down(po->byron_kind, d.kind, n));
     HIPCHK(c, down(po->payload_off, d.ioff, 8 * n));
     HIPCHK(c, down(po->payload_len, d.ilen, 4 * n));
@@ -196,7 +184,7 @@ extern "C" int praos_verify_gen_txs(praos_ctx* c, const praos_header_bytes* item
                                     praos_gtx_items* per_item, praos_gtx_txs* txs, praos_txw_wits* wits) {
   if (!c || !items || !cfg) return PRAOS_E_ARG;
   if (cfg->n_eras < 1 || cfg->n_eras > 32) { c->err = "praos_verify_gen_txs: n_eras must be 1..32"; return PRAOS_E_ARG; }
-  if (items->n && (!items->off || !items->len || (items->bytes_len && !items->bytes))) return PRAOS_E_ARG;
+  if (items->n && !items_ok(items)) return PRAOS_E_ARG;
   if (items->n > 0x7fffffffull) { c->err = "praos_verify_gen_txs: too many items in one call"; return PRAOS_E_ARG; }
   if (praos_host_only_(c)) return PRAOS_E_STATE;
   if (txs) txs->n_rows = 0;

@@ -188,8 +188,6 @@ int rp_download_results(praos_ctx* c, praos_batch* b, uint16_t* bits, int32_t* p
 // header dedup writes the distinct headers' spans there, and the decode of a replay batch reads
 // arena and spans from it, over those rows only
 int rp_device(const praos_ctx* c) { return c ? c->device : -1; }
-hipStream_t rp_copy_stream(praos_ctx* c) { return c->cstream; }
-bool rp_have_epoch(const praos_ctx* c) { return c && c->have_epoch; }
 
 uint8_t* rp_scratch(praos_ctx* c, size_t bytes) {
   if (!c || c->device < 0) return nullptr;

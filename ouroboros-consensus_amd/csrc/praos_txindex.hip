@@ -205,9 +205,7 @@ int praos_impl::txi_run(praos_ctx* c, praos_batch* b, const praos_txi_cfg* cfg, 
     return PRAOS_OK;
   }
   const size_t t = (size_t)total;
-  auto down = [&](void* dst, const void* src, size_t bytes) {
-    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
-  };
+  const Down down{s};
   HIPCHK(c, down(rows->block, fr.block, 4 * t));
   HIPCHK(c, down(rows->body_off, fr.body_off, 8 * t));
   HIPCHK(c, down(rows->body_len, fr.body_len, 4 * t));

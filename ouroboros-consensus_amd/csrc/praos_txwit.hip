@@ -118,9 +118,7 @@ int txw_rows_down_wits(praos_ctx* c, praos_txw_wits* wits, const txw_rows& R) {
   hipStream_t s = c->stream;
   const size_t W = (size_t)R.W;
   if (!W) return PRAOS_OK;
-  auto down = [&](void* dst, const void* src, size_t bytes) {
-    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
-  };
+  const Down down{s};
   HIPCHK(c, down(wits->tx, R.tx, 4 * W));
   HIPCHK(c, down(wits->kind, R.kind, W));
   HIPCHK(c, down(wits->key_off, R.koff, 8 * W));
@@ -184,9 +182,7 @@ int txw_run(praos_ctx* c, praos_batch* b, const praos_txw_cfg* cfg, praos_txw_bl
   }
   launch_txw_blocks(s, n, K.tfirst, R.st, R.cnt, R.txbad, d_bwit, d_bbad, d_bshape);
   HIPCHK(c, hipGetLastError());
-  auto down = [&](void* dst, const void* src, size_t bytes) {
-    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
-  };
+  const Down down{s};
   if (bo) {
     HIPCHK(c, down(bo->n_wit, d_bwit, 4 * n));
     HIPCHK(c, down(bo->n_bad, d_bbad, 4 * n));

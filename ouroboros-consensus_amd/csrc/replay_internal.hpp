@@ -91,14 +91,13 @@ int rp_fold(praos_ctx* c, const praos_headers* h, const uint8_t* prev_hash, cons
 // the ChainSync client's fold (PRAOS_V_DOESNT_FIT before validateHeader; ends at the first
 // failure).  err_out: the error text, instead of the context's (folds running side by side).
 //
-// The candidates call (praos_candidates.hip): a device buffer of at least `bytes` the context keeps
-// between calls (NULL: allocation failed; its earlier contents are gone when it grows), an upload
+// The context's device (praos_group.hip).  The candidates call (praos_candidates.hip): a device
+// buffer of at least `bytes` the context keeps between calls (NULL: allocation failed; its earlier
+// contents are gone when it grows; carved by api_internal.hpp's carve_kept), an upload
 // of the spans' concatenation into it (copy stream, pinned staging; dst has room for the bytes
 // rounded up to 8 plus 16, the pad is zeroed), and the decode of rows [first, n) of a replay
 // batch from device span arrays into that arena.
 int rp_device(const praos_ctx* c);
-hipStream_t rp_copy_stream(praos_ctx* c);
-bool rp_have_epoch(const praos_ctx* c);
 uint8_t* rp_scratch(praos_ctx* c, size_t bytes);
 int rp_upload_bytes(praos_ctx* c, uint8_t* dst, const praos_span* spans, size_t nspans);
 int rp_decode_rows(praos_ctx* c, praos_batch* b, const uint8_t* arena, size_t arena_len, const uint64_t* hoff,

@@ -542,6 +542,8 @@ SIGNATURES = {
                                                    ctypes.POINTER(TxwTxs), ctypes.POINTER(TxwWits)]),
     "praos_debug_span_equal": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, u8p, ctypes.c_size_t, u64p, u64p, u32p,
                                               u8p]),
+    "praos_debug_row_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, u8p, u8p, u8p, ctypes.c_uint32, ctypes.c_int,
+                                           u32p, u32p, u32p]),
     "praos_block_batch_tx_witnesses": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(TxwCfg),
                                                       ctypes.POINTER(TxwBlocks), ctypes.POINTER(TxwTxs),
                                                       ctypes.POINTER(TxwWits)]),
@@ -1863,6 +1865,22 @@ class Context:
         self.check(self.L.praos_debug_span_equal(self.h, len(a_off), ptr(a) if len(a) else None, len(a),
                                                  ptr(a_off, u64p), ptr(b_off, u64p), ptr(length, u32p), ptr(out)))
         return out
+
+    def debug_row_set(self, flag, tag=None, key=None, tag_mask=0xffffffff, dedup=True, limit=None):
+        """The row set of the wire calls alone (praos_debug_row_set): (item_row u32[n], n_rows).
+        dedup: items with flag 0 and a tag below 32 in tag_mask classed by (tag, 32-byte key);
+        without it every item with flag 0 below `limit` its own class.  Rows in order of first
+        appearance; 0xFFFFFFFF (PRAOS_NO_ROW) for an item in no class."""
+        flag = np.ascontiguousarray(flag, np.uint8)
+        n = len(flag)
+        tag = np.ascontiguousarray(tag if tag is not None else np.zeros(n), np.uint8)
+        key = np.ascontiguousarray(key if key is not None else np.zeros((n, 32)), np.uint8).reshape(n, 32)
+        lim = None if limit is None else np.array([limit], np.uint32)
+        rows, total = np.zeros(n, np.uint32), np.zeros(1, np.uint32)
+        self.check(self.L.praos_debug_row_set(self.h, n, ptr(flag), ptr(tag), ptr(key), tag_mask, 1 if dedup else 0,
+                                              None if lim is None else ptr(lim, u32p), ptr(rows, u32p),
+                                              ptr(total, u32p)))
+        return rows, int(total[0])
 
 class Group:
     """praos_group: one context per listed device (repeats allowed), batches split into
