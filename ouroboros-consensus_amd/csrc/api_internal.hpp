@@ -650,10 +650,49 @@ static inline void pack_nonce_table(const praos_nonce* etas, uint32_t k, uint32_
   }
 }
 
+// A key cache's lists after kc_lists, as the launchers take them (kargs.hpp): the misses, the hits
+// against this run's entry space, and the wide tier's hits against its tables
+static inline KeyItems key_misses(const praos_batch::KeyCache& k) { return {k.miss, k.counters + 2}; }
+static inline KeyHits key_hits(const praos_batch::KeyCache& k) {
+  return {k.hit, k.counters + 1, k.item_entry, k.kt, k.ki};
+}
+static inline KeyHits key_wide_hits(const praos_batch::KeyCache& k) {
+  return {k.wide.hit, k.wide.wcnt + 1, k.item_entry, k.wide.wtab, k.ki};
+}
+
+// The KES kernels' arguments of an uploaded batch in header mode (the period from the slot), verdicts
+// to bits; and stage V's part of the VRF arguments (batch_run_impl fills in the rest)
+static inline KesIn batch_kes_in(const praos_batch* b, uint64_t slots_per_kes_period, uint16_t* bits) {
+  KesIn a{};
+  a.hot_vk = b->hot_vk;
+  a.kes_sig = b->kes_sig;
+  a.body_off = b->body_off;
+  a.body_len = b->body_len;
+  a.body = b->body;
+  a.body_bytes_len = b->body_bytes_len;
+  a.slot = b->slot;
+  a.ocert_c0 = b->ocert_c0;
+  a.slots_per_kes_period = slots_per_kes_period;
+  a.bits = bits;
+  a.tabs = b->tab_kes;
+  return a;
+}
+static inline VrfIn batch_vrf_v_in(const praos_ctx* c, const praos_batch* b) {
+  VrfIn a{};
+  a.vrf_vk = b->vrf_vk;
+  a.vrf_proof = b->vrf_proof;
+  a.slot = b->slot;
+  a.eta0 = b->eta_tab ? b->eta_tab : c->d_eta0;
+  a.eta0_neutral = c->eta0_neutral;
+  a.eta_idx = b->eta_idx;
+  a.tabs = b->tab_vrf;
+  return a;
+}
+
 // praos_run.hip: the key-cache prepass (hash set, entries, hit / miss lists), the entries' key
 // tables, and the crypto step's stream scheduler
 int kc_lists(praos_ctx* c, praos_batch* b, const RunPlan& P, praos_batch::KeyCache& k, size_t n, const uint8_t* keys,
-             hipStream_t st, const uint32_t* list, const uint32_t* count, int which);
+             hipStream_t st, KeyItems items, int which);
 void kc_precompute(praos_ctx* c, const RunPlan& P, praos_batch::KeyCache& k, const uint8_t* keys, int kind,
                    hipStream_t st, size_t n);
 RunShape run_shape(const praos_ctx* c, size_t n, bool tp_only, bool v_done);   // the context's options + the batch

@@ -10,10 +10,7 @@ __global__ void __launch_bounds__(NT, LB_ED) k_ocert(size_t n, const uint32_t* _
   const ge_niels* btab = stage_btab<1>(gbtab, sbtab);
   const size_t t = (size_t)blockIdx.x * NT + threadIdx.x;
   if (t >= items) return;
-  const size_t i = list ? list[t] : t;
-  uint32_t pk[8], sg[16], hram[16];
-  ocert_load(a, i, sg, hram, pk);
-  ocert_store(a, i, ed25519_verify_core(pk, sg, sg + 8, hram, btab, lane_tab(a.tabs, i, LT_ED)));
+  ocert_miss_item(a, list ? list[t] : t, btab);
 }
 
 __global__ void __launch_bounds__(NT, LB_ED) k_ocert_ck(const uint32_t* __restrict__ list,
@@ -28,11 +25,7 @@ __global__ void __launch_bounds__(NT, LB_ED) k_ocert_ck(const uint32_t* __restri
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= items) return;
   wave_setprio(a.wave_prio);
-  const size_t i = list[t];
-  const size_t e = (size_t)item_entry[i];
-  uint32_t pk[8], sg[16], hram[16];
-  ocert_load(a, i, sg, hram, pk);
-  ocert_store(a, i, ed25519_verify_cached(sg, sg + 8, hram, kinfo[9 * e], ktab + e * KT_STRIDE, btab));
+  ocert_hit_item(a, list[t], item_entry, ktab, kinfo, btab);
 }
 
 __global__ void __launch_bounds__(NT, LB_ED) k_kes(size_t n, const uint32_t* __restrict__ list,
@@ -44,12 +37,7 @@ __global__ void __launch_bounds__(NT, LB_ED) k_kes(size_t n, const uint32_t* __r
   const ge_niels* btab = stage_btab<1>(gbtab, sbtab);
   const size_t q = (size_t)blockIdx.x * NT + threadIdx.x;
   if (q >= items) return;
-  const size_t i = list ? list[q] : q;
-  uint32_t sg[16], leaf[8], hram[16];
-  bool merkle_ok, in_range;
-  kes_prepare(a, i, sg, leaf, hram, merkle_ok, in_range);
-  const bool leaf_ok = ed25519_verify_core(leaf, sg, sg + 8, hram, btab, lane_tab(a.tabs, i, LT_ED));
-  kes_store(a, i, merkle_ok, leaf_ok, in_range);
+  kes_miss_item(a, list ? list[q] : q, btab);
 }
 
 // Hits of the leaf-key cache: the leaf key's multi-power tables were built once per
@@ -75,14 +63,7 @@ __global__ void __launch_bounds__(NT, LB_ED) k_kes_ck(const uint32_t* __restrict
   const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= items) return;
   wave_setprio(a.wave_prio);
-  const size_t i = list[q];
-  const size_t e = (size_t)item_entry[i];
-  uint32_t sg[16], leaf[8], hram[16];
-  bool merkle_ok, in_range;
-  kes_prepare_dd(a, i, rep_ok ? entry_rep[e] : i, rep_ok ? rep_ok + e : nullptr, sg, leaf, hram, merkle_ok,
-                 in_range);
-  const bool leaf_ok = ed25519_verify_cached(sg, sg + 8, hram, kinfo[9 * e], ktab + e * KT_STRIDE, btab);
-  kes_store(a, i, merkle_ok, leaf_ok, in_range);
+  kes_hit_item(a, list[q], item_entry, ktab, kinfo, btab, entry_rep, rep_ok);
 }
 
 __global__ void __launch_bounds__(NT, LB_ED) k_kes_ck2(const uint32_t* __restrict__ list,
@@ -192,61 +173,38 @@ __global__ void __launch_bounds__(NT) k_kes_leafkeys(size_t n, KesIn a, uint8_t*
 }
 
 
-// ---- host launchers (kernels are only launchable from their own module)
-void launch_ocert(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count,
-                  const ge_niels* gbtab, const uint8_t* cold_vk, const uint8_t* hot_vk, const uint64_t* ocert_n,
-                  const uint64_t* ocert_c0, const uint8_t* sig, const uint64_t* slot, uint64_t slots_per_kes_period,
-                  uint64_t max_kes_evo, uint16_t* bits, uint8_t* ok_out, ge_cached* tabs) {
-  OcertIn a{cold_vk, hot_vk, ocert_n, ocert_c0, sig, slot, slots_per_kes_period, max_kes_evo, bits, ok_out, tabs};
-  hipLaunchKernelGGL(k_ocert, grid, block, 0, stream, n, list, count, gbtab, a);
+// ---- host launchers (kernels are only launchable from their own module; the ILP-4 twins'
+// launchers are k_miss4.hip's).
+void launch_ocert(hipStream_t stream, size_t n, KeyItems items, const ge_niels* gbtab, const OcertIn& a, int ilp4) {
+  if (ilp4) return launch_ocert4(stream, n, items, gbtab, a);
+  hipLaunchKernelGGL(k_ocert, launch_grid(n), dim3(NT), 0, stream, n, items.list, items.count, gbtab, a);
 }
-void launch_ocert_ck(dim3 grid, dim3 block, hipStream_t stream, const uint32_t* list, const uint32_t* count,
-                     const int32_t* item_entry, const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* gbtab,
-                     const uint8_t* cold_vk, const uint8_t* hot_vk, const uint64_t* ocert_n, const uint64_t* ocert_c0,
-                     const uint8_t* sig, const uint64_t* slot, uint64_t slots_per_kes_period, uint64_t max_kes_evo,
-                     uint16_t* bits, uint8_t* ok_out, int prio) {
-  OcertIn a{cold_vk, hot_vk, ocert_n, ocert_c0, sig, slot, slots_per_kes_period, max_kes_evo, bits, ok_out, nullptr,
-            prio};
-  hipLaunchKernelGGL(k_ocert_ck, grid, block, 0, stream, list, count, item_entry, ktab, kinfo, gbtab, a);
+void launch_ocert_ck(hipStream_t stream, size_t n, const KeyHits& h, const ge_niels* comb, const OcertIn& a,
+                     int ilp4) {
+  if (ilp4) return launch_ocert_ck4(stream, n, h, comb, a);
+  hipLaunchKernelGGL(k_ocert_ck, launch_grid(n), dim3(NT), 0, stream, h.list, h.count, h.item_entry, h.ktab, h.kinfo,
+                     comb, a);
 }
 
-void launch_kes(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count,
-                const ge_niels* gbtab, const uint8_t* hot_vk, const uint8_t* kes_sig, const uint64_t* body_off,
-                const uint32_t* body_len, const uint8_t* body, size_t body_bytes_len, const uint64_t* slot,
-                const uint64_t* ocert_c0, uint64_t slots_per_kes_period, const uint32_t* period, uint16_t* bits,
-                uint8_t* result, ge_cached* tabs) {
-  KesIn a{hot_vk, kes_sig, body_off, body_len, body, body_bytes_len, slot, ocert_c0, slots_per_kes_period,
-          period, bits, result, tabs};
-  hipLaunchKernelGGL(k_kes, grid, block, 0, stream, n, list, count, gbtab, a);
+void launch_kes(hipStream_t stream, size_t n, KeyItems items, const ge_niels* gbtab, const KesIn& a, int ilp4) {
+  if (ilp4) return launch_kes4(stream, n, items, gbtab, a);
+  hipLaunchKernelGGL(k_kes, launch_grid(n), dim3(NT), 0, stream, n, items.list, items.count, gbtab, a);
 }
-void launch_kes_ck(dim3 grid, dim3 block, hipStream_t stream, const uint32_t* list, const uint32_t* count,
-                   const int32_t* item_entry, const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* gbtab,
-                   const uint8_t* hot_vk, const uint8_t* kes_sig, const uint64_t* body_off, const uint32_t* body_len,
-                   const uint8_t* body, size_t body_bytes_len, const uint64_t* slot, const uint64_t* ocert_c0,
-                   uint64_t slots_per_kes_period, uint16_t* bits, uint32_t pair_min, const uint32_t* entry_rep,
-                   const uint8_t* rep_ok, int prio) {
-  KesIn a{hot_vk, kes_sig, body_off, body_len, body, body_bytes_len, slot, ocert_c0, slots_per_kes_period,
-          nullptr, bits, nullptr, nullptr, prio};
+void launch_kes_ck(hipStream_t stream, size_t n, const KeyHits& h, const ge_niels* comb, const KesIn& a,
+                   uint32_t pair_min, const uint32_t* entry_rep, const uint8_t* rep_ok, int ilp4) {
+  if (ilp4) return launch_kes_ck4(stream, n, h, comb, a);
   if (pair_min)     // (the one-header kernel keeps its registers: the paired one spills 176 bytes)
-    hipLaunchKernelGGL(k_kes_ck2, grid, block, 0, stream, list, count, item_entry, ktab, kinfo, gbtab, a, pair_min,
-                       entry_rep, rep_ok);
+    hipLaunchKernelGGL(k_kes_ck2, launch_grid(n), dim3(NT), 0, stream, h.list, h.count, h.item_entry, h.ktab, h.kinfo,
+                       comb, a, pair_min, entry_rep, rep_ok);
   else
-    hipLaunchKernelGGL(k_kes_ck, grid, block, 0, stream, list, count, item_entry, ktab, kinfo, gbtab, a, entry_rep,
-                       rep_ok);
+    hipLaunchKernelGGL(k_kes_ck, launch_grid(n), dim3(NT), 0, stream, h.list, h.count, h.item_entry, h.ktab, h.kinfo,
+                       comb, a, entry_rep, rep_ok);
 }
 void launch_kes_merkle_reps(hipStream_t stream, const uint32_t* counters, uint32_t max_entries,
-                            const uint32_t* entry_rep, const uint8_t* hot_vk, const uint8_t* kes_sig,
-                            const uint64_t* slot, const uint64_t* ocert_c0, uint64_t slots_per_kes_period,
-                            uint8_t* rep_ok) {
-  KesIn a{hot_vk, kes_sig, nullptr, nullptr, nullptr, 0, slot, ocert_c0, slots_per_kes_period, nullptr, nullptr,
-          nullptr, nullptr};
-  hipLaunchKernelGGL(k_kes_merkle_reps, dim3((max_entries + NT - 1) / NT), dim3(NT), 0, stream, counters, max_entries,
+                            const uint32_t* entry_rep, const KesIn& a, uint8_t* rep_ok) {
+  hipLaunchKernelGGL(k_kes_merkle_reps, launch_grid(max_entries), dim3(NT), 0, stream, counters, max_entries,
                      entry_rep, a, rep_ok);
 }
-void launch_kes_leafkeys(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint8_t* kes_sig,
-                         const uint64_t* slot, const uint64_t* ocert_c0, uint64_t slots_per_kes_period,
-                         uint8_t* keys) {
-  KesIn a{nullptr, kes_sig, nullptr, nullptr, nullptr, 0, slot, ocert_c0, slots_per_kes_period,
-          nullptr, nullptr, nullptr, nullptr};
-  hipLaunchKernelGGL(k_kes_leafkeys, grid, block, 0, stream, n, a, keys);
+void launch_kes_leafkeys(hipStream_t stream, size_t n, const KesIn& a, uint8_t* keys) {
+  hipLaunchKernelGGL(k_kes_leafkeys, launch_grid(n), dim3(NT), 0, stream, n, a, keys);
 }

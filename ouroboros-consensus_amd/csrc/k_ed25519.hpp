@@ -3,25 +3,7 @@
 #pragma once
 #include "kcommon.hpp"
 
-// ------------------------------------------------------------------ OCert + KES period checks
-// bits |= KES_BEFORE_START / KES_AFTER_END / OCERT_SIG.  If ok_out != null the
-// kernel is the plain praos_verify_ocert batch (ok_out[i] = 1 when valid).
-// Items: i in [0, n), or list[0 .. *count) when list != null (key-cache
-// partition, k_keys.hip): k_ocert takes the misses, k_ocert_ck the hits.
-struct OcertIn {
-  const uint8_t* __restrict__ cold_vk;
-  const uint8_t* __restrict__ hot_vk;
-  const uint64_t* __restrict__ ocert_n;
-  const uint64_t* __restrict__ ocert_c0;
-  const uint8_t* __restrict__ sig;
-  const uint64_t* __restrict__ slot;
-  uint64_t slots_per_kes_period, max_kes_evo;
-  uint16_t* __restrict__ bits;
-  uint8_t* __restrict__ ok_out;
-  ge_cached* __restrict__ tabs;          // per-lane tables (LT_ED entries per item)
-  int wave_prio;                         // cached verifies: waves at s_setprio <wave_prio> (0 = off)
-};
-
+// ------------------------------------------------------------------ OCert (OcertIn: kargs.hpp)
 __device__ __forceinline__ void ocert_store(const OcertIn& a, size_t i, bool ok) {
   if (a.ok_out) {
     a.ok_out[i] = ok ? 1 : 0;
@@ -44,32 +26,43 @@ __device__ __forceinline__ void ocert_load(const OcertIn& a, size_t i, uint32_t 
   ocert_hram(hram, sg, pk, hot, a.ocert_n[i], a.ocert_c0[i]);
 }
 
-// ------------------------------------------------------------------ KES
-// Header mode: t = kp >= c0 ? kp - c0 : 0 (Praos.hs:570), result to bits.
-// Plain mode (result != null): t = period[i], result 0 ok / 1 Reject / 2 leaf.
-// Items: i in [0, n), or list[0 .. *count) (leaf-key cache partition): k_kes takes
-// the misses, k_kes_ck the hits.
-struct KesIn {
-  const uint8_t* __restrict__ hot_vk;
-  const uint8_t* __restrict__ kes_sig;
-  const uint64_t* __restrict__ body_off;
-  const uint32_t* __restrict__ body_len;
-  const uint8_t* __restrict__ body;
-  size_t body_bytes_len;
-  const uint64_t* __restrict__ slot;
-  const uint64_t* __restrict__ ocert_c0;
-  uint64_t slots_per_kes_period;
-  const uint32_t* __restrict__ period;
-  uint16_t* __restrict__ bits;
-  uint8_t* __restrict__ result;
-  ge_cached* __restrict__ tabs;
-  int wave_prio;                         // cached verifies: waves at s_setprio <wave_prio> (0 = off)
-};
+// One uncached item (k_ocert; k_ocert4 from the ILP-4 build): the full verify on the lane's tables
+__device__ __forceinline__ void ocert_miss_item(const OcertIn& a, size_t i, const ge_niels* btab) {
+  uint32_t pk[8], sg[16], hram[16];
+  ocert_load(a, i, sg, hram, pk);
+  ocert_store(a, i, ed25519_verify_core(pk, sg, sg + 8, hram, btab, lane_tab(a.tabs, i, LT_ED)));
+}
 
+// One hit of the cold-key cache (k_ocert_ck; k_ocert_ck4): btab = the radix-2^16 comb, read in place
+__device__ __forceinline__ void ocert_hit_item(const OcertIn& a, size_t i, const int32_t* item_entry,
+                                               const ge_cached* ktab,
+                                               const uint32_t* kinfo,
+                                               const ge_niels* btab) {
+  const size_t e = (size_t)item_entry[i];
+  uint32_t pk[8], sg[16], hram[16];
+  ocert_load(a, i, sg, hram, pk);
+  ocert_store(a, i, ed25519_verify_cached(sg, sg + 8, hram, kinfo[9 * e], ktab + e * KT_STRIDE, btab));
+}
+
+// ------------------------------------------------------------------ KES (KesIn: kargs.hpp)
 __device__ __forceinline__ uint64_t kes_t(const KesIn& a, size_t i) {
   if (a.period) return a.period[i];
   const uint64_t kp = a.slot[i] / a.slots_per_kes_period, c0 = a.ocert_c0[i];
   return kp >= c0 ? kp - c0 : 0;
+}
+
+// the tail of both prepares: the signature words, the body range check and SHA-512(R || leaf || M)
+__device__ __forceinline__ void kes_hram(const KesIn& a, size_t i, const uint8_t* sig,
+                                         const uint32_t leaf[8], uint32_t sg[16], uint32_t hram[16], bool& in_range) {
+  load_words(sg, sig, 16);
+  uint64_t off = a.body_off[i];
+  uint32_t len = a.body_len[i];
+  in_range = (off & 7) == 0 && off <= a.body_bytes_len && len <= a.body_bytes_len - off;
+  if (!in_range) { off = 0; len = 0; }
+  uint32_t pre[16];
+#pragma unroll
+  for (int k = 0; k < 8; k++) { pre[k] = sg[k]; pre[8 + k] = leaf[k]; }
+  sha512_stream(hram, pre, 64, a.body + off, len);
 }
 
 // Merkle walk + SHA-512(R || leaf || M); returns merkle_ok, in_range, the leaf
@@ -80,15 +73,7 @@ __device__ __forceinline__ void kes_prepare(const KesIn& a, size_t i, uint32_t s
   uint32_t vk[8];
   load_words(vk, a.hot_vk + 32 * i, 8);
   merkle_ok = kes_merkle(leaf, vk, kes_t(a, i), sig);
-  load_words(sg, sig, 16);
-  uint64_t off = a.body_off[i];
-  uint32_t len = a.body_len[i];
-  in_range = (off & 7) == 0 && off <= a.body_bytes_len && len <= a.body_bytes_len - off;
-  if (!in_range) { off = 0; len = 0; }
-  uint32_t pre[16];
-#pragma unroll
-  for (int k = 0; k < 8; k++) { pre[k] = sg[k]; pre[8 + k] = leaf[k]; }
-  sha512_stream(hram, pre, 64, a.body + off, len);
+  kes_hram(a, i, sig, leaf, sg, hram, in_range);
 }
 
 // Merkle walk shared per leaf-key cache entry (KES path dedup): the walk reads hot_vk, t and
@@ -143,15 +128,7 @@ __device__ __forceinline__ void kes_prepare_dd(const KesIn& a, size_t i, size_t 
     load_words(vk, a.hot_vk + 32 * i, 8);
     merkle_ok = kes_merkle(leaf, vk, t, sig);
   }
-  load_words(sg, sig, 16);
-  uint64_t off = a.body_off[i];
-  uint32_t len = a.body_len[i];
-  in_range = (off & 7) == 0 && off <= a.body_bytes_len && len <= a.body_bytes_len - off;
-  if (!in_range) { off = 0; len = 0; }
-  uint32_t pre[16];
-#pragma unroll
-  for (int k = 0; k < 8; k++) { pre[k] = sg[k]; pre[8 + k] = leaf[k]; }
-  sha512_stream(hram, pre, 64, a.body + off, len);
+  kes_hram(a, i, sig, leaf, sg, hram, in_range);
 }
 
 __device__ __forceinline__ void kes_store(const KesIn& a, size_t i, bool merkle_ok, bool leaf_ok, bool in_range) {
@@ -164,4 +141,28 @@ __device__ __forceinline__ void kes_store(const KesIn& a, size_t i, bool merkle_
   else if (!leaf_ok) b |= PRAOS_BIT_KES_LEAF;
   if (!in_range) b |= PRAOS_BIT_INPUT;
   a.bits[i] = b;
+}
+
+// One uncached item (k_kes; k_kes4 from the ILP-4 build)
+__device__ __forceinline__ void kes_miss_item(const KesIn& a, size_t i, const ge_niels* btab) {
+  uint32_t sg[16], leaf[8], hram[16];
+  bool merkle_ok, in_range;
+  kes_prepare(a, i, sg, leaf, hram, merkle_ok, in_range);
+  const bool leaf_ok = ed25519_verify_core(leaf, sg, sg + 8, hram, btab, lane_tab(a.tabs, i, LT_ED));
+  kes_store(a, i, merkle_ok, leaf_ok, in_range);
+}
+
+// One hit of the leaf-key cache (k_kes_ck; k_kes_ck4, which has no path dedup: rep_ok null)
+__device__ __forceinline__ void kes_hit_item(const KesIn& a, size_t i, const int32_t* item_entry,
+                                             const ge_cached* ktab, const uint32_t* kinfo,
+                                             const ge_niels* btab,
+                                             const uint32_t* entry_rep,
+                                             const uint8_t* rep_ok) {
+  const size_t e = (size_t)item_entry[i];
+  uint32_t sg[16], leaf[8], hram[16];
+  bool merkle_ok, in_range;
+  kes_prepare_dd(a, i, rep_ok ? entry_rep[e] : i, rep_ok ? rep_ok + e : nullptr, sg, leaf, hram, merkle_ok,
+                 in_range);
+  const bool leaf_ok = ed25519_verify_cached(sg, sg + 8, hram, kinfo[9 * e], ktab + e * KT_STRIDE, btab);
+  kes_store(a, i, merkle_ok, leaf_ok, in_range);
 }

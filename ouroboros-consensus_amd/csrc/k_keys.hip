@@ -223,11 +223,8 @@ __global__ void __launch_bounds__(64) k_key_precompute(int kind, const uint32_t*
   // chains: raised wave priority wins the SIMD's issue arbitration against the
   // throughput kernels resident beside it
   if (wave_prio) __builtin_amdgcn_s_setprio(3);
-  // grid-stride: the host sizes the grid from the previous run's entry count (a grid sized
-  // for the worst case is thousands of empty blocks that wait for wave slots on a busy GPU)
-  const uint32_t ne = min(counters[0], max_entries);
-  for (uint32_t e = (base ? *base : 0u) + blockIdx.x * blockDim.x + threadIdx.x; e < ne; e += gridDim.x * blockDim.x)
-    key_precompute_entry(kind, e, entry_rep, keys, ktab, kinfo);
+  key_precompute_entries(kind, counters, max_entries, entry_rep, keys, ktab, kinfo, base,
+                         blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
 // pass 2: lane (entry, chunk) expands the chunk base into its 8-entry table (not for a key of the
@@ -383,31 +380,31 @@ __global__ void k_ocert_fanout(size_t n, const uint32_t* __restrict__ item_rep, 
 }
 
 // ---- host launchers
-void launch_key_insert(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count,
-                       const uint8_t* keys, uint32_t mask, uint32_t* slot_rep, uint32_t* slot_cnt, int32_t* item_slot,
-                       const int32_t* pentry, const uint32_t* pkey, uint32_t pmask, uint32_t* scnt) {
-  hipLaunchKernelGGL(k_key_insert, grid, block, 0, stream, n, list, count, keys, mask, slot_rep, slot_cnt, item_slot,
-                     pentry, pkey, pmask, scnt);
+void launch_key_insert(hipStream_t stream, size_t n, KeyItems items, const uint8_t* keys, uint32_t mask,
+                       uint32_t* slot_rep, uint32_t* slot_cnt, int32_t* item_slot, const int32_t* pentry,
+                       const uint32_t* pkey, uint32_t pmask, uint32_t* scnt) {
+  hipLaunchKernelGGL(k_key_insert, launch_grid(n), dim3(NT), 0, stream, n, items.list, items.count, keys, mask,
+                     slot_rep, slot_cnt, item_slot, pentry, pkey, pmask, scnt);
 }
 void launch_key_store_ranges(hipStream_t stream, uint32_t entries, const uint32_t* scnt, uint32_t* spos,
                              uint32_t* counters) {
   hipLaunchKernelGGL(k_key_store_ranges, dim3((entries + 255) / 256), dim3(256), 0, stream, entries, scnt, spos,
                      counters);
 }
-void launch_key_assign(dim3 grid, dim3 block, hipStream_t stream, uint32_t cap, const uint32_t* slot_rep,
-                       const uint32_t* slot_cnt, uint32_t min_count, uint32_t max_entries, int32_t* slot_entry,
-                       uint32_t* entry_rep, uint32_t* entry_pos, uint32_t* counters, const KeyWide& w) {
-  hipLaunchKernelGGL(k_key_assign, grid, block, 0, stream, cap, slot_rep, slot_cnt, min_count, max_entries, slot_entry,
-                     entry_rep, entry_pos, counters, w.min_uses, w.cap, w.min_uses ? w.entry_wide : nullptr, w.wide_ent,
+void launch_key_assign(hipStream_t stream, uint32_t cap, const uint32_t* slot_rep, const uint32_t* slot_cnt,
+                       uint32_t min_count, uint32_t max_entries, int32_t* slot_entry, uint32_t* entry_rep,
+                       uint32_t* entry_pos, uint32_t* counters, const KeyWide& w) {
+  hipLaunchKernelGGL(k_key_assign, launch_grid(cap), dim3(NT), 0, stream, cap, slot_rep, slot_cnt, min_count,
+                     max_entries, slot_entry, entry_rep, entry_pos, counters, w.min_uses, w.cap,
+                     w.min_uses ? w.entry_wide : nullptr, w.wide_ent,
                      w.wcnt);   // (tier off: no entry_wide, whose size is the batch's own entry count)
 }
-void launch_key_partition(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint32_t* list,
-                          const uint32_t* count, const int32_t* item_slot, const int32_t* slot_entry,
-                          int32_t* item_entry, uint32_t* entry_pos, uint32_t* hit_list, uint32_t* miss_list,
-                          uint32_t* counters, uint32_t* spos, const KeyWide& w) {
-  hipLaunchKernelGGL(k_key_partition, grid, block, 0, stream, n, list, count, item_slot, slot_entry, item_entry,
-                     entry_pos, hit_list, miss_list, counters, spos, w.min_uses ? w.entry_wide : nullptr, w.hit,
-                     w.wcnt);
+void launch_key_partition(hipStream_t stream, size_t n, KeyItems items, const int32_t* item_slot,
+                          const int32_t* slot_entry, int32_t* item_entry, uint32_t* entry_pos, uint32_t* hit_list,
+                          uint32_t* miss_list, uint32_t* counters, uint32_t* spos, const KeyWide& w) {
+  hipLaunchKernelGGL(k_key_partition, launch_grid(n), dim3(NT), 0, stream, n, items.list, items.count, item_slot,
+                     slot_entry, item_entry, entry_pos, hit_list, miss_list, counters, spos,
+                     w.min_uses ? w.entry_wide : nullptr, w.hit, w.wcnt);
 }
 void launch_key_precompute(int kind, hipStream_t stream, const uint32_t* counters, uint32_t max_entries,
                            const uint32_t* entry_rep, const uint8_t* keys, ge_cached* ktab, uint32_t* kinfo,
@@ -438,15 +435,15 @@ void launch_pkey_publish(hipStream_t stream, const uint32_t* counters, const uin
   hipLaunchKernelGGL(k_pkey_publish, dim3((span + 255) / 256), dim3(256), 0, stream, counters, base, max_entries,
                      entry_rep, keys, pentry, pkey, pmask, count);
 }
-void launch_ocert_dedup(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint8_t* cold, const uint8_t* hot,
+void launch_ocert_dedup(hipStream_t stream, size_t n, const uint8_t* cold, const uint8_t* hot,
                         const uint64_t* on, const uint64_t* oc, const uint8_t* sig, uint32_t mask, uint32_t* slot_rep,
                         uint32_t* item_rep, uint32_t* reps, uint32_t* counters) {
-  hipLaunchKernelGGL(k_ocert_dedup, grid, block, 0, stream, n, cold, hot, on, oc, sig, mask, slot_rep, item_rep, reps,
-                     counters);
+  hipLaunchKernelGGL(k_ocert_dedup, launch_grid(n), dim3(NT), 0, stream, n, cold, hot, on, oc, sig, mask, slot_rep,
+                     item_rep, reps, counters);
 }
-void launch_ocert_fanout(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint32_t* item_rep,
+void launch_ocert_fanout(hipStream_t stream, size_t n, const uint32_t* item_rep,
                          const uint8_t* ok, const uint64_t* slot, const uint64_t* oc, uint64_t slots_per_kes_period,
                          uint64_t max_kes_evo, uint16_t* bits) {
-  hipLaunchKernelGGL(k_ocert_fanout, grid, block, 0, stream, n, item_rep, ok, slot, oc, slots_per_kes_period,
-                     max_kes_evo, bits);
+  hipLaunchKernelGGL(k_ocert_fanout, launch_grid(n), dim3(NT), 0, stream, n, item_rep, ok, slot, oc,
+                     slots_per_kes_period, max_kes_evo, bits);
 }

@@ -45,3 +45,17 @@ FE_INLINE void key_precompute_entry(int kind, uint32_t e, const uint32_t* __rest
   key_decode_entry(kind, e, entry_rep, keys, kinfo, P, true);
   key_chunk_bases(ktab + (size_t)e * KT_STRIDE, P, key_chunks(kind));
 }
+
+// The loop of lane `lane` of `lanes` over the run's new entries (k_keys.hip k_key_precompute;
+// k_key_precompute4 from the ILP-4 build).  Grid-stride: the host sizes the grid from the previous
+// run's entry count (a grid sized for the worst case is thousands of empty blocks that wait for wave
+// slots on a busy GPU).  The kernels compute lane and lanes: under their launch bounds blockDim is
+// one load.
+__device__ __forceinline__ void key_precompute_entries(int kind, const uint32_t* counters, uint32_t max_entries,
+                                                       const uint32_t* entry_rep, const uint8_t* keys, ge_cached* ktab,
+                                                       uint32_t* kinfo, const uint32_t* base, uint32_t lane,
+                                                       uint32_t lanes) {
+  const uint32_t ne = min(counters[0], max_entries);
+  for (uint32_t e = (base ? *base : 0u) + lane; e < ne; e += lanes)
+    key_precompute_entry(kind, e, entry_rep, keys, ktab, kinfo);
+}

@@ -12,11 +12,11 @@ __global__ void __launch_bounds__(64) k_key_precompute4(int kind, const uint32_t
                                                          uint32_t* __restrict__ kinfo, int wave_prio,
                                                          const uint32_t* __restrict__ base) {
   if (wave_prio) __builtin_amdgcn_s_setprio(3);
-  const uint32_t ne = min(counters[0], max_entries);
-  for (uint32_t e = (base ? *base : 0u) + blockIdx.x * blockDim.x + threadIdx.x; e < ne; e += gridDim.x * blockDim.x)
-    key_precompute_entry(kind, e, entry_rep, keys, ktab, kinfo);
+  key_precompute_entries(kind, counters, max_entries, entry_rep, keys, ktab, kinfo, base,
+                         blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
+// ---- host launcher, called by k_keys.hip's only (launch.hpp)
 void launch_key_precompute4(int kind, hipStream_t stream, const uint32_t* counters, uint32_t max_entries,
                             const uint32_t* entry_rep, const uint8_t* keys, ge_cached* ktab, uint32_t* kinfo,
                             int wave_prio, const uint32_t* base, uint32_t span) {

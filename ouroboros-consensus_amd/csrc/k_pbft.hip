@@ -295,18 +295,16 @@ void launch_pbft_decode(hipStream_t stream, size_t n, const uint8_t* arena, uint
             prev_genesis, header_hash, bits, gk_idx, dhash, keys, sig, hram, vlist, vcount};
   hipLaunchKernelGGL(k_pbft_decode, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, stream, n, a);
 }
-void launch_pbft_sig(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count, const ge_niels* gbtab,
-                     const uint8_t* keys, const uint8_t* sig, const uint8_t* hram, uint8_t* bits, ge_cached* tabs) {
+void launch_pbft_sig(hipStream_t stream, size_t n, KeyItems items, const ge_niels* gbtab, const uint8_t* keys,
+                     const uint8_t* sig, const uint8_t* hram, uint8_t* bits, ge_cached* tabs) {
   PbftSig a{keys, sig, hram, bits, tabs};
-  hipLaunchKernelGGL(k_pbft_sig, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, stream, list, count, gbtab, a);
+  hipLaunchKernelGGL(k_pbft_sig, launch_grid(n), dim3(NT), 0, stream, items.list, items.count, gbtab, a);
 }
-void launch_pbft_sig_ck(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count,
-                        const int32_t* item_entry, const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* comb,
-                        const uint8_t* keys, const uint8_t* sig, const uint8_t* hram, uint8_t* bits) {
+void launch_pbft_sig_ck(hipStream_t stream, size_t n, const KeyHits& h, const ge_niels* comb, const uint8_t* keys,
+                        const uint8_t* sig, const uint8_t* hram, uint8_t* bits) {
   PbftSig a{keys, sig, hram, bits, nullptr};
-  const unsigned bs = lat_block(n);
-  hipLaunchKernelGGL(k_pbft_sig_ck, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, stream, list, count, item_entry,
-                     ktab, kinfo, comb, a);
+  hipLaunchKernelGGL(k_pbft_sig_ck, launch_grid(n), dim3(NT), 0, stream, h.list, h.count, h.item_entry, h.ktab,
+                     h.kinfo, comb, a);
 }
 void launch_pbft_keyhash(hipStream_t stream, size_t n, const uint8_t* keys64, uint8_t* out28) {
   hipLaunchKernelGGL(k_pbft_keyhash, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, stream, n, keys64, out28);

@@ -2,8 +2,7 @@
 #include "k_vrf.hpp"
 
 // ------------------------------------------------------------------ VRF
-// Items: i in [0, n) or list[0 .. *count) (key-cache partition, k_keys.hip):
-// k_vrf takes the misses, k_vrf_ck the hits (cached VRF key, short U chain).
+// Items: i in [0, n) or list[0 .. *count).
 template <bool CACHED>
 __device__ __forceinline__ void vrf_item(const VrfIn& a, size_t i, const ge_niels* __restrict__ btab,
                                          const ge_cached* __restrict__ ktab, const uint32_t* __restrict__ kinfo) {
@@ -81,23 +80,6 @@ __global__ void __launch_bounds__(NT, LB_VRF) k_vrf(size_t n, const uint32_t* __
   if (t >= items) return;
   vrf_item<false>(a, list ? list[t] : t, btab, nullptr, nullptr);
 }
-
-__global__ void __launch_bounds__(NT, LB_VRF) k_vrf_ck(const uint32_t* __restrict__ list,
-                                                       const uint32_t* __restrict__ count,
-                                                       const int32_t* __restrict__ item_entry,
-                                                       const ge_cached* __restrict__ ktab,
-                                                       const uint32_t* __restrict__ kinfo,
-                                                       const ge_niels* __restrict__ gbtab, VrfIn a) {
-  const size_t items = *count;
-  if ((size_t)blockIdx.x * NT >= items) return;
-  const ge_niels* btab = gbtab;                                 // the radix-2^16 comb, read in place
-  const size_t t = (size_t)blockIdx.x * NT + threadIdx.x;
-  if (t >= items) return;
-  const size_t i = list[t];
-  const size_t e = (size_t)item_entry[i];
-  vrf_item<true>(a, i, btab, ktab + e * KT_STRIDE, kinfo + 9 * e);
-}
-
 
 // ------------------------------------------------------------------ TPraos VRF
 // cardano-protocol-tpraos OVERLAY.praosVrfChecks: pool lookup, VRF key hash,
@@ -194,38 +176,14 @@ __global__ void __launch_bounds__(NT, LB_VRF) k_vrf_tp(
   bits[i] = b;
 }
 
-// ---- host launchers (kernels are only launchable from their own module)
-void launch_vrf(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count,
-                const ge_niels* gbtab, const uint8_t* cold_vk, const uint8_t* vrf_vk, const uint8_t* vrf_out,
-                const uint8_t* vrf_proof, const uint64_t* slot, const uint32_t* eta0, int eta0_neutral,
-                const uint8_t* eta_idx, const uint32_t* pool_hash, const uint32_t* pool_vrf, const int32_t* pool_map,
-                uint32_t npools, int check_output, const uint8_t* alpha_in, uint16_t* bits, int32_t* pool_idx,
-                int32_t* pool_sorted_idx, uint8_t* beta_out, uint8_t* leader_out, uint8_t* nonce_out, uint8_t* ok_out,
-                ge_cached* tabs) {
-  VrfIn a{cold_vk, vrf_vk, vrf_out, vrf_proof, slot, eta0, eta0_neutral, eta_idx, pool_hash, pool_vrf, pool_map, npools,
-          check_output, alpha_in, bits, pool_idx, pool_sorted_idx, beta_out, leader_out, nonce_out, ok_out, tabs};
-  hipLaunchKernelGGL(k_vrf, grid, block, 0, stream, n, list, count, gbtab, a);
+// ---- host launchers (kernels are only launchable from their own module).
+void launch_vrf(hipStream_t stream, size_t n, KeyItems items, const ge_niels* gbtab, const VrfIn& a) {
+  hipLaunchKernelGGL(k_vrf, launch_grid(n), dim3(NT), 0, stream, n, items.list, items.count, gbtab, a);
 }
-void launch_vrf_ck(dim3 grid, dim3 block, hipStream_t stream, const uint32_t* list, const uint32_t* count,
-                   const int32_t* item_entry, const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* gbtab,
-                   const uint8_t* cold_vk, const uint8_t* vrf_vk, const uint8_t* vrf_out, const uint8_t* vrf_proof,
-                   const uint64_t* slot, const uint32_t* eta0, int eta0_neutral, const uint8_t* eta_idx,
-                   const uint32_t* pool_hash, const uint32_t* pool_vrf, const int32_t* pool_map, uint32_t npools,
-                   int check_output, const uint8_t* alpha_in, uint16_t* bits, int32_t* pool_idx,
-                   int32_t* pool_sorted_idx, uint8_t* beta_out, uint8_t* leader_out, uint8_t* nonce_out,
-                   uint8_t* ok_out, ge_cached* tabs) {
-  VrfIn a{cold_vk, vrf_vk, vrf_out, vrf_proof, slot, eta0, eta0_neutral, eta_idx, pool_hash, pool_vrf, pool_map, npools,
-          check_output, alpha_in, bits, pool_idx, pool_sorted_idx, beta_out, leader_out, nonce_out, ok_out, tabs};
-  hipLaunchKernelGGL(k_vrf_ck, grid, block, 0, stream, list, count, item_entry, ktab, kinfo, gbtab, a);
-}
-void launch_vrf_tp(dim3 grid, dim3 block, hipStream_t stream, size_t n, const ge_niels* gbtab, const uint8_t* cold_vk,
-                   const uint8_t* vrf_vk, const uint8_t* eta_out, const uint8_t* eta_proof, const uint8_t* l_out,
-                   const uint8_t* l_proof, const uint64_t* slot, const uint32_t* eta0, int eta0_neutral,
-                   const uint32_t* pool_hash, const uint32_t* pool_vrf, const int32_t* pool_map, uint32_t npools,
-                   int check_output, uint16_t* bits, int32_t* pool_idx, int32_t* pool_sorted_idx, uint8_t* beta_eta,
-                   uint8_t* beta_l, uint8_t* nonce_out, ge_cached* tabs, const int32_t* ovl_class,
-                   const uint32_t* gen, const uint8_t* eta_idx) {
-  hipLaunchKernelGGL(k_vrf_tp, grid, block, 0, stream, n, gbtab, cold_vk, vrf_vk, eta_out, eta_proof, l_out, l_proof,
-                     slot, eta0, eta0_neutral, pool_hash, pool_vrf, pool_map, npools, check_output, bits, pool_idx,
-                     pool_sorted_idx, beta_eta, beta_l, nonce_out, tabs, ovl_class, gen, eta_idx);
+void launch_vrf_tp(hipStream_t stream, size_t n, const ge_niels* gbtab, const VrfIn& a, const uint8_t* l_out,
+                   const uint8_t* l_proof, uint8_t* beta_l, const int32_t* ovl_class, const uint32_t* gen) {
+  hipLaunchKernelGGL(k_vrf_tp, launch_grid(n), dim3(NT), 0, stream, n, gbtab, a.cold_vk, a.vrf_vk, a.vrf_out,
+                     a.vrf_proof, l_out, l_proof, a.slot, a.eta0, a.eta0_neutral, a.pool_hash, a.pool_vrf, a.pool_map,
+                     a.npools, a.check_output, a.bits, a.pool_idx, a.pool_sorted_idx, a.beta_out, beta_l, a.nonce_out,
+                     a.tabs, ovl_class, gen, a.eta_idx);
 }

@@ -3,41 +3,6 @@
 // TPraos; k_vrf_stage.hip: the staged header pipeline)
 #include "kcommon.hpp"
 
-// Header mode: issuer hash -> pool (binary search), VRF key hash, alpha =
-// mkInputVRF(slot, eta0), proof verify, beta, output check, leader/nonce values.
-// Plain mode (ok_out != null): alpha given per item; ok_out, beta only.
-struct VrfIn {
-  const uint8_t* __restrict__ cold_vk;
-  const uint8_t* __restrict__ vrf_vk;
-  const uint8_t* __restrict__ vrf_out;
-  const uint8_t* __restrict__ vrf_proof;
-  const uint64_t* __restrict__ slot;
-  const uint32_t* __restrict__ eta0;     // eta_idx == null: the epoch nonce (8 words)
-  int eta0_neutral;
-  const uint8_t* __restrict__ eta_idx;   // several epochs per batch: header i uses entry eta_idx[i]
-                                         // of eta0 = table of 9-word entries (nonce, neutral flag)
-  const uint32_t* __restrict__ pool_hash;
-  const uint32_t* __restrict__ pool_vrf;
-  const int32_t* __restrict__ pool_map;
-  uint32_t npools;
-  int check_output;
-  const uint8_t* __restrict__ alpha_in;
-  uint16_t* __restrict__ bits;
-  int32_t* __restrict__ pool_idx;
-  int32_t* __restrict__ pool_sorted_idx;
-  uint8_t* __restrict__ beta_out;
-  uint8_t* __restrict__ leader_out;
-  uint8_t* __restrict__ nonce_out;
-  uint8_t* __restrict__ ok_out;
-  ge_cached* __restrict__ tabs;          // per-lane tables (LT_VRF entries per item)
-  int wave_prio;                         // stage V / join waves at s_setprio 3 (small batches)
-  int tp_seed;                           // stage V alpha: 0 Praos mkInputVRF; 1 + k TPraos mkSeed
-                                         // with ucNonce k (0 seedEta, 1 seedL)
-  int pre;                               // join: the pool part ran ahead (k_vrf_pool wrote bits[i])
-  const int32_t* __restrict__ rec_entry; // join / k_vrf_pool: header i's VRF key-cache entry or -1 ...
-  const uint32_t* __restrict__ rec;      // ... and the per-entry pool records (k_vrf_keyrec), or null
-};
-
 // issuer pool: hashKey (Blake2b-224 of the cold vk, Praos.hs:552) -> sorted index or -1
 __device__ __forceinline__ int32_t pool_search(const uint32_t hk[8], const uint32_t* __restrict__ pool_hash,
                                                uint32_t npools) {
@@ -114,12 +79,23 @@ __device__ __forceinline__ void header_alpha(uint32_t alpha[8], const VrfIn& a, 
   else mk_input_vrf(alpha, a.slot[i], e0, neutral);
 }
 
-static inline VrfIn vrf_in(const uint8_t* cold_vk, const uint8_t* vrf_vk, const uint8_t* vrf_out, const uint8_t* vrf_proof,
-                    const uint64_t* slot, const uint32_t* eta0, int eta0_neutral, const uint8_t* eta_idx,
-                    const uint32_t* pool_hash, const uint32_t* pool_vrf, const int32_t* pool_map, uint32_t npools,
-                    int check_output, uint16_t* bits, int32_t* pool_idx, int32_t* pool_sorted_idx, uint8_t* beta_out,
-                    uint8_t* leader_out, uint8_t* nonce_out, ge_cached* tabs) {
-  return VrfIn{cold_vk, vrf_vk, vrf_out, vrf_proof, slot, eta0, eta0_neutral, eta_idx, pool_hash, pool_vrf, pool_map,
-               npools, check_output, nullptr, bits, pool_idx, pool_sorted_idx, beta_out, leader_out, nonce_out, nullptr,
-               tabs};
+// Stage V of header i (k_vrf_stage.hip k_vrf_v; k_vrf_v4 / k_vrf_v4x from the ILP-4 build): alpha, H,
+// Gamma and V into the stage record (stride n)
+__device__ __forceinline__ void vrf_v_item(const VrfIn& a, size_t n, size_t i, uint4* mid) {
+  uint32_t pk[8], pr[20], alpha[8];
+  load_words(pk, a.vrf_vk + 32 * i, 8);
+  load_words(pr, a.vrf_proof + 80 * i, 20);
+  header_alpha(alpha, a, i);
+  vrf_v_core(mid, n, i, pk, pr, pr + 8, pr + 12, alpha, lane_tab(a.tabs, i, LT_VRF));
+}
+
+// Stage U of header i, a hit of the VRF key cache (k_vrf_u; k_vrf_u4): the key's tables and the comb
+__device__ __forceinline__ void vrf_u_item(uint4* mid, size_t stride, size_t i,
+                                           const int32_t* item_entry,
+                                           const ge_cached* ktab, const uint32_t* kinfo,
+                                           const ge_niels* comb, const uint8_t* vrf_proof) {
+  const size_t e = (size_t)item_entry[i];
+  uint32_t pr[20];
+  load_words(pr, vrf_proof + 80 * i, 20);
+  vrf_u_core<true>(mid, stride, i, nullptr, pr + 8, pr + 12, comb, nullptr, ktab + e * KT_STRIDE, kinfo + 9 * e);
 }

@@ -23,11 +23,7 @@ __global__ void __launch_bounds__(NT, LB_VRF_V) k_vrf_v(size_t n, size_t i0, siz
   const size_t i = i0 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // headers [i0, i1), record stride n
   if (i >= i1) return;
   if (a.wave_prio) __builtin_amdgcn_s_setprio(3);
-  uint32_t pk[8], pr[20], alpha[8];
-  load_words(pk, a.vrf_vk + 32 * i, 8);
-  load_words(pr, a.vrf_proof + 80 * i, 20);
-  header_alpha(alpha, a, i);
-  vrf_v_core(mid, n, i, pk, pr, pr + 8, pr + 12, alpha, lane_tab(a.tabs, i, LT_VRF));
+  vrf_v_item(a, n, i, mid);
 }
 
 // stage F: pool lookup and key hash (Praos.hs:533-541), U + challenge + beta, the output
@@ -141,11 +137,7 @@ __global__ void __launch_bounds__(NT, LB_VRF_F) k_vrf_u(size_t stride, const uin
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (size_t)*count) return;
   wave_setprio(prio);
-  const size_t i = list[t];
-  const size_t e = (size_t)item_entry[i];
-  uint32_t pr[20];
-  load_words(pr, vrf_proof + 80 * i, 20);
-  vrf_u_core<true>(mid, stride, i, nullptr, pr + 8, pr + 12, comb, nullptr, ktab + e * KT_STRIDE, kinfo + 9 * e);
+  vrf_u_item(mid, stride, list[t], item_entry, ktab, kinfo, comb, vrf_proof);
 }
 
 // U of a key of the wide tier (their own hit list): the key's positional tables
@@ -356,109 +348,62 @@ __global__ void __launch_bounds__(NT, LB_VRF_J) k_vrf_join_tp(size_t n, int cert
   a.bits[i] = b;
 }
 
-// ---- host launchers (kernels are only launchable from their own module)
-void launch_vrf_v(hipStream_t stream, size_t n, const uint8_t* vrf_vk, const uint8_t* vrf_proof, const uint64_t* slot,
-                  const uint32_t* eta0, int eta0_neutral, const uint8_t* eta_idx, ge_cached* tabs, void* mid,
-                  size_t i0, size_t i1, int wave_prio, int tp_seed, int ilp4) {
-  if (ilp4) {
-    launch_vrf_v4(stream, n, i0, i1, vrf_vk, vrf_proof, slot, eta0, eta0_neutral, eta_idx, tabs, mid, wave_prio,
-                  tp_seed, ilp4 > 1);
-    return;
-  }
-  VrfIn a = vrf_in(nullptr, vrf_vk, nullptr, vrf_proof, slot, eta0, eta0_neutral, eta_idx, nullptr, nullptr,
-                   nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tabs);
-  a.wave_prio = wave_prio;
-  a.tp_seed = tp_seed;
-  const unsigned bs = lat_block(n);
+// ---- host launchers (kernels are only launchable from their own module; the ILP-4 twins'
+// launchers are k_vrf_v4.hip's).
+void launch_vrf_v(hipStream_t stream, size_t n, const VrfIn& a, void* mid, size_t i0, size_t i1, int ilp4) {
   i1 = i1 < n ? i1 : n;
   if (i1 <= i0) return;
-  hipLaunchKernelGGL(k_vrf_v, dim3((unsigned)((i1 - i0 + bs - 1) / bs)), dim3(bs), 0, stream, n, i0, i1, a,
-                     (uint4*)mid);
+  if (ilp4) return launch_vrf_v4(stream, n, i0, i1, a, mid, ilp4 > 1);
+  hipLaunchKernelGGL(k_vrf_v, launch_grid(i1 - i0), dim3(NT), 0, stream, n, i0, i1, a, (uint4*)mid);
 }
-void launch_vrf_fin(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count,
-                    const int32_t* item_entry, const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* comb,
-                    const ge_niels* gbtab, const uint8_t* cold_vk, const uint8_t* vrf_vk, const uint8_t* vrf_out,
-                    const uint8_t* vrf_proof, const uint32_t* pool_hash, const uint32_t* pool_vrf,
-                    const int32_t* pool_map, uint32_t npools, int check_output, uint16_t* bits, int32_t* pool_idx,
-                    int32_t* pool_sorted_idx, uint8_t* beta_out, uint8_t* leader_out, uint8_t* nonce_out,
-                    ge_cached* tabs, const void* mid, const int32_t* entry_wide, const uint32_t* rec) {
-  VrfIn a = vrf_in(cold_vk, vrf_vk, vrf_out, vrf_proof, nullptr, nullptr, 0, nullptr, pool_hash, pool_vrf,
-                   pool_map, npools, check_output, bits, pool_idx, pool_sorted_idx, beta_out, leader_out,
-                   nonce_out, tabs);
-  a.rec = ktab ? rec : nullptr;
-  const dim3 g((unsigned)((n + NT - 1) / NT));
+void launch_vrf_fin(hipStream_t stream, size_t n, KeyItems items, const ge_niels* gbtab, const VrfIn& in,
+                    const void* mid) {
+  VrfIn a = in;
+  a.rec = nullptr;                              // (the records are the cached keys')
+  hipLaunchKernelGGL(k_vrf_fin_nc, launch_grid(n), dim3(NT), 0, stream, n, items.list, items.count, gbtab, a,
+                     (const uint4*)mid);
+}
+void launch_vrf_fin(hipStream_t stream, size_t n, const KeyHits& h, const ge_niels* comb, const VrfIn& a,
+                    const void* mid, const int32_t* entry_wide) {
   if (entry_wide)
-    hipLaunchKernelGGL(k_vrf_fin_w, g, dim3(NT), 0, stream, n, list, count, item_entry, entry_wide, ktab, kinfo, comb,
-                       a, (const uint4*)mid);
-  else if (ktab)
-    hipLaunchKernelGGL(k_vrf_fin, g, dim3(NT), 0, stream, n, list, count, item_entry, ktab, kinfo, comb, a,
-                       (const uint4*)mid);
+    hipLaunchKernelGGL(k_vrf_fin_w, launch_grid(n), dim3(NT), 0, stream, n, h.list, h.count, h.item_entry, entry_wide,
+                       h.ktab, h.kinfo, comb, a, (const uint4*)mid);
   else
-    hipLaunchKernelGGL(k_vrf_fin_nc, g, dim3(NT), 0, stream, n, list, count, gbtab, a, (const uint4*)mid);
+    hipLaunchKernelGGL(k_vrf_fin, launch_grid(n), dim3(NT), 0, stream, n, h.list, h.count, h.item_entry, h.ktab,
+                       h.kinfo, comb, a, (const uint4*)mid);
 }
-void launch_vrf_u(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count, const int32_t* item_entry,
-                  const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* comb, const ge_niels* gbtab,
-                  const uint8_t* vrf_vk, const uint8_t* vrf_proof, ge_cached* utabs, void* mid, int ilp4,
-                  int prio, const int32_t* entry_wide) {
-  const dim3 g((unsigned)((n + NT - 1) / NT));
-  const unsigned bs = lat_block(n);
+void launch_vrf_u(hipStream_t stream, size_t n, KeyItems items, const ge_niels* gbtab, const VrfIn& a,
+                  ge_cached* utabs, void* mid) {
+  hipLaunchKernelGGL(k_vrf_u_nc, launch_grid(n), dim3(NT), 0, stream, n, items.list, items.count, gbtab, a.vrf_vk,
+                     a.vrf_proof, utabs, (uint4*)mid);
+}
+void launch_vrf_u(hipStream_t stream, size_t n, const KeyHits& h, const ge_niels* comb, const VrfIn& a, void* mid,
+                  int ilp4, const int32_t* entry_wide) {
   if (entry_wide)
-    hipLaunchKernelGGL(k_vrf_u_w, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, stream, n, list, count, item_entry,
-                       entry_wide, ktab, kinfo, comb, vrf_proof, (uint4*)mid, prio);
-  else if (ktab && ilp4)
-    launch_vrf_u4(stream, n, list, count, item_entry, ktab, kinfo, comb, vrf_proof, mid, prio);
-  else if (ktab)
-    hipLaunchKernelGGL(k_vrf_u, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, stream, n, list, count, item_entry,
-                       ktab, kinfo, comb, vrf_proof, (uint4*)mid, prio);
+    hipLaunchKernelGGL(k_vrf_u_w, launch_grid(n), dim3(NT), 0, stream, n, h.list, h.count, h.item_entry, entry_wide,
+                       h.ktab, h.kinfo, comb, a.vrf_proof, (uint4*)mid, a.wave_prio);
+  else if (ilp4)
+    launch_vrf_u4(stream, n, h, comb, a.vrf_proof, mid, a.wave_prio);
   else
-    hipLaunchKernelGGL(k_vrf_u_nc, g, dim3(NT), 0, stream, n, list, count, gbtab, vrf_vk, vrf_proof, utabs,
-                       (uint4*)mid);
+    hipLaunchKernelGGL(k_vrf_u, launch_grid(n), dim3(NT), 0, stream, n, h.list, h.count, h.item_entry, h.ktab, h.kinfo,
+                       comb, a.vrf_proof, (uint4*)mid, a.wave_prio);
 }
-void launch_vrf_join(hipStream_t stream, size_t n, const uint8_t* cold_vk, const uint8_t* vrf_vk,
-                     const uint8_t* vrf_out, const uint8_t* vrf_proof, const uint32_t* pool_hash,
-                     const uint32_t* pool_vrf, const int32_t* pool_map, uint32_t npools, int check_output,
-                     uint16_t* bits, int32_t* pool_idx, int32_t* pool_sorted_idx, uint8_t* beta_out,
-                     uint8_t* leader_out, uint8_t* nonce_out, const void* mid, int wave_prio, int pre,
-                     const int32_t* rec_entry, const uint32_t* rec) {
-  VrfIn a = vrf_in(cold_vk, vrf_vk, vrf_out, vrf_proof, nullptr, nullptr, 0, nullptr, pool_hash, pool_vrf,
-                   pool_map, npools, check_output, bits, pool_idx, pool_sorted_idx, beta_out, leader_out,
-                   nonce_out, nullptr);
-  a.wave_prio = wave_prio;
-  a.pre = pre;
-  a.rec_entry = rec_entry;
-  a.rec = rec_entry ? rec : nullptr;
-  const unsigned bs = lat_block(n);
-  hipLaunchKernelGGL(k_vrf_join, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, stream, n, a, (const uint4*)mid);
+void launch_vrf_join(hipStream_t stream, size_t n, const VrfIn& in, const void* mid) {
+  VrfIn a = in;
+  a.rec = a.rec_entry ? a.rec : nullptr;
+  hipLaunchKernelGGL(k_vrf_join, launch_grid(n), dim3(NT), 0, stream, n, a, (const uint4*)mid);
 }
-void launch_vrf_pool(hipStream_t stream, size_t n, const uint8_t* cold_vk, const uint8_t* vrf_vk,
-                     const uint8_t* vrf_out, const uint32_t* pool_hash, const uint32_t* pool_vrf,
-                     const int32_t* pool_map, uint32_t npools, uint16_t* bits, int32_t* pool_idx,
-                     int32_t* pool_sorted_idx, uint8_t* leader_out, uint8_t* nonce_out, const int32_t* rec_entry,
-                     const uint32_t* rec) {
-  VrfIn a = vrf_in(cold_vk, vrf_vk, vrf_out, nullptr, nullptr, nullptr, 0, nullptr, pool_hash, pool_vrf,
-                   pool_map, npools, 0, bits, pool_idx, pool_sorted_idx, nullptr, leader_out, nonce_out,
-                   nullptr);
-  a.rec_entry = rec_entry;
-  a.rec = rec_entry ? rec : nullptr;
-  hipLaunchKernelGGL(k_vrf_pool, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, stream, n, a);
+void launch_vrf_pool(hipStream_t stream, size_t n, const VrfIn& in) {
+  VrfIn a = in;
+  a.rec = a.rec_entry ? a.rec : nullptr;
+  hipLaunchKernelGGL(k_vrf_pool, launch_grid(n), dim3(NT), 0, stream, n, a);
 }
 void launch_vrf_keyrec(hipStream_t stream, const uint32_t* counters, uint32_t max_entries, const uint32_t* entry_rep,
-                       const uint8_t* cold_vk, const uint8_t* vrf_vk, const uint32_t* pool_hash,
-                       const uint32_t* pool_vrf, const int32_t* pool_map, uint32_t npools, uint32_t* rec) {
-  const VrfIn a = vrf_in(cold_vk, vrf_vk, nullptr, nullptr, nullptr, nullptr, 0, nullptr, pool_hash, pool_vrf,
-                         pool_map, npools, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  hipLaunchKernelGGL(k_vrf_keyrec, dim3((max_entries + NT - 1) / NT), dim3(NT), 0, stream, counters, max_entries,
-                     entry_rep, a, rec);
+                       const VrfIn& a, uint32_t* rec) {
+  hipLaunchKernelGGL(k_vrf_keyrec, launch_grid(max_entries), dim3(NT), 0, stream, counters, max_entries, entry_rep, a,
+                     rec);
 }
-void launch_vrf_join_tp(hipStream_t stream, size_t n, int cert, const uint8_t* cold_vk, const uint8_t* vrf_vk,
-                        const uint8_t* cert_out, const uint8_t* cert_proof, const uint32_t* pool_hash,
-                        const uint32_t* pool_vrf, const int32_t* pool_map, uint32_t npools, int check_output,
-                        uint16_t* bits, int32_t* pool_idx, int32_t* pool_sorted_idx, uint8_t* beta_out,
-                        uint8_t* nonce_out, const void* mid, const int32_t* ovl_class, const uint32_t* gen) {
-  const VrfIn a = vrf_in(cold_vk, vrf_vk, cert_out, cert_proof, nullptr, nullptr, 0, nullptr, pool_hash, pool_vrf,
-                         pool_map, npools, check_output, bits, pool_idx, pool_sorted_idx, beta_out, nullptr,
-                         nonce_out, nullptr);
-  const unsigned bs = lat_block(n);
-  hipLaunchKernelGGL(k_vrf_join_tp, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, stream, n, cert, a,
-                     (const uint4*)mid, ovl_class, gen);
+void launch_vrf_join_tp(hipStream_t stream, size_t n, int cert, const VrfIn& a, const void* mid,
+                        const int32_t* ovl_class, const uint32_t* gen) {
+  hipLaunchKernelGGL(k_vrf_join_tp, launch_grid(n), dim3(NT), 0, stream, n, cert, a, (const uint4*)mid, ovl_class, gen);
 }

@@ -12,11 +12,7 @@ __global__ void __launch_bounds__(NT, 2) k_vrf_v4(size_t n, size_t i0, size_t i1
   const size_t i = i0 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // headers [i0, i1), record stride n
   if (i >= i1) return;
   if (a.wave_prio) __builtin_amdgcn_s_setprio(3);
-  uint32_t pk[8], pr[20], alpha[8];
-  load_words(pk, a.vrf_vk + 32 * i, 8);
-  load_words(pr, a.vrf_proof + 80 * i, 20);
-  header_alpha(alpha, a, i);
-  vrf_v_core(mid, n, i, pk, pr, pr + 8, pr + 12, alpha, lane_tab(a.tabs, i, LT_VRF));
+  vrf_v_item(a, n, i, mid);
 }
 
 // The same kernel holding its SIMD alone: touching a255 makes every wave allocate its 202
@@ -29,11 +25,7 @@ __global__ void __launch_bounds__(NT, 1) k_vrf_v4x(size_t n, size_t i0, size_t i
   const size_t i = i0 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= i1) return;
   if (a.wave_prio) __builtin_amdgcn_s_setprio(3);
-  uint32_t pk[8], pr[20], alpha[8];
-  load_words(pk, a.vrf_vk + 32 * i, 8);
-  load_words(pr, a.vrf_proof + 80 * i, 20);
-  header_alpha(alpha, a, i);
-  vrf_v_core(mid, n, i, pk, pr, pr + 8, pr + 12, alpha, lane_tab(a.tabs, i, LT_VRF));
+  vrf_v_item(a, n, i, mid);
 }
 
 // Stage U of a cached key (k_vrf_stage.hip k_vrf_u) from the same ILP-4 build: small batches
@@ -48,30 +40,19 @@ __global__ void __launch_bounds__(NT, 2) k_vrf_u4(size_t stride, const uint32_t*
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (size_t)*count) return;
   wave_setprio(prio);
-  const size_t i = list[t];
-  const size_t e = (size_t)item_entry[i];
-  uint32_t pr[20];
-  load_words(pr, vrf_proof + 80 * i, 20);
-  vrf_u_core<true>(mid, stride, i, nullptr, pr + 8, pr + 12, comb, nullptr, ktab + e * KT_STRIDE, kinfo + 9 * e);
+  vrf_u_item(mid, stride, list[t], item_entry, ktab, kinfo, comb, vrf_proof);
 }
 
-void launch_vrf_u4(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count, const int32_t* item_entry,
-                   const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* comb, const uint8_t* vrf_proof,
+// ---- host launchers, called by k_vrf_stage.hip's only (launch.hpp)
+void launch_vrf_u4(hipStream_t stream, size_t n, const KeyHits& h, const ge_niels* comb, const uint8_t* vrf_proof,
                    void* mid, int prio) {
-  hipLaunchKernelGGL(k_vrf_u4, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, stream, n, list, count, item_entry,
-                     ktab, kinfo, comb, vrf_proof, (uint4*)mid, prio);
+  hipLaunchKernelGGL(k_vrf_u4, launch_grid(n), dim3(NT), 0, stream, n, h.list, h.count, h.item_entry, h.ktab, h.kinfo,
+                     comb, vrf_proof, (uint4*)mid, prio);
 }
 
-void launch_vrf_v4(hipStream_t stream, size_t n, size_t i0, size_t i1, const uint8_t* vrf_vk,
-                   const uint8_t* vrf_proof, const uint64_t* slot, const uint32_t* eta0, int eta0_neutral,
-                   const uint8_t* eta_idx, ge_cached* tabs, void* mid, int wave_prio, int tp_seed, int excl) {
-  VrfIn a = vrf_in(nullptr, vrf_vk, nullptr, vrf_proof, slot, eta0, eta0_neutral, eta_idx, nullptr, nullptr,
-                   nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tabs);
-  a.wave_prio = wave_prio;
-  a.tp_seed = tp_seed;
-  i1 = i1 < n ? i1 : n;
-  if (i1 <= i0) return;
-  const dim3 grid((unsigned)((i1 - i0 + NT - 1) / NT));
+// headers [i0, i1), i1 <= n and i0 < i1 (launch_vrf_v clamps)
+void launch_vrf_v4(hipStream_t stream, size_t n, size_t i0, size_t i1, const VrfIn& a, void* mid, int excl) {
+  const dim3 grid = launch_grid(i1 - i0);
   if (excl)
     hipLaunchKernelGGL(k_vrf_v4x, grid, dim3(NT), 0, stream, n, i0, i1, a, (uint4*)mid);
   else

@@ -16,6 +16,12 @@
 #include "launch.hpp"
 
 #define NT 256                      // threads per block (4 waves)
+// The launchers of the OCert, KES, VRF, key-cache and PBFT signature kernels take the item count and
+// launch ceil(n / NT) blocks of NT, the kernels without LDS tables (V / U / join of the VRF, the
+// cached-key Ed25519 chains) included: 1-wave blocks for small batches (so that 54k headers = 844
+// waves spread over all 256 CUs instead of 211 four-wave blocks) measured slower (k_vrf_v 2.70 ->
+// 2.98 ms at 54k, profiles/r03/timeline_54k_wave_blocks.txt): 4-wave blocks everywhere.
+static inline dim3 launch_grid(size_t n) { return dim3((unsigned)((n + NT - 1) / NT)); }
 // minimum waves per SIMD requested from the register allocator
 #ifndef LB_ED
 #define LB_ED 3

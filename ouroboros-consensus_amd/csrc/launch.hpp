@@ -4,41 +4,30 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
-// Block size of the kernels without LDS tables (V / U / join of the VRF, the cached-key
-// Ed25519 chains).  1-wave blocks for small batches (so that 54k headers = 844 waves spread
-// over all 256 CUs instead of 211 four-wave blocks) measured slower (k_vrf_v 2.70 -> 2.98 ms
-// at 54k, profiles/r03/timeline_54k_wave_blocks.txt): 4-wave blocks everywhere.
-static inline unsigned lat_block(size_t n) { (void)n; return 256u; }
-struct ge_niels;
-struct ge_cached;
-void launch_ocert(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count,
-                  const ge_niels* gbtab, const uint8_t* cold_vk, const uint8_t* hot_vk, const uint64_t* ocert_n,
-                  const uint64_t* ocert_c0, const uint8_t* sig, const uint64_t* slot, uint64_t slots_per_kes_period,
-                  uint64_t max_kes_evo, uint16_t* bits, uint8_t* ok_out, ge_cached* tabs);
-void launch_ocert_ck(dim3 grid, dim3 block, hipStream_t stream, const uint32_t* list, const uint32_t* count,
-                     const int32_t* item_entry, const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* gbtab,
-                     const uint8_t* cold_vk, const uint8_t* hot_vk, const uint64_t* ocert_n, const uint64_t* ocert_c0,
-                     const uint8_t* sig, const uint64_t* slot, uint64_t slots_per_kes_period, uint64_t max_kes_evo,
-                     uint16_t* bits, uint8_t* ok_out, int prio = 0);
-void launch_vrf(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count,
-                const ge_niels* gbtab, const uint8_t* cold_vk, const uint8_t* vrf_vk, const uint8_t* vrf_out,
-                const uint8_t* vrf_proof, const uint64_t* slot, const uint32_t* eta0, int eta0_neutral,
-                const uint8_t* eta_idx, const uint32_t* pool_hash, const uint32_t* pool_vrf, const int32_t* pool_map,
-                uint32_t npools, int check_output, const uint8_t* alpha_in, uint16_t* bits, int32_t* pool_idx,
-                int32_t* pool_sorted_idx, uint8_t* beta_out, uint8_t* leader_out, uint8_t* nonce_out, uint8_t* ok_out,
-                ge_cached* tabs);
-void launch_vrf_ck(dim3 grid, dim3 block, hipStream_t stream, const uint32_t* list, const uint32_t* count,
-                   const int32_t* item_entry, const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* gbtab,
-                   const uint8_t* cold_vk, const uint8_t* vrf_vk, const uint8_t* vrf_out, const uint8_t* vrf_proof,
-                   const uint64_t* slot, const uint32_t* eta0, int eta0_neutral, const uint8_t* eta_idx,
-                   const uint32_t* pool_hash, const uint32_t* pool_vrf, const int32_t* pool_map, uint32_t npools,
-                   int check_output, const uint8_t* alpha_in, uint16_t* bits, int32_t* pool_idx,
-                   int32_t* pool_sorted_idx, uint8_t* beta_out, uint8_t* leader_out, uint8_t* nonce_out,
-                   uint8_t* ok_out, ge_cached* tabs);
+#include "kargs.hpp"
+// The launchers of the OCert, KES, VRF, key-cache and PBFT signature kernels take the stream, the
+// item count n (they launch ceil(n / 256) blocks of 256: kcommon.hpp launch_grid), the list they run
+// over (KeyItems: null list = every i < n; KeyHits: a cache's hits), the tables, and the kernel's
+// argument struct (kargs.hpp), which goes to the kernel as it is but for the fields a launcher is
+// said to clear.  "reads" names the struct fields the kernels behind a launcher read: a caller may
+// leave the others as they are.  ilp4: the kernel's twin from the ILP-4 build (the end of this file).
+
+// OCert.  launch_ocert (k_ocert; ilp4: k_ocert4, list mode only) reads cold_vk, hot_vk, ocert_n,
+// ocert_c0, sig, tabs, and ok_out (non-null: the verdict goes there and slot, slots_per_kes_period,
+// max_kes_evo, bits are not read); ilp4 also wave_prio (non-zero: waves at s_setprio 3).
+// launch_ocert_ck (k_ocert_ck; ilp4: k_ocert_ck4) reads the same but tabs, and wave_prio (2 or 3;
+// ilp4: not read).
+void launch_ocert(hipStream_t stream, size_t n, KeyItems items, const ge_niels* gbtab, const OcertIn& a, int ilp4 = 0);
+void launch_ocert_ck(hipStream_t stream, size_t n, const KeyHits& h, const ge_niels* comb, const OcertIn& a,
+                     int ilp4 = 0);
+// One-kernel VRF (k_vrf), the plain praos_verify_vrf batch: reads vrf_vk, vrf_proof, tabs, alpha_in,
+// ok_out, beta_out (null: not written).  With alpha_in null it is the header mode (every field up to
+// nonce_out; leader_out / nonce_out / beta_out null: not written), which has no caller.
+void launch_vrf(hipStream_t stream, size_t n, KeyItems items, const ge_niels* gbtab, const VrfIn& a);
 // pentry / pkey / pmask: the pool-key store probed first (null: none)
-void launch_key_insert(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count,
-                       const uint8_t* keys, uint32_t mask, uint32_t* slot_rep, uint32_t* slot_cnt, int32_t* item_slot,
-                       const int32_t* pentry, const uint32_t* pkey, uint32_t pmask, uint32_t* scnt);
+void launch_key_insert(hipStream_t stream, size_t n, KeyItems items, const uint8_t* keys, uint32_t mask,
+                       uint32_t* slot_rep, uint32_t* slot_cnt, int32_t* item_slot, const int32_t* pentry,
+                       const uint32_t* pkey, uint32_t pmask, uint32_t* scnt);
 // stored entries' hit-list ranges (after the new keys'), from their uses this run
 void launch_key_store_ranges(hipStream_t stream, uint32_t entries, const uint32_t* scnt, uint32_t* spos,
                              uint32_t* counters);
@@ -52,17 +41,17 @@ struct KeyWide {
   uint32_t *wide_ent = nullptr, *wcnt = nullptr, *hit = nullptr;
   ge_cached *wtab = nullptr, *wbase = nullptr;
 };
-void launch_key_assign(dim3 grid, dim3 block, hipStream_t stream, uint32_t cap, const uint32_t* slot_rep,
-                       const uint32_t* slot_cnt, uint32_t min_count, uint32_t max_entries, int32_t* slot_entry,
-                       uint32_t* entry_rep, uint32_t* entry_pos, uint32_t* counters, const KeyWide& w = KeyWide());
-void launch_key_partition(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint32_t* list,
-                          const uint32_t* count, const int32_t* item_slot, const int32_t* slot_entry,
-                          int32_t* item_entry, uint32_t* entry_pos, uint32_t* hit_list, uint32_t* miss_list,
-                          uint32_t* counters, uint32_t* spos, const KeyWide& w = KeyWide());
-void launch_ocert_dedup(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint8_t* cold, const uint8_t* hot,
+// one lane per hash-set slot (cap of them)
+void launch_key_assign(hipStream_t stream, uint32_t cap, const uint32_t* slot_rep, const uint32_t* slot_cnt,
+                       uint32_t min_count, uint32_t max_entries, int32_t* slot_entry, uint32_t* entry_rep,
+                       uint32_t* entry_pos, uint32_t* counters, const KeyWide& w = KeyWide());
+void launch_key_partition(hipStream_t stream, size_t n, KeyItems items, const int32_t* item_slot,
+                          const int32_t* slot_entry, int32_t* item_entry, uint32_t* entry_pos, uint32_t* hit_list,
+                          uint32_t* miss_list, uint32_t* counters, uint32_t* spos, const KeyWide& w = KeyWide());
+void launch_ocert_dedup(hipStream_t stream, size_t n, const uint8_t* cold, const uint8_t* hot,
                         const uint64_t* on, const uint64_t* oc, const uint8_t* sig, uint32_t mask, uint32_t* slot_rep,
                         uint32_t* item_rep, uint32_t* reps, uint32_t* counters);
-void launch_ocert_fanout(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint32_t* item_rep,
+void launch_ocert_fanout(hipStream_t stream, size_t n, const uint32_t* item_rep,
                          const uint8_t* ok, const uint64_t* slot, const uint64_t* oc, uint64_t slots_per_kes_period,
                          uint64_t max_kes_evo, uint16_t* bits);
 // entries [*base (0 when null), min(counters[0], max_entries)), at most span of them
@@ -71,53 +60,26 @@ void launch_key_precompute(int kind, hipStream_t stream, const uint32_t* counter
                            int wave_prio, const uint32_t* base, uint32_t span,
                            int mode,                       // 1: the chain from the ILP-4 build (k_keys4.hip)
                            const KeyWide& w = KeyWide());
-void launch_key_precompute4(int kind, hipStream_t stream, const uint32_t* counters, uint32_t max_entries,
-                            const uint32_t* entry_rep, const uint8_t* keys, ge_cached* ktab, uint32_t* kinfo,
-                            int wave_prio, const uint32_t* base, uint32_t span);
 void launch_pkey_reset(hipStream_t stream, uint32_t* count, int32_t* pentry, uint32_t slots, uint32_t limit, int force);
 void launch_pkey_publish(hipStream_t stream, const uint32_t* counters, const uint32_t* base, uint32_t max_entries,
                          const uint32_t* entry_rep, const uint8_t* keys, int32_t* pentry, uint32_t* pkey,
                          uint32_t pmask, uint32_t* count, uint32_t span);
-// the cached verifies of a small batch from the ILP-4 build (k_miss4.hip)
-void launch_ocert_ck4(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count,
-                      const int32_t* item_entry, const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* gbtab,
-                      const uint8_t* cold_vk, const uint8_t* hot_vk, const uint64_t* ocert_n, const uint64_t* ocert_c0,
-                      const uint8_t* sig, const uint64_t* slot, uint64_t slots_per_kes_period, uint64_t max_kes_evo,
-                      uint16_t* bits, uint8_t* ok_out);
-void launch_kes_ck4(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count,
-                    const int32_t* item_entry, const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* gbtab,
-                    const uint8_t* hot_vk, const uint8_t* kes_sig, const uint64_t* body_off, const uint32_t* body_len,
-                    const uint8_t* body, size_t body_bytes_len, const uint64_t* slot, const uint64_t* ocert_c0,
-                    uint64_t slots_per_kes_period, uint16_t* bits);
-// the uncached verifies of a small batch from the ILP-4 build (k_miss4.hip), list mode only
-void launch_ocert4(dim3 grid, dim3 block, hipStream_t stream, const uint32_t* list, const uint32_t* count,
-                   const ge_niels* gbtab, const uint8_t* cold_vk, const uint8_t* hot_vk, const uint64_t* ocert_n,
-                   const uint64_t* ocert_c0, const uint8_t* sig, const uint64_t* slot, uint64_t slots_per_kes_period,
-                   uint64_t max_kes_evo, uint16_t* bits, uint8_t* ok_out, ge_cached* tabs, int prio);
-void launch_kes4(dim3 grid, dim3 block, hipStream_t stream, const uint32_t* list, const uint32_t* count,
-                 const ge_niels* gbtab, const uint8_t* hot_vk, const uint8_t* kes_sig, const uint64_t* body_off,
-                 const uint32_t* body_len, const uint8_t* body, size_t body_bytes_len, const uint64_t* slot,
-                 const uint64_t* ocert_c0, uint64_t slots_per_kes_period, uint16_t* bits, ge_cached* tabs, int prio);
-void launch_kes(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count,
-                const ge_niels* gbtab, const uint8_t* hot_vk, const uint8_t* kes_sig, const uint64_t* body_off,
-                const uint32_t* body_len, const uint8_t* body, size_t body_bytes_len, const uint64_t* slot,
-                const uint64_t* ocert_c0, uint64_t slots_per_kes_period, const uint32_t* period, uint16_t* bits,
-                uint8_t* result, ge_cached* tabs);
-void launch_kes_ck(dim3 grid, dim3 block, hipStream_t stream, const uint32_t* list, const uint32_t* count,
-                   const int32_t* item_entry, const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* gbtab,
-                   const uint8_t* hot_vk, const uint8_t* kes_sig, const uint64_t* body_off, const uint32_t* body_len,
-                   const uint8_t* body, size_t body_bytes_len, const uint64_t* slot, const uint64_t* ocert_c0,
-                   uint64_t slots_per_kes_period, uint16_t* bits,
+// KES.  launch_kes (k_kes; ilp4: k_kes4, list mode only) reads hot_vk, kes_sig, body_off, body_len,
+// body, body_bytes_len, tabs, period (null: the period from slot, ocert_c0, slots_per_kes_period),
+// result (non-null: the verdict goes there, not to bits); ilp4 also wave_prio (non-zero: s_setprio 3).
+// launch_kes_ck (k_kes_ck, or k_kes_ck2 when pair_min != 0; ilp4: k_kes_ck4, which ignores pair_min,
+// entry_rep / rep_ok and wave_prio) reads the same but tabs, and wave_prio (2 or 3).
+// launch_kes_merkle_reps reads hot_vk, kes_sig and the period's fields; launch_kes_leafkeys kes_sig
+// and the period's fields.
+void launch_kes(hipStream_t stream, size_t n, KeyItems items, const ge_niels* gbtab, const KesIn& a, int ilp4 = 0);
+void launch_kes_ck(hipStream_t stream, size_t n, const KeyHits& h, const ge_niels* comb, const KesIn& a,
                    uint32_t pair_min,                       // two headers per lane from pair_min hits on (0: never)
                    const uint32_t* entry_rep,               // with rep_ok (k_kes_merkle_reps): the Merkle path
-                   const uint8_t* rep_ok, int prio = 0);                  // dedup per cache entry (null: every item walks)
+                   const uint8_t* rep_ok,                   // dedup per cache entry (null: every item walks)
+                   int ilp4 = 0);
 void launch_kes_merkle_reps(hipStream_t stream, const uint32_t* counters, uint32_t max_entries,
-                            const uint32_t* entry_rep, const uint8_t* hot_vk, const uint8_t* kes_sig,
-                            const uint64_t* slot, const uint64_t* ocert_c0, uint64_t slots_per_kes_period,
-                            uint8_t* rep_ok);
-void launch_kes_leafkeys(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint8_t* kes_sig,
-                         const uint64_t* slot, const uint64_t* ocert_c0, uint64_t slots_per_kes_period,
-                         uint8_t* keys);
+                            const uint32_t* entry_rep, const KesIn& a, uint8_t* rep_ok);
+void launch_kes_leafkeys(hipStream_t stream, size_t n, const KesIn& a, uint8_t* keys);
 void launch_init_btab(dim3 grid, dim3 block, hipStream_t stream, ge_niels* btab);
 void launch_init_bcomb16(hipStream_t stream, const ge_niels* btab, ge_niels* bcomb16);
 void launch_leader(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint8_t* leader_in, const int32_t* pool_sorted_idx, const uint32_t* pool_x, const uint32_t* x_item, int f_is_one, int leader_words, const uint16_t* b_ocert, const uint16_t* b_kes, const uint16_t* b_vrf, uint16_t* bits, uint8_t* is_leader, int32_t* iters, const uint16_t* dec_status);
@@ -143,71 +105,54 @@ void launch_synth_leader_search(dim3 grid, dim3 block, hipStream_t stream, uint6
                                 const uint32_t* pool_thr, const uint32_t* eta0, int eta0_neutral, int f_is_one,
                                 int tpraos, int32_t* leader);
 void launch_synth_corrupt(dim3 grid, dim3 block, hipStream_t stream, size_t n, uint32_t per10000, uint64_t salt, uint8_t* ocert_sig, uint8_t* kes_sig, uint8_t* vrf_proof, uint8_t* vrf_out, uint8_t* body_bytes, const uint64_t* body_off, const uint32_t* body_len, uint8_t* corrupted, uint8_t* l_proof, int cbor_body, uint32_t fields, uint8_t* cold_vk, uint8_t* hot_vk, uint64_t* ocert_n, uint64_t* ocert_c0);
-// two-stage VRF of the header pipeline (k_vrf.hip): stage V over all n headers into the
-// record `mid` (VRF_MID_PLANES x 16 x n bytes); stage F over list[0 .. *count) (or all n when
-// list is null), cached (ktab != null: k_vrf_fin) or per-lane U (k_vrf_fin_nc)
-void launch_vrf_v(hipStream_t stream, size_t n, const uint8_t* vrf_vk, const uint8_t* vrf_proof, const uint64_t* slot,
-                  const uint32_t* eta0, int eta0_neutral, const uint8_t* eta_idx, ge_cached* tabs, void* mid,
-                  size_t i0 = 0, size_t i1 = SIZE_MAX,    // headers [i0, min(i1, n)); mid stride n
-                  int wave_prio = 0,                       // waves at s_setprio 3
-                  int tp_seed = 0,                         // 1 + k: TPraos mkSeed alpha, ucNonce k
-                  int ilp4 = 0);                           // 1: the ILP-4 build (k_vrf_v4.hip),
-                                                           // 2: the same holding its SIMD alone
-
-// stage V built with the ILP-4 group formulas at 2 waves per SIMD (k_vrf_v4.hip; small batches)
-void launch_vrf_v4(hipStream_t stream, size_t n, size_t i0, size_t i1, const uint8_t* vrf_vk,
-                   const uint8_t* vrf_proof, const uint64_t* slot, const uint32_t* eta0, int eta0_neutral,
-                   const uint8_t* eta_idx, ge_cached* tabs, void* mid, int wave_prio, int tp_seed, int excl);
-void launch_vrf_fin(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count,
-                    const int32_t* item_entry, const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* comb,
-                    const ge_niels* gbtab, const uint8_t* cold_vk, const uint8_t* vrf_vk, const uint8_t* vrf_out,
-                    const uint8_t* vrf_proof, const uint32_t* pool_hash, const uint32_t* pool_vrf,
-                    const int32_t* pool_map, uint32_t npools, int check_output, uint16_t* bits, int32_t* pool_idx,
-                    int32_t* pool_sorted_idx, uint8_t* beta_out, uint8_t* leader_out, uint8_t* nonce_out,
-                    ge_cached* tabs, const void* mid,
-                    const int32_t* entry_wide = nullptr,    // list = a wide hit list, ktab = the wide tables
-                    const uint32_t* rec = nullptr);         // cached keys: the entries' pool records (launch_vrf_keyrec)
-// three-kernel VRF: stage U (cached: ktab != null, k_vrf_u over the hit list; uncached: k_vrf_u_nc
-// over list[0 .. *count) or all n, 8-entry lane tables utabs) and the join over all n
-void launch_vrf_u(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count, const int32_t* item_entry,
-                  const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* comb, const ge_niels* gbtab,
-                  const uint8_t* vrf_vk, const uint8_t* vrf_proof, ge_cached* utabs, void* mid,
-                  int ilp4 = 0,                            // cached keys: the ILP-4 build (k_vrf_v4.hip k_vrf_u4)
-                  int prio = 0,                            // cached keys: waves at s_setprio <prio>
-                  const int32_t* entry_wide = nullptr);    // list = a wide hit list, ktab = the wide tables
-void launch_vrf_u4(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count, const int32_t* item_entry,
-                   const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* comb, const uint8_t* vrf_proof,
-                   void* mid, int prio = 0);
-void launch_vrf_join(hipStream_t stream, size_t n, const uint8_t* cold_vk, const uint8_t* vrf_vk,
-                     const uint8_t* vrf_out, const uint8_t* vrf_proof, const uint32_t* pool_hash,
-                     const uint32_t* pool_vrf, const int32_t* pool_map, uint32_t npools, int check_output,
-                     uint16_t* bits, int32_t* pool_idx, int32_t* pool_sorted_idx, uint8_t* beta_out,
-                     uint8_t* leader_out, uint8_t* nonce_out, const void* mid, int wave_prio = 0,
-                     int pre = 0,                          // pre: launch_vrf_pool ran before (bits, pool, leader, nonce)
-                     const int32_t* rec_entry = nullptr,   // the VRF key cache's item_entry and pool records
-                     const uint32_t* rec = nullptr);       // (launch_vrf_keyrec), or null
-// the join's pool part ahead of it (k_vrf_stage.hip k_vrf_pool): key bits, pool indices, leader / nonce
-void launch_vrf_pool(hipStream_t stream, size_t n, const uint8_t* cold_vk, const uint8_t* vrf_vk,
-                     const uint8_t* vrf_out, const uint32_t* pool_hash, const uint32_t* pool_vrf,
-                     const int32_t* pool_map, uint32_t npools, uint16_t* bits, int32_t* pool_idx,
-                     int32_t* pool_sorted_idx, uint8_t* leader_out, uint8_t* nonce_out,
-                     const int32_t* rec_entry = nullptr, const uint32_t* rec = nullptr);   // as launch_vrf_join
-// the pool record of each VRF key-cache entry (k_vrf_stage.hip k_vrf_keyrec; VREC_WORDS words per
-// entry): the pool part of the entry's representative, which the entry's headers with the same
-// cold key take instead of hashing and searching themselves
+// The staged VRF of the header pipeline (k_vrf_stage.hip; `mid`: the stage record, VRF_MID_PLANES x
+// 16 x n bytes).
+// Stage V over headers [i0, min(i1, n)), mid stride n (k_vrf_v; ilp4 1: k_vrf_v4 from the ILP-4 build,
+// 2: k_vrf_v4x, the same holding its SIMD alone): reads vrf_vk, vrf_proof, slot, eta0, eta0_neutral,
+// eta_idx (null: one nonce), tabs, wave_prio (non-zero: s_setprio 3), tp_seed.
+void launch_vrf_v(hipStream_t stream, size_t n, const VrfIn& a, void* mid, size_t i0 = 0, size_t i1 = SIZE_MAX,
+                  int ilp4 = 0);
+// Two-stage form, stage F = U + join over a list: the uncached keys (k_vrf_fin_nc: per-lane U;
+// clears rec) or a cache's hits (k_vrf_fin; entry_wide: k_vrf_fin_w, h = the wide tier's hits and
+// tables).  Reads cold_vk, vrf_vk, vrf_out, vrf_proof, the pool fields, check_output, bits, pool_idx,
+// pool_sorted_idx, beta_out, leader_out, nonce_out, tabs, and the hits rec (null: no pool records).
+// The two tables have one type: gbtab is the fixed-base comb of BCOMB_T tables (the context's btab,
+// staged into LDS), comb the radix-2^16 comb (the context's bcomb16, read in place).  The same holds
+// for launch_vrf_u, the OCert / KES launchers above and the PBFT ones below.
+void launch_vrf_fin(hipStream_t stream, size_t n, KeyItems items, const ge_niels* gbtab, const VrfIn& a,
+                    const void* mid);
+void launch_vrf_fin(hipStream_t stream, size_t n, const KeyHits& h, const ge_niels* comb, const VrfIn& a,
+                    const void* mid, const int32_t* entry_wide = nullptr);
+// Three-kernel form, stage U over a list: the uncached keys (k_vrf_u_nc, 8-entry lane tables utabs;
+// reads vrf_vk, vrf_proof) or a cache's hits (k_vrf_u; ilp4: k_vrf_u4; entry_wide: k_vrf_u_w, no ILP-4
+// form; reads vrf_proof, wave_prio 2 or 3) ...
+void launch_vrf_u(hipStream_t stream, size_t n, KeyItems items, const ge_niels* gbtab, const VrfIn& a,
+                  ge_cached* utabs, void* mid);
+void launch_vrf_u(hipStream_t stream, size_t n, const KeyHits& h, const ge_niels* comb, const VrfIn& a, void* mid,
+                  int ilp4 = 0, const int32_t* entry_wide = nullptr);
+// ... and the join over all n (k_vrf_join): reads what the cached stage F reads but tabs, and
+// wave_prio (non-zero: s_setprio 3), pre (launch_vrf_pool ran before: bits, pool, leader, nonce are
+// there), rec_entry (the VRF key cache's item_entry, or null) and rec; clears rec when rec_entry is null.
+void launch_vrf_join(hipStream_t stream, size_t n, const VrfIn& a, const void* mid);
+// the join's pool part ahead of it (k_vrf_pool): reads cold_vk, vrf_vk, vrf_out, the pool fields, bits,
+// pool_idx, pool_sorted_idx, leader_out, nonce_out, rec_entry, rec (cleared as by the join)
+void launch_vrf_pool(hipStream_t stream, size_t n, const VrfIn& a);
+// the pool record of each VRF key-cache entry (k_vrf_keyrec; VREC_WORDS words per entry): the pool
+// part of the entry's representative, which the entry's headers with the same cold key take instead
+// of hashing and searching themselves.  Reads cold_vk, vrf_vk and the pool fields.
 #define VREC_WORDS 12
 void launch_vrf_keyrec(hipStream_t stream, const uint32_t* counters, uint32_t max_entries, const uint32_t* entry_rep,
-                       const uint8_t* cold_vk, const uint8_t* vrf_vk, const uint32_t* pool_hash,
-                       const uint32_t* pool_vrf, const int32_t* pool_map, uint32_t npools, uint32_t* rec);
-// TPraos join of certificate cert (0: eta, 1: leader; k_vrf_stage.hip k_vrf_join_tp), after
-// stage V (tp_seed 1 + cert) and U of that certificate into `mid`
-void launch_vrf_join_tp(hipStream_t stream, size_t n, int cert, const uint8_t* cold_vk, const uint8_t* vrf_vk,
-                        const uint8_t* cert_out, const uint8_t* cert_proof, const uint32_t* pool_hash,
-                        const uint32_t* pool_vrf, const int32_t* pool_map, uint32_t npools, int check_output,
-                        uint16_t* bits, int32_t* pool_idx, int32_t* pool_sorted_idx, uint8_t* beta_out,
-                        uint8_t* nonce_out, const void* mid, const int32_t* ovl_class, const uint32_t* gen);
-void launch_vrf_tp(dim3 grid, dim3 block, hipStream_t stream, size_t n, const ge_niels* gbtab, const uint8_t* cold_vk, const uint8_t* vrf_vk, const uint8_t* eta_out, const uint8_t* eta_proof, const uint8_t* l_out, const uint8_t* l_proof, const uint64_t* slot, const uint32_t* eta0, int eta0_neutral, const uint32_t* pool_hash, const uint32_t* pool_vrf, const int32_t* pool_map, uint32_t npools, int check_output, uint16_t* bits, int32_t* pool_idx, int32_t* pool_sorted_idx, uint8_t* beta_eta, uint8_t* beta_l, uint8_t* nonce_out, ge_cached* tabs,
-                   const int32_t* ovl_class, const uint32_t* gen, const uint8_t* eta_idx = nullptr);
+                       const VrfIn& a, uint32_t* rec);
+// TPraos join of certificate cert (0: eta, 1: leader; k_vrf_join_tp), after stage V (tp_seed 1 + cert)
+// and U of that certificate into `mid`: reads cold_vk, vrf_vk, vrf_out / vrf_proof / beta_out (the
+// certificate's), the pool fields, check_output, bits, pool_idx, pool_sorted_idx, nonce_out.
+void launch_vrf_join_tp(hipStream_t stream, size_t n, int cert, const VrfIn& a, const void* mid,
+                        const int32_t* ovl_class, const uint32_t* gen);
+// one-kernel TPraos (k_vrf_tp, which takes the columns one by one): a's vrf_out / vrf_proof / beta_out
+// are the eta certificate's, l_* the leader certificate's; reads every field up to nonce_out but
+// alpha_in and leader_out, and tabs.
+void launch_vrf_tp(hipStream_t stream, size_t n, const ge_niels* gbtab, const VrfIn& a, const uint8_t* l_out,
+                   const uint8_t* l_proof, uint8_t* beta_l, const int32_t* ovl_class, const uint32_t* gen);
 void launch_decode_praos(dim3 grid, dim3 block, hipStream_t stream, size_t n, const uint8_t* arena, uint64_t arena_len,
                          const uint64_t* hoff, const uint32_t* hlen, uint64_t* slot, uint8_t* cold_vk, uint8_t* vrf_vk,
                          uint8_t* vrf_out, uint8_t* vrf_proof, uint8_t* hot_vk, uint8_t* ocert_sig, uint8_t* kes_sig,
@@ -310,11 +255,10 @@ void launch_pbft_decode(hipStream_t stream, size_t n, const uint8_t* arena, uint
                         const uint32_t* dtab, uint32_t n_delegs, uint64_t* slot, uint64_t* block_no,
                         uint8_t* prev_hash, uint8_t* prev_genesis, uint8_t* header_hash, uint8_t* bits, int32_t* gk_idx,
                         uint8_t* dhash, uint8_t* keys, uint8_t* sig, uint8_t* hram, uint32_t* vlist, uint32_t* vcount);
-void launch_pbft_sig(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count, const ge_niels* gbtab,
-                     const uint8_t* keys, const uint8_t* sig, const uint8_t* hram, uint8_t* bits, ge_cached* tabs);
-void launch_pbft_sig_ck(hipStream_t stream, size_t n, const uint32_t* list, const uint32_t* count,
-                        const int32_t* item_entry, const ge_cached* ktab, const uint32_t* kinfo, const ge_niels* comb,
-                        const uint8_t* keys, const uint8_t* sig, const uint8_t* hram, uint8_t* bits);
+void launch_pbft_sig(hipStream_t stream, size_t n, KeyItems items, const ge_niels* gbtab, const uint8_t* keys,
+                     const uint8_t* sig, const uint8_t* hram, uint8_t* bits, ge_cached* tabs);
+void launch_pbft_sig_ck(hipStream_t stream, size_t n, const KeyHits& h, const ge_niels* comb, const uint8_t* keys,
+                        const uint8_t* sig, const uint8_t* hram, uint8_t* bits);
 void launch_pbft_keyhash(hipStream_t stream, size_t n, const uint8_t* keys64, uint8_t* out28);
 // replay: nonce contribution of each header's certified VRF output (k_misc.hip)
 void launch_vrf_nonce(hipStream_t stream, size_t n, const uint8_t* vrf_out, int tpraos, uint8_t* nonce_out);
@@ -471,3 +415,17 @@ void launch_bf_verdict(hipStream_t stream, size_t n, size_t R, int byron_on, con
                        const uint32_t* item_row, const uint32_t* exp_idx, const uint64_t* exp_slot,
                        const uint8_t* exp_hash, const uint64_t* slot, const uint8_t* header_hash, const uint8_t* bits,
                        uint8_t* which, uint8_t* verdict);
+
+// ---- between kernel modules only: no host module calls these.  The launchers of the ILP-4 twins
+// (k_miss4.hip, k_vrf_v4.hip, k_keys4.hip: the same bodies built with PRAOS_ILP4), which the launchers
+// above forward to under their ilp4 / mode argument.
+void launch_ocert4(hipStream_t stream, size_t n, KeyItems items, const ge_niels* gbtab, const OcertIn& a);
+void launch_kes4(hipStream_t stream, size_t n, KeyItems items, const ge_niels* gbtab, const KesIn& a);
+void launch_ocert_ck4(hipStream_t stream, size_t n, const KeyHits& h, const ge_niels* comb, const OcertIn& a);
+void launch_kes_ck4(hipStream_t stream, size_t n, const KeyHits& h, const ge_niels* comb, const KesIn& a);
+void launch_vrf_v4(hipStream_t stream, size_t n, size_t i0, size_t i1, const VrfIn& a, void* mid, int excl);
+void launch_vrf_u4(hipStream_t stream, size_t n, const KeyHits& h, const ge_niels* comb, const uint8_t* vrf_proof,
+                   void* mid, int prio);
+void launch_key_precompute4(int kind, hipStream_t stream, const uint32_t* counters, uint32_t max_entries,
+                            const uint32_t* entry_rep, const uint8_t* keys, ge_cached* ktab, uint32_t* kinfo,
+                            int wave_prio, const uint32_t* base, uint32_t span);

@@ -75,9 +75,7 @@ int praos_block_batch_run(praos_ctx* c, praos_batch* b, uint64_t slots_per_kes_p
   launch_seg_hash(dim3(nblocks(4 * n, NT)), blk, c->side[0], n, b->arena, b->seg_off, b->seg_len, b->nseg,
                   b->seg_hash);
   HIPCHK(c, hipEventRecord(c->side_ev[0], c->side[0]));
-  launch_kes(g, blk, c->stream, n, (const uint32_t*)nullptr, (const uint32_t*)nullptr, c->btab, b->hot_vk, b->kes_sig, b->body_off, b->body_len, b->body,
-             b->body_bytes_len, b->slot, b->ocert_c0, slots_per_kes_period, (const uint32_t*)nullptr, bk,
-             (uint8_t*)nullptr, b->tab_kes);
+  launch_kes(c->stream, n, KeyItems{}, c->btab, batch_kes_in(b, slots_per_kes_period, bk));
   HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
   HIPCHK(c, hipStreamWaitEvent(c->stream, c->side_ev[0], 0));
   launch_block_join(g, blk, c->stream, n, b->nseg, b->split_status, b->dec_status, bk, b->seg_hash, b->body_hash,
@@ -378,17 +376,16 @@ static int pbft_verify_dev(praos_ctx* c, praos_batch* b, size_t n, const uint8_t
   // with it -- 21,600 headers 2.152 ms against the ILP-4 build's 2.175, 65,536 2.878 against
   // 2.960 -- and was not kept)
   auto sig_nc = [&](const uint32_t* list, const uint32_t* count) {   // uncached verifies over a list
-    launch_pbft_sig(st, n, list, count, c->btab, d_keys, d_sig, d_hram, d_bits, b->tab_ocert);
+    launch_pbft_sig(st, n, KeyItems{list, count}, c->btab, d_keys, d_sig, d_hram, d_bits, b->tab_ocert);
   };
   if (cached) {
     RunShape shape = run_shape(c, n, false, false);
     shape.pool_keys = 0;                               // the batch's own entries, not the pool-key store
     const RunPlan P = plan_run(c->knobs, shape);
-    const int r = kc_lists(c, b, P, k, n, d_keys, st, d_vlist, d_vcount, 0);
+    const int r = kc_lists(c, b, P, k, n, d_keys, st, KeyItems{d_vlist, d_vcount}, 0);
     if (r == PRAOS_OK) kc_precompute(c, P, k, d_keys, 0, st, n);
     if (r != PRAOS_OK) return r;
-    launch_pbft_sig_ck(st, n, k.hit, k.counters + 1, k.item_entry, k.kt, k.ki, c->bcomb16, d_keys, d_sig, d_hram,
-                       d_bits);
+    launch_pbft_sig_ck(st, n, key_hits(k), c->bcomb16, d_keys, d_sig, d_hram, d_bits);
     sig_nc(k.miss, k.counters + 2);
   } else {
     sig_nc(d_vlist, d_vcount);

@@ -47,8 +47,16 @@ int praos_verify_ocert(praos_ctx* c, size_t n, const uint8_t* cold_vk, const uin
   auto dtab = s.up<ge_cached>(nullptr, LT_ED_B * n);
   if (!s.ok) { c->err = "alloc/copy"; return PRAOS_E_OOM; }
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-  launch_ocert(dim3(nblocks(n, NT)), dim3(NT), c->stream, n, nullptr, nullptr, c->btab, dv, dh, dn, dc, ds,
-                     (const uint64_t*)nullptr, (uint64_t)1, (uint64_t)0, (uint16_t*)nullptr, dok, dtab);
+  OcertIn a{};                                   // plain mode: the verdicts to ok_out, no period checks
+  a.cold_vk = dv;
+  a.hot_vk = dh;
+  a.ocert_n = dn;
+  a.ocert_c0 = dc;
+  a.sig = ds;
+  a.slots_per_kes_period = 1;
+  a.ok_out = dok;
+  a.tabs = dtab;
+  launch_ocert(c->stream, n, KeyItems{}, c->btab, a);
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -84,10 +92,18 @@ int praos_verify_kes(praos_ctx* c, size_t n, const uint8_t* vk, const uint32_t* 
   auto dtab = s.up<ge_cached>(nullptr, LT_ED_B * n);
   if (!s.ok) { c->err = "alloc/copy"; return PRAOS_E_OOM; }
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-  launch_kes(dim3(nblocks(n, NT)), dim3(NT), c->stream, n, (const uint32_t*)nullptr, (const uint32_t*)nullptr,
-             c->btab, dvk, dsig, doff, dlen, dmsg,
-                     total, (const uint64_t*)nullptr, (const uint64_t*)nullptr, (uint64_t)1, dp, (uint16_t*)nullptr,
-                     dres, dtab);
+  KesIn a{};                                     // plain mode: the caller's periods, the verdicts to result
+  a.hot_vk = dvk;
+  a.kes_sig = dsig;
+  a.body_off = doff;
+  a.body_len = dlen;
+  a.body = dmsg;
+  a.body_bytes_len = total;
+  a.slots_per_kes_period = 1;
+  a.period = dp;
+  a.result = dres;
+  a.tabs = dtab;
+  launch_kes(c->stream, n, KeyItems{}, c->btab, a);
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -110,12 +126,15 @@ int praos_verify_vrf(praos_ctx* c, size_t n, const uint8_t* vk, const uint8_t* p
   auto dtab = s.up<ge_cached>(nullptr, LT_VRF_B * n);
   if (!s.ok) { c->err = "alloc/copy"; return PRAOS_E_OOM; }
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-  launch_vrf(dim3(nblocks(n, NT)), dim3(NT), c->stream, n, nullptr, nullptr, c->btab, (const uint8_t*)nullptr, dvk,
-                     (const uint8_t*)nullptr, dpr, (const uint64_t*)nullptr, (const uint32_t*)nullptr, 1,
-                     (const uint8_t*)nullptr,
-                     (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const int32_t*)nullptr, 0u, 0, dal,
-                     (uint16_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, dbeta, (uint8_t*)nullptr,
-                     (uint8_t*)nullptr, dok, dtab);
+  VrfIn a{};                                     // plain mode: the caller's alphas, ok and beta only
+  a.vrf_vk = dvk;
+  a.vrf_proof = dpr;
+  a.eta0_neutral = 1;
+  a.alpha_in = dal;
+  a.beta_out = dbeta;
+  a.ok_out = dok;
+  a.tabs = dtab;
+  launch_vrf(c->stream, n, KeyItems{}, c->btab, a);
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));

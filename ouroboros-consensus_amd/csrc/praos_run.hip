@@ -71,9 +71,8 @@ static bool ensure_pks(praos_ctx* c, int t, hipStream_t st) {
 }
 
 int kc_lists(praos_ctx* c, praos_batch* b, const RunPlan& P, praos_batch::KeyCache& k, size_t n, const uint8_t* keys,
-             hipStream_t st, const uint32_t* list, const uint32_t* count, int which) {
+             hipStream_t st, KeyItems items, int which) {
   int min_uses = P.min_uses[which];
-  const dim3 g(nblocks(n, NT)), blk(NT);
   k.kt = k.ktab; k.ki = k.kinfo; k.erep = k.entry_rep; k.epos = k.entry_pos; k.emax = k.max_entries;
   k.ebase = nullptr; k.store = -1;
   HIPCHK(c, hipMemsetAsync(k.slot_rep, 0, 4 * (size_t)k.cap, st));
@@ -118,14 +117,13 @@ int kc_lists(praos_ctx* c, praos_batch* b, const RunPlan& P, praos_batch::KeyCac
     k.wide.cap = need;
     HIPCHK(c, hipMemsetAsync(k.wide.wcnt, 0, 16, st));
   }
-  launch_key_insert(g, blk, st, n, list, count, keys, k.cap - 1, k.slot_rep, k.slot_cnt, k.item_slot,
-                    ps ? ps->pentry : nullptr, ps ? ps->pkey : nullptr, ps ? ps->slots - 1 : 0u,
-                    ps ? ps->scnt : nullptr);
-  launch_key_assign(dim3(nblocks(k.cap, NT)), blk, st, k.cap, k.slot_rep, k.slot_cnt, (uint32_t)min_uses,
-                    k.emax, k.slot_entry, k.erep, k.epos, k.counters, k.wide);
+  launch_key_insert(st, n, items, keys, k.cap - 1, k.slot_rep, k.slot_cnt, k.item_slot, ps ? ps->pentry : nullptr,
+                    ps ? ps->pkey : nullptr, ps ? ps->slots - 1 : 0u, ps ? ps->scnt : nullptr);
+  launch_key_assign(st, k.cap, k.slot_rep, k.slot_cnt, (uint32_t)min_uses, k.emax, k.slot_entry, k.erep, k.epos,
+                    k.counters, k.wide);
   if (ps) launch_key_store_ranges(st, ps->cap, ps->scnt, ps->spos, k.counters);
-  launch_key_partition(g, blk, st, n, list, count, k.item_slot, k.slot_entry, k.item_entry, k.epos, k.hit, k.miss,
-                       k.counters, ps ? ps->spos : nullptr, k.wide);
+  launch_key_partition(st, n, items, k.item_slot, k.slot_entry, k.item_entry, k.epos, k.hit, k.miss, k.counters,
+                       ps ? ps->spos : nullptr, k.wide);
   return PRAOS_OK;
 }
 void kc_precompute(praos_ctx* c, const RunPlan& P, praos_batch::KeyCache& k, const uint8_t* keys, int kind,
@@ -163,7 +161,11 @@ struct Run {
   hipStream_t sV;               // Praos stage V
   hipStream_t sVk[2];           // staged TPraos: stage V of the two certificates
   uint16_t *bo, *bk, *bv;       // the chains' bit arrays
-  dim3 g, blk, gl, bl;          // n items in blocks of NT; of lat_block(n) for kernels without LDS tables
+  // the kernels' arguments over the whole batch (header mode, verdicts to bo / bk / bv, every
+  // per-launch field zero); a pass changes a copy where a launch differs
+  OcertIn ocert;
+  KesIn kes;
+  VrfIn vrf;
   int32_t* dcls = nullptr;      // TPraos overlay classes (praos_set_overlay)
   bool v_queued = false, vrf_keys_queued = false;
   // pool records of the VRF key cache's entries (k_vrf_keyrec), set once this run's lists are queued;
@@ -188,7 +190,8 @@ static int queue_stage_v(Run& r) {
   praos_batch* b = r.b;
   const size_t n = r.n;
   const RunPlan& P = r.P;
-  const uint32_t* eta = b->eta_tab ? b->eta_tab : c->d_eta0;
+  VrfIn a = r.vrf;
+  a.wave_prio = P.wprio_v;
   if (P.tp_staged) {
     // the two certificates' stage V side by side (own lane tables, mkSeed alphas): a batch
     // below ~300k headers leaves most wave slots empty with one V at a time
@@ -198,8 +201,10 @@ static int queue_stage_v(Run& r) {
     for (int k = 0; k < 2; k++) {
       if (r.sVk[k] != c->stream) HIPCHK(c, hipStreamWaitEvent(r.sVk[k], c->ev[0], 0));
       if (k == 0) HIPCHK(c, hipEventRecord(c->v0_ev, r.sVk[0]));
-      launch_vrf_v(r.sVk[k], n, b->vrf_vk, proof[k], b->slot, eta, c->eta0_neutral, b->eta_idx, vtab[k], mid[k], 0,
-                   SIZE_MAX, P.wprio_v, 1 + k, P.v_ilp4);
+      a.vrf_proof = proof[k];
+      a.tabs = vtab[k];
+      a.tp_seed = 1 + k;
+      launch_vrf_v(r.sVk[k], n, a, mid[k], 0, SIZE_MAX, P.v_ilp4);
     }
     HIPCHK(c, hipEventRecord(c->v1_ev, r.sVk[0]));
     HIPCHK(c, hipEventRecord(c->v_ev, r.sVk[0]));
@@ -207,8 +212,7 @@ static int queue_stage_v(Run& r) {
   } else {
     if (r.sV != c->stream) HIPCHK(c, hipStreamWaitEvent(r.sV, c->ev[0], 0));
     HIPCHK(c, hipEventRecord(c->v0_ev, r.sV));
-    launch_vrf_v(r.sV, n, b->vrf_vk, b->vrf_proof, b->slot, eta, c->eta0_neutral, b->eta_idx, b->tab_vrf,
-                 b->vrf_mid, 0, SIZE_MAX, P.wprio_v, 0, P.v_ilp4);
+    launch_vrf_v(r.sV, n, a, b->vrf_mid, 0, SIZE_MAX, P.v_ilp4);
     HIPCHK(c, hipEventRecord(c->v1_ev, r.sV));
   }
   c->v_timed = true;
@@ -217,11 +221,8 @@ static int queue_stage_v(Run& r) {
 }
 
 static void queue_vrec(Run& r, praos_batch::KeyCache& k) {
-  praos_ctx* c = r.c;
-  praos_batch* b = r.b;
   if (!r.P.vrf_perkey || k.store >= 0 || !k.vrec) return;
-  launch_vrf_keyrec(r.sm_[2], k.counters, k.max_entries, k.entry_rep, b->cold_vk, b->vrf_vk, c->d_pool_hash,
-                    c->d_pool_vrf, c->d_pool_map, c->npools, k.vrec);
+  launch_vrf_keyrec(r.sm_[2], k.counters, k.max_entries, k.entry_rep, r.vrf, k.vrec);
   r.vrec = k.vrec;
 }
 
@@ -237,28 +238,30 @@ static int vrf_key_chain(Run& r, int ncert, const uint8_t* const proof[], uint8_
   const RunPlan& P = r.P;
   hipStream_t sv = r.sv, sm = r.sm_[2];
   praos_batch::KeyCache& k = b->kc[1];
-  int rc = kc_lists(c, b, P, k, n, b->vrf_vk, sv, nullptr, nullptr, 1);
+  int rc = kc_lists(c, b, P, k, n, b->vrf_vk, sv, KeyItems{}, 1);
   if (rc == PRAOS_OK) rc = to_main(r, 2, sv);
   if (rc != PRAOS_OK) return rc;
   if (praos) {
     // (the records head the miss stream: the join and k_vrf_pool follow them there or wait for u_ev)
     queue_vrec(r, k);
-    if (P.pre_join)
-      launch_vrf_pool(sm, n, b->cold_vk, b->vrf_vk, b->vrf_out, c->d_pool_hash, c->d_pool_vrf, c->d_pool_map,
-                      c->npools, r.bv, b->pool_idx, b->pool_sorted, b->leader, b->nonce,
-                      r.vrec ? k.item_entry : nullptr, r.vrec);
+    if (P.pre_join) {
+      VrfIn a = r.vrf;
+      a.rec_entry = r.vrec ? k.item_entry : nullptr;
+      a.rec = r.vrec;
+      launch_vrf_pool(sm, n, a);
+    }
   }
-  for (int q = 0; q < ncert; q++)
-    launch_vrf_u(sm, n, k.miss, k.counters + 2, nullptr, nullptr, nullptr, c->bcomb16, c->btab, b->vrf_vk, proof[q],
-                 b->tab_vrfu, mid[q]);
+  VrfIn a = r.vrf;                               // (stage U reads the key and the certificate's proof)
+  for (int q = 0; q < ncert; q++) {
+    a.vrf_proof = proof[q];
+    launch_vrf_u(sm, n, key_misses(k), c->btab, a, b->tab_vrfu, mid[q]);
+  }
   if (sm != sv) HIPCHK(c, hipEventRecord(c->u_ev, sm));
   kc_precompute(c, P, k, b->vrf_vk, 1, sv, n);
   for (int q = 0; q < ncert; q++) {
-    launch_vrf_u(sv, n, k.hit, k.counters + 1, k.item_entry, k.kt, k.ki, c->bcomb16, c->btab, b->vrf_vk, proof[q],
-                 b->tab_vrfu, mid[q], P.u4, 0);
-    if (k.wide.min_uses)
-      launch_vrf_u(sv, n, k.wide.hit, k.wide.wcnt + 1, k.item_entry, k.wide.wtab, k.ki, c->bcomb16, c->btab,
-                   b->vrf_vk, proof[q], b->tab_vrfu, mid[q], 0, 0, k.wide.entry_wide);
+    a.vrf_proof = proof[q];
+    launch_vrf_u(sv, n, key_hits(k), c->bcomb16, a, mid[q], P.u4);
+    if (k.wide.min_uses) launch_vrf_u(sv, n, key_wide_hits(k), c->bcomb16, a, mid[q], 0, k.wide.entry_wide);
   }
   if (sm != sv && !(praos && P.v_main && P.vm_mode == 2)) HIPCHK(c, hipStreamWaitEvent(sv, c->u_ev, 0));
   r.vrf_keys_queued = true;
@@ -277,49 +280,34 @@ static int pass_ocert(Run& r) {
   praos_batch* b = r.b;
   const size_t n = r.n;
   const RunPlan& P = r.P;
-  const praos_params& pp = c->params;
-  const dim3 g = r.g, blk = r.blk;
   hipStream_t so = r.so, sm = r.sm_[0];
-  uint16_t* bo = r.bo;
-  // With dedup the pass runs over the distinct OCert tuples only (their representatives: list /
-  // count), writes their verdicts to ok_out, and the verdicts fan out to every header carrying
+  // With dedup the pass runs over the distinct OCert tuples only (their representatives: the
+  // items), writes their verdicts to ok_out, and the verdicts fan out to every header carrying
   // them; without it the pass runs over every header (null list, null ok_out) and that is all.
   const bool dedup = P.dedup;
-  const uint32_t* const list = dedup ? b->dd_reps : nullptr;
-  const uint32_t* const count = dedup ? b->dd_counters : nullptr;
-  uint8_t* const ok_out = dedup ? b->dd_ok : nullptr;
+  const KeyItems items = dedup ? KeyItems{b->dd_reps, b->dd_counters} : KeyItems{};
+  OcertIn a = r.ocert;
+  a.ok_out = dedup ? b->dd_ok : nullptr;
   if (dedup) {
     b->dd_used = true;
     HIPCHK(c, hipMemsetAsync(b->dd_slot, 0, 4 * (size_t)b->dd_cap, so));
     HIPCHK(c, hipMemsetAsync(b->dd_counters, 0, 16, so));
-    launch_ocert_dedup(g, blk, so, n, b->cold_vk, b->hot_vk, b->ocert_n, b->ocert_c0, b->ocert_sig, b->dd_cap - 1,
-                       b->dd_slot, b->dd_item_rep, b->dd_reps, b->dd_counters);
+    launch_ocert_dedup(so, n, b->cold_vk, b->hot_vk, b->ocert_n, b->ocert_c0, b->ocert_sig, b->dd_cap - 1, b->dd_slot,
+                       b->dd_item_rep, b->dd_reps, b->dd_counters);
   }
   if (P.kc) {
     praos_batch::KeyCache& k = b->kc[0];
-    int rc = kc_lists(c, b, P, k, n, b->cold_vk, so, list, count, 0);
+    int rc = kc_lists(c, b, P, k, n, b->cold_vk, so, items, 0);
     if (rc == PRAOS_OK) rc = to_main(r, 0, so);
     if (rc != PRAOS_OK) return rc;
     kc_precompute(c, P, k, b->cold_vk, 0, so, n);
-    if (P.ck4)
-      launch_ocert_ck4(so, n, k.hit, k.counters + 1, k.item_entry, k.kt, k.ki, c->bcomb16, b->cold_vk, b->hot_vk,
-                       b->ocert_n, b->ocert_c0, b->ocert_sig, b->slot, pp.slots_per_kes_period, pp.max_kes_evo, bo,
-                       ok_out);
-    else
-      launch_ocert_ck(r.gl, r.bl, so, k.hit, k.counters + 1, k.item_entry, k.kt, k.ki, c->bcomb16, b->cold_vk,
-                      b->hot_vk, b->ocert_n, b->ocert_c0, b->ocert_sig, b->slot, pp.slots_per_kes_period,
-                      pp.max_kes_evo, bo, ok_out, 0);
+    launch_ocert_ck(so, n, key_hits(k), c->bcomb16, a, P.ck4);
     // the misses go to their stream after the hit chain's launches are queued
-    if (P.miss4)
-      launch_ocert4(g, blk, sm, k.miss, k.counters + 2, c->btab, b->cold_vk, b->hot_vk, b->ocert_n, b->ocert_c0,
-                    b->ocert_sig, b->slot, pp.slots_per_kes_period, pp.max_kes_evo, bo, ok_out, b->tab_ocert,
-                    P.miss_prio);
-    else
-      launch_ocert(g, blk, sm, n, k.miss, k.counters + 2, c->btab, b->cold_vk, b->hot_vk, b->ocert_n, b->ocert_c0,
-                   b->ocert_sig, b->slot, pp.slots_per_kes_period, pp.max_kes_evo, bo, ok_out, b->tab_ocert);
+    OcertIn miss = a;
+    miss.wave_prio = P.miss_prio;                // (the ILP-4 form's; k_ocert has no priority)
+    launch_ocert(sm, n, key_misses(k), c->btab, miss, P.miss4);
   } else {
-    launch_ocert(g, blk, so, n, list, count, c->btab, b->cold_vk, b->hot_vk, b->ocert_n, b->ocert_c0,
-                 b->ocert_sig, b->slot, pp.slots_per_kes_period, pp.max_kes_evo, bo, ok_out, b->tab_ocert);
+    launch_ocert(so, n, items, c->btab, a);
   }
   if (dedup) {
     // the fanout reads dd_ok of the misses (main stream) and of the hits (this stream)
@@ -327,8 +315,8 @@ static int pass_ocert(Run& r) {
       (void)hipEventRecord(c->miss_ev[3], sm);
       (void)hipStreamWaitEvent(so, c->miss_ev[3], 0);
     }
-    launch_ocert_fanout(g, blk, so, n, b->dd_item_rep, b->dd_ok, b->slot, b->ocert_c0, pp.slots_per_kes_period,
-                        pp.max_kes_evo, bo);
+    launch_ocert_fanout(so, n, b->dd_item_rep, b->dd_ok, b->slot, b->ocert_c0, a.slots_per_kes_period, a.max_kes_evo,
+                        r.bo);
   }
   return PRAOS_OK;
 }
@@ -339,51 +327,32 @@ static int pass_kes(Run& r) {
   praos_batch* b = r.b;
   const size_t n = r.n;
   const RunPlan& P = r.P;
-  const praos_params& pp = c->params;
-  const dim3 g = r.g, blk = r.blk;
   hipStream_t sk = r.sk, sm = r.sm_[1];
-  uint16_t* bk = r.bk;
   if (!P.kc) {
-    launch_kes(g, blk, sk, n, (const uint32_t*)nullptr, (const uint32_t*)nullptr, c->btab, b->hot_vk, b->kes_sig,
-               b->body_off, b->body_len, b->body, b->body_bytes_len, b->slot, b->ocert_c0, pp.slots_per_kes_period,
-               (const uint32_t*)nullptr, bk, (uint8_t*)nullptr, b->tab_kes);
+    launch_kes(sk, n, KeyItems{}, c->btab, r.kes);
     return PRAOS_OK;
   }
   // leaf-key cache: the Ed25519 key a Sum6KES signature ends on repeats for every
   // header a pool signs in one KES period
   praos_batch::KeyCache& k = b->kc[2];
-  launch_kes_leafkeys(g, blk, sk, n, b->kes_sig, b->slot, b->ocert_c0, pp.slots_per_kes_period, b->kes_leaf);
+  launch_kes_leafkeys(sk, n, r.kes, b->kes_leaf);
   // (the lists of the KES pass run over every header)
-  int rc = kc_lists(c, b, P, k, n, b->kes_leaf, sk, nullptr, nullptr, 2);
+  int rc = kc_lists(c, b, P, k, n, b->kes_leaf, sk, KeyItems{}, 2);
   if (rc == PRAOS_OK) rc = to_main(r, 1, sk);
   if (rc != PRAOS_OK) return rc;
-  if (P.miss4)
-    launch_kes4(g, blk, sm, k.miss, k.counters + 2, c->btab, b->hot_vk, b->kes_sig, b->body_off, b->body_len,
-                b->body, b->body_bytes_len, b->slot, b->ocert_c0, pp.slots_per_kes_period, bk, b->tab_kes,
-                P.miss_prio);
-  else
-    launch_kes(g, blk, sm, n, k.miss, k.counters + 2, c->btab, b->hot_vk, b->kes_sig, b->body_off, b->body_len,
-               b->body, b->body_bytes_len, b->slot, b->ocert_c0, pp.slots_per_kes_period, (const uint32_t*)nullptr,
-               bk, (uint8_t*)nullptr, b->tab_kes);
+  KesIn miss = r.kes;
+  miss.wave_prio = P.miss_prio;                  // (the ILP-4 form's; k_kes has no priority)
+  launch_kes(sm, n, key_misses(k), c->btab, miss, P.miss4);
   // Merkle path dedup: a pool's headers of one KES period carry the same hot key, period and
   // six vk pairs, so each cache entry's representative walks once and equal paths reuse it.
   // The walks stay on the KES stream ahead of the key precompute: on the miss stream, on a
   // stream of their own or behind the misses, with k_kes_ck waiting for their event, the 432k
   // step was 0.06-0.09 ms longer (profiles/r08_perkey_ab.json, kes_walks_placement)
-  if (P.kes_dd)
-    launch_kes_merkle_reps(sk, k.counters, k.max_entries, k.entry_rep, b->hot_vk, b->kes_sig, b->slot, b->ocert_c0,
-                           pp.slots_per_kes_period, k.rep_ok);
+  if (P.kes_dd) launch_kes_merkle_reps(sk, k.counters, k.max_entries, k.entry_rep, r.kes, k.rep_ok);
   kc_precompute(c, P, k, b->kes_leaf, 0, sk, n);
   HIPCHK(c, hipEventRecord(c->kc0_ev, sk));
-  if (P.kes_ck4)
-    launch_kes_ck4(sk, n, k.hit, k.counters + 1, k.item_entry, k.kt, k.ki, c->bcomb16, b->hot_vk, b->kes_sig,
-                   b->body_off, b->body_len, b->body, b->body_bytes_len, b->slot, b->ocert_c0,
-                   pp.slots_per_kes_period, bk);
-  else
-    launch_kes_ck(r.gl, r.bl, sk, k.hit, k.counters + 1, k.item_entry, k.kt, k.ki, c->bcomb16, b->hot_vk, b->kes_sig,
-                  b->body_off, b->body_len, b->body, b->body_bytes_len, b->slot, b->ocert_c0,
-                  pp.slots_per_kes_period, bk, P.kes_pair_min, P.kes_dd ? k.entry_rep : nullptr,
-                  P.kes_dd ? k.rep_ok : nullptr, 0);
+  launch_kes_ck(sk, n, key_hits(k), c->bcomb16, r.kes, P.kes_pair_min, P.kes_dd ? k.entry_rep : nullptr,
+                P.kes_dd ? k.rep_ok : nullptr, P.kes_ck4);
   HIPCHK(c, hipEventRecord(c->kc1_ev, sk));
   c->kes_ck_timed = true;
   return PRAOS_OK;
@@ -397,25 +366,25 @@ static int after_v(Run& r, hipStream_t st) {
   return PRAOS_OK;
 }
 
-// stage F (U + join) over a list: uncached (k null), against the key tables, or the wide tier's
-static void vrf_fin(Run& r, hipStream_t st, const uint32_t* list, const uint32_t* count,
-                    const praos_batch::KeyCache* k, bool wide = false) {
-  praos_ctx* c = r.c;
-  praos_batch* b = r.b;
-  launch_vrf_fin(st, r.n, list, count, k ? k->item_entry : nullptr, k ? (wide ? k->wide.wtab : k->kt) : nullptr,
-                 k ? k->ki : nullptr, c->bcomb16, c->btab, b->cold_vk, b->vrf_vk, b->vrf_out, b->vrf_proof,
-                 c->d_pool_hash, c->d_pool_vrf, c->d_pool_map, c->npools, (int)c->params.vrf_check_output, r.bv,
-                 b->pool_idx, b->pool_sorted, b->beta, b->leader, b->nonce, b->tab_vrf, b->vrf_mid,
-                 wide ? k->wide.entry_wide : nullptr, k ? r.vrec : nullptr);
+// stage F (U + join): over a list of uncached keys, or over a cache's hits (against the key tables,
+// or the wide tier's), with the entries' pool records when the run has them
+static void vrf_fin_nc(Run& r, hipStream_t st, KeyItems items) {
+  launch_vrf_fin(st, r.n, items, r.c->btab, r.vrf, r.b->vrf_mid);
+}
+static void vrf_fin(Run& r, hipStream_t st, const praos_batch::KeyCache& k, bool wide = false) {
+  VrfIn a = r.vrf;
+  a.rec = r.vrec;
+  launch_vrf_fin(st, r.n, wide ? key_wide_hits(k) : key_hits(k), r.c->bcomb16, a, r.b->vrf_mid,
+                 wide ? k.wide.entry_wide : nullptr);
 }
 
 static void vrf_join(Run& r, hipStream_t st) {
-  praos_ctx* c = r.c;
-  praos_batch* b = r.b;
-  launch_vrf_join(st, r.n, b->cold_vk, b->vrf_vk, b->vrf_out, b->vrf_proof, c->d_pool_hash, c->d_pool_vrf,
-                  c->d_pool_map, c->npools, (int)c->params.vrf_check_output, r.bv, b->pool_idx, b->pool_sorted, b->beta,
-                  b->leader, b->nonce, b->vrf_mid, r.P.wprio_v, r.P.pre_join ? 1 : 0,
-                  r.vrec && r.P.kc ? b->kc[1].item_entry : nullptr, r.vrec);
+  VrfIn a = r.vrf;
+  a.wave_prio = r.P.wprio_v;
+  a.pre = r.P.pre_join ? 1 : 0;
+  a.rec_entry = r.vrec && r.P.kc ? r.b->kc[1].item_entry : nullptr;
+  a.rec = r.vrec;
+  launch_vrf_join(st, r.n, a, r.b->vrf_mid);
 }
 
 // Praos VRF, two stages (k_vrf_stage.hip): V over every header on its own stream, from ev[0] on
@@ -439,8 +408,7 @@ static int pass_vrf_praos(Run& r) {
     if (P.kc) {
       if (!r.vrf_keys_queued && (rc = praos_vrf_keys(r)) != PRAOS_OK) return rc;
     } else {
-      launch_vrf_u(sv, r.n, nullptr, nullptr, nullptr, nullptr, nullptr, c->bcomb16, c->btab, b->vrf_vk,
-                   b->vrf_proof, b->tab_vrfu, b->vrf_mid);
+      launch_vrf_u(sv, r.n, KeyItems{}, c->btab, r.vrf, b->tab_vrfu, b->vrf_mid);
     }
     if (P.v_main && P.vm_mode == 3) {  // V on the main stream, the join on the VRF stream after U
       HIPCHK(c, hipEventRecord(c->v_ev, c->stream));
@@ -457,7 +425,7 @@ static int pass_vrf_praos(Run& r) {
     }
   } else if (P.kc) {
     praos_batch::KeyCache& k = b->kc[1];
-    rc = kc_lists(c, b, P, k, r.n, b->vrf_vk, sv, nullptr, nullptr, 1);
+    rc = kc_lists(c, b, P, k, r.n, b->vrf_vk, sv, KeyItems{}, 1);
     if (rc == PRAOS_OK) rc = to_main(r, 2, sv);
     if (rc != PRAOS_OK) return rc;
     // the entries' pool records: on the miss stream ahead of its wait for stage V, off the chain
@@ -466,7 +434,7 @@ static int pass_vrf_praos(Run& r) {
     const bool vrec_wait = r.vrec && sm != sv;
     if (vrec_wait) HIPCHK(c, hipEventRecord(c->vrec_ev, sm));
     if ((rc = after_v(r, sm)) != PRAOS_OK) return rc;
-    vrf_fin(r, sm, k.miss, k.counters + 2, nullptr);
+    vrf_fin_nc(r, sm, key_misses(k));
     kc_precompute(c, P, k, b->vrf_vk, 1, sv, r.n);
     if (k.wide.min_uses && sm != sv) {
       // two hit lists, and this is the step's tail: the chunk tier's few waves run beside the wide
@@ -475,19 +443,19 @@ static int pass_vrf_praos(Run& r) {
       // alternating runs, lower in every pair; profiles/r07_wide_ab.json)
       HIPCHK(c, hipEventRecord(c->u_ev, sv));
       HIPCHK(c, hipStreamWaitEvent(sm, c->u_ev, 0));
-      vrf_fin(r, sm, k.hit, k.counters + 1, &k);
+      vrf_fin(r, sm, k);
       if ((rc = after_v(r, sv)) != PRAOS_OK) return rc;
       if (vrec_wait) HIPCHK(c, hipStreamWaitEvent(sv, c->vrec_ev, 0));
-      vrf_fin(r, sv, k.wide.hit, k.wide.wcnt + 1, &k, true);
+      vrf_fin(r, sv, k, true);
     } else {
       if ((rc = after_v(r, sv)) != PRAOS_OK) return rc;
       if (vrec_wait) HIPCHK(c, hipStreamWaitEvent(sv, c->vrec_ev, 0));
-      if (k.wide.min_uses) vrf_fin(r, sv, k.wide.hit, k.wide.wcnt + 1, &k, true);
-      vrf_fin(r, sv, k.hit, k.counters + 1, &k);
+      if (k.wide.min_uses) vrf_fin(r, sv, k, true);
+      vrf_fin(r, sv, k);
     }
   } else {
     if ((rc = after_v(r, sv)) != PRAOS_OK) return rc;
-    vrf_fin(r, sv, nullptr, nullptr, nullptr);
+    vrf_fin_nc(r, sv, KeyItems{});
   }
   return PRAOS_OK;
 }
@@ -500,13 +468,9 @@ static int pass_vrf_tpraos(Run& r) {
   praos_ctx* c = r.c;
   praos_batch* b = r.b;
   const size_t n = r.n;
-  const praos_params& pp = c->params;
   hipStream_t sv = r.sv;
   if (!r.P.tp_staged) {
-    launch_vrf_tp(r.g, r.blk, sv, n, c->btab, b->cold_vk, b->vrf_vk, b->vrf_out, b->vrf_proof, b->lead_out,
-                  b->lead_proof, b->slot, b->eta_tab ? b->eta_tab : c->d_eta0, c->eta0_neutral, c->d_pool_hash,
-                  c->d_pool_vrf, c->d_pool_map, c->npools, (int)pp.vrf_check_output, r.bv, b->pool_idx, b->pool_sorted,
-                  b->beta, b->beta_l, b->nonce, b->tab_vrf, r.dcls, c->d_gen, b->eta_idx);
+    launch_vrf_tp(sv, n, c->btab, r.vrf, b->lead_out, b->lead_proof, b->beta_l, r.dcls, c->d_gen);
     return PRAOS_OK;
   }
   int rc;
@@ -518,16 +482,21 @@ static int pass_vrf_tpraos(Run& r) {
   if (r.P.kc) {
     if ((rc = vrf_key_chain(r, 2, proof, mid, false)) != PRAOS_OK) return rc;
   } else {
-    for (int q = 0; q < 2; q++)
-      launch_vrf_u(sv, n, nullptr, nullptr, nullptr, nullptr, nullptr, c->bcomb16, c->btab, b->vrf_vk, proof[q],
-                   b->tab_vrfu, mid[q]);
+    VrfIn a = r.vrf;
+    for (int q = 0; q < 2; q++) {
+      a.vrf_proof = proof[q];
+      launch_vrf_u(sv, n, KeyItems{}, c->btab, a, b->tab_vrfu, mid[q]);
+    }
   }
   if (sv != r.sVk[0]) HIPCHK(c, hipStreamWaitEvent(sv, c->v_ev, 0));
   if (sv != r.sVk[1]) HIPCHK(c, hipStreamWaitEvent(sv, c->v2_ev, 0));
-  for (int q = 0; q < 2; q++)
-    launch_vrf_join_tp(sv, n, q, b->cold_vk, b->vrf_vk, outv[q], proof[q], c->d_pool_hash, c->d_pool_vrf,
-                       c->d_pool_map, c->npools, (int)pp.vrf_check_output, r.bv, b->pool_idx, b->pool_sorted, beta[q],
-                       b->nonce, mid[q], r.dcls, c->d_gen);
+  VrfIn a = r.vrf;
+  for (int q = 0; q < 2; q++) {
+    a.vrf_out = outv[q];
+    a.vrf_proof = proof[q];
+    a.beta_out = beta[q];
+    launch_vrf_join_tp(sv, n, q, a, mid[q], r.dcls, c->d_gen);
+  }
   return PRAOS_OK;
 }
 
@@ -574,10 +543,37 @@ int batch_run_impl(praos_ctx* c, praos_batch* b) {
   r.bo = b->bits3;
   r.bk = b->bits3 + n;
   r.bv = b->bits3 + 2 * n;
-  r.g = dim3(nblocks(n, NT));
-  r.blk = dim3(NT);
-  r.gl = dim3(nblocks(n, lat_block(n)));
-  r.bl = dim3(lat_block(n));
+  {
+    const praos_params& pp = c->params;
+    OcertIn& o = r.ocert;
+    o = OcertIn{};
+    o.cold_vk = b->cold_vk;
+    o.hot_vk = b->hot_vk;
+    o.ocert_n = b->ocert_n;
+    o.ocert_c0 = b->ocert_c0;
+    o.sig = b->ocert_sig;
+    o.slot = b->slot;
+    o.slots_per_kes_period = pp.slots_per_kes_period;
+    o.max_kes_evo = pp.max_kes_evo;
+    o.bits = r.bo;
+    o.tabs = b->tab_ocert;
+    r.kes = batch_kes_in(b, pp.slots_per_kes_period, r.bk);
+    VrfIn& v = r.vrf;
+    v = batch_vrf_v_in(c, b);
+    v.cold_vk = b->cold_vk;
+    v.vrf_out = b->vrf_out;
+    v.pool_hash = c->d_pool_hash;
+    v.pool_vrf = c->d_pool_vrf;
+    v.pool_map = c->d_pool_map;
+    v.npools = c->npools;
+    v.check_output = (int)pp.vrf_check_output;
+    v.bits = r.bv;
+    v.pool_idx = b->pool_idx;
+    v.pool_sorted_idx = b->pool_sorted;
+    v.beta_out = b->beta;
+    v.leader_out = b->leader;
+    v.nonce_out = b->nonce;
+  }
   const bool conc = c->concurrent != 0;
   r.so = conc ? c->side[0] : c->stream;
   r.sk = conc ? c->side[1] : c->stream;
@@ -651,8 +647,8 @@ int batch_run_impl(praos_ctx* c, praos_batch* b) {
       HIPCHK(c, hipStreamWaitEvent(c->stream, c->mdone_ev[k], 0));
     }
   }
-  launch_leader(r.g, r.blk, c->stream, n, b->tp_only ? b->lead_out : b->leader, b->pool_sorted, c->d_pool_x,
-                (const uint32_t*)nullptr, (int)c->params.f_is_one, b->tp_only ? 16 : 8, r.bo, r.bk, r.bv, b->bits,
+  launch_leader(dim3(nblocks(n, NT)), dim3(NT), c->stream, n, b->tp_only ? b->lead_out : b->leader, b->pool_sorted,
+                c->d_pool_x, (const uint32_t*)nullptr, (int)c->params.f_is_one, b->tp_only ? 16 : 8, r.bo, r.bk, r.bv, b->bits,
                 (uint8_t*)nullptr, (int32_t*)nullptr, b->from_bytes ? b->dec_status : (const uint16_t*)nullptr);
   HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
   HIPCHK(c, hipGetLastError());

@@ -369,7 +369,6 @@ static int verify_bytes_pipelined(praos_ctx* c, const praos_header_bytes* in, pr
     const int rc = ensure_bcomb16(c);
     if (rc != PRAOS_OK) return rc;
   }
-  const uint32_t* eta = b->eta_tab ? b->eta_tab : c->d_eta0;
   // stage V chunk by chunk under the upload, or (submitted calls, PRAOS_STREAM_CHUNK_V=0) in the
   // run over the whole batch
   const bool vrf = (c->kernels & 4) != 0 && (!async || c->knobs.stream_chunk_v);
@@ -393,8 +392,7 @@ static int verify_bytes_pipelined(praos_ctx* c, const praos_header_bytes* in, pr
       // each other (a chunk's V alone is latency-bound)
       hipStream_t sv = (k & 1) ? c->vstream2 : c->vstream;
       HIPCHK(c, hipStreamWaitEvent(sv, c->done_ev[k], 0));
-      launch_vrf_v(sv, n, b->vrf_vk, b->vrf_proof, b->slot, eta, c->eta0_neutral, b->eta_idx, b->tab_vrf,
-                   b->vrf_mid, lo[k], lo[k + 1], 0, 0, sched_v_ilp4(c->knobs, n));
+      launch_vrf_v(sv, n, batch_vrf_v_in(c, b), b->vrf_mid, lo[k], lo[k + 1], sched_v_ilp4(c->knobs, n));
       HIPCHK(c, hipGetLastError());
     }
   }

@@ -31,3 +31,18 @@ def corrupt(b: bytes, k: int) -> bytes:
     i = k % len(b)
     b[i] = (b[i] + 1) & 0xFF
     return bytes(b)
+
+
+def _context_under(env):
+    """a context opened with env set (the schedule's knobs are read when a context opens)"""
+    import praos_hip
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return praos_hip.Context(0)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v

@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+from helpers import _context_under
+
 pytestmark = pytest.mark.gpu
 
 
@@ -372,21 +374,6 @@ def test_schedule_variants_equal_single_batch(ctx, c5_batch, env, concurrent):
                 assert np.array_equal(D1[k], D2[k]), (chunks, k)
     finally:
         c2.close()
-
-
-def _context_under(env):
-    """a context opened with env set (the schedule's knobs are read when a context opens)"""
-    import praos_hip
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return praos_hip.Context(0)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
 
 
 # every auto knob at the value it takes at 432,000 headers (csrc/sched.hpp plan_run; tests/test_sched_plan.py

@@ -16,7 +16,7 @@ import os
 import sys
 from collections import defaultdict
 
-KERNELS = ("k_ocert", "k_ocert_ck", "k_kes", "k_kes_ck", "k_kes_leafkeys", "k_vrf", "k_vrf_ck", "k_vrf_v", "k_vrf_fin",
+KERNELS = ("k_ocert", "k_ocert_ck", "k_kes", "k_kes_ck", "k_kes_leafkeys", "k_vrf", "k_vrf_v", "k_vrf_fin",
            "k_vrf_fin_nc", "k_vrf_tp", "k_leader", "k_key_precompute", "k_key_tables", "k_decode_praos", "k_synth_headers")
 
 
